@@ -17,6 +17,13 @@ its slot shard only.  --weak runs --clients-per-gpu clients on EVERY rank instea
 A step = one round on device-resident inputs: seed-schedule launch +
 row-sum/unmask launch (+ RCCL reduce-scatter of the L-slot partial for G > 1).
 value = algorithmic bytes (4*|U|*L read + 4*L written) / max-over-ranks time.
+
+A plain run sets up, settles the clock, warms up, times the K steps, checks out == |U| and
+prints the line.  --dump-outputs DIR also writes the last timed round's output vector to
+DIR/out.npy (see dump_outputs).  --full adds every other leg after the timed steps: windows of
+the output against the C oracle, the same-run ChaCha and HBM ceilings, the pairs-only variant,
+mask expansion, the device-group leg, the other BASELINE configs, the PCIe-inclusive round, the
+CPU baselines and the live PMC traffic passes (each with its own --no-* switch).
 """
 from __future__ import annotations
 
@@ -66,6 +73,13 @@ def parse():
     ap.add_argument("--settle-ms", type=float, default=200.0,
                     help="untimed rounds before the warm-up until this much GPU time has passed: MI355X ramps its "
                          "clock over ~100 ms of load (tools/probes/tail_probe.py, DESIGN.md section 6)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the round's output "
+                         "vector, this rank's slots) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: oracle parity, same-run ceilings, CPU "
+                         "baselines, other configs, PCIe-inclusive rounds, the device-group leg, live PMC traffic "
+                         "(the --no-* options below drop single legs of a --full run)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-copy", action="store_true", help="skip the PCIe-inclusive measurement")
     ap.add_argument("--no-variants", action="store_true", help="skip the pairs-only variant")
@@ -187,6 +201,22 @@ def oracle_windows(torch, dist, rows, out_mine, lo, G, rank, seeds, signs, L, co
             "what": "oracle/flamingo_oracle.c aggregate_unmask over the first and last slots of every rank's shard "
                     "(row sums all-reduced over the ranks), bit-exact against the GPU output, outside the timed "
                     "region"}
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # all files of one --dump-outputs directory together
+
+
+def dump_outputs(d, out, rank, G):
+    """--dump-outputs DIR: what the last timed round returned to its caller -- this rank's slots
+    [lo, hi) of the unmasked sum, uint32 per slot -- as float64 (exact for every uint32) in
+    DIR/out.npy (one GPU) or DIR/out_rank<r>.npy (G ranks).  A vector that would not fit the
+    directory's DUMP_MAX_BYTES is written as a fixed sample: the slots PCG64(0) picks, in order."""
+    os.makedirs(d, exist_ok=True)
+    v = out.cpu().numpy().view(np.uint32)
+    cap = DUMP_MAX_BYTES // (8 * G) - 16       # float64 per slot, the .npy header left out of the data
+    if v.size > cap:
+        v = v[np.sort(np.random.Generator(np.random.PCG64(0)).choice(v.size, cap, replace=False))]
+    np.save(os.path.join(d, "out.npy" if G == 1 else f"out_rank{rank}.npy"), v.astype(np.float64))
 
 
 def group_leg_main(args):
@@ -381,7 +411,11 @@ def main():
     if G > 1:
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
     ok = bool(okt.item())
-    xch = time_exchange(torch, dist, rnd, stream, coll_dev, L) if G > 1 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, G)
+    # every leg below the headline runs only with --full (never in a --profile child)
+    extra = args.full and not args.profile
+    xch = time_exchange(torch, dist, rnd, stream, coll_dev, L) if G > 1 and extra else None
     # every rank's dominant-kernel time: the line shows the imbalance between ranks
     k_all = [kms]
     if G > 1:
@@ -391,7 +425,7 @@ def main():
         k_all = [float(x.item()) for x in k_all]
     # in-run parity of the timed round: windows of every rank's shard against the C oracle
     parity = None
-    if not args.profile:
+    if extra:
         parity = oracle_windows(torch, dist, rows_on, out, rnd.lo, G, rank, d_seeds, d_signs, L, coll_dev)
 
     ms_per_step = elapsed / args.steps * 1e3
@@ -444,29 +478,29 @@ def main():
                                           "2.38 GHz)"},
     }
 
-    if not args.profile:
+    if extra:
         ceil = mask_only_ceiling(eng, torch, d_seeds, d_signs, L, rnd.lo, rnd.hi, stream)
         res["roofline_valu"]["same_run_ceiling"] = ceil
         res["roofline_valu"]["measured_chacha_ceiling_gwords"] = ceil["mask_gwords_per_s"]
         res["roofline_valu"]["frac_of_same_run_ceiling"] = round(
             words / (kms * 1e-3) / 1e9 / ceil["mask_gwords_per_s"], 4)
-    cpi = committed_cpi()
+    cpi = committed_cpi() if args.full else None
     if cpi is not None:
         res["roofline_valu"]["pmc"] = cpi
-    tr = committed_traffic(rows_rank, L, int(K))
+    tr = committed_traffic(rows_rank, L, int(K)) if args.full else None
     if tr is not None:
         res["roofline"]["traffic"] = tr["bytes"]
         res["roofline"]["traffic_source"] = tr["source"]
-    if not args.profile:
+    if extra:
         pk = practical_peak(eng, torch, rows_on, L, stream)
         res["roofline"]["practical_peak"] = pk
         res["roofline"]["frac_of_practical_peak"] = round(ach_gbs / pk["GB/s"], 4)
     if G > 1:
         res["scaling_check"] = scaling_check(G, strong, N, L, k_all, value, bytes_round,
                                              eng.comm_size()[0] if rnd.comm == "rccl" else None, rnd.comm)
-    if rank == 0 and G == 1 and not args.profile and not args.no_prg_expand:
+    if rank == 0 and G == 1 and extra and not args.no_prg_expand:
         res["prg_expand"] = measure_prg_expand(eng, torch, stream, res["roofline_valu"].get("measured_chacha_ceiling_gwords"))
-    if not args.profile and not args.no_variants:
+    if extra and not args.no_variants:
         # every rank at once (each over its own rows and its own slot shard), rank 0 reports
         po = variant_pairs_only(eng, torch, rows_on, nbrs, N, L, stream, P, rnd.lo, rnd.hi)["pairs_only"]
         po["frac_of_practical_peak"] = round(po["GB/s"] / res["roofline"]["practical_peak"]["GB/s"], 4)
@@ -476,7 +510,7 @@ def main():
             dist.all_gather(v_all, vt)
             po["kernel_ms_per_rank"] = [round(float(x.item()), 4) for x in v_all]
         res["variants"] = {"pairs_only": po}
-    if G > 1 and not args.profile and not args.no_cpu:
+    if G > 1 and extra and not args.no_cpu:
         # the reference's CPU path beside the G-GPU number: rank 0 rebuilds every client's row, runs
         # the reference loop on the whole c4 workload and compares it with the gathered shards
         full_out = gather_full_out(torch, dist, out, rnd.S, L, G, coll_dev)
@@ -491,7 +525,7 @@ def main():
             del rows_all, d_cs_a
             torch.cuda.empty_cache()
         dist.barrier()
-    if rank == 0 and G == 1 and not args.profile:
+    if rank == 0 and G == 1 and extra:
         if not args.no_group:
             res["group"] = group_leg_subprocess(args)
         if not args.no_configs:
@@ -526,7 +560,7 @@ def main():
                 res["roofline"]["traffic_committed"] = res["roofline"].get("traffic")
                 res["roofline"]["traffic"] = live["bytes"]
                 res["roofline"]["traffic_source"] = live["source"]
-    if G > 1 and not args.profile and not args.no_pmc:
+    if G > 1 and extra and not args.no_pmc:
         # the same-run HBM traffic of rank 0's kernel (its PMC child runs while the other ranks wait)
         if rank == 0:
             live = live_traffic(args, rows_rank, L, int(K), rank=0, world=G)
@@ -535,10 +569,10 @@ def main():
                 res["roofline"]["traffic"] = live["bytes"]
                 res["roofline"]["traffic_source"] = live["source"]
         dist.barrier()
-    if G > 1 and not args.profile and not args.no_copy:
+    if G > 1 and extra and not args.no_copy:
         res["with_copy"] = with_copy_sharded(torch, dist, rnd, rows_on, d_seeds, d_signs, stream, len(online), L,
                                              coll_dev)
-    if G > 1 and not args.profile and not args.no_configs:
+    if G > 1 and extra and not args.no_configs:
         res["other_configs"] = {"c5": measure_c5_sharded(eng, torch, dist, P, G, rank,
                                                          backend=args.dist_backend, comm=comm)}
     if rank == 0:

@@ -16,7 +16,7 @@ imported by the product path.  Restates, in plain affine integer arithmetic:
   modulus = n), map_to_curve (:233-275), hash_str_to_curve = Q0 + Q1 (:277-283).  Checker for
   flm_hash_to_curve*; its square root takes a^((p+1)/4) first for libnum's sqrtmod (absent here,
   so that root order is "parity unpinned"; every other step is pinned by the h2c points of the
-  reference's own runs in tests/golden/ref_golden.npz and by tests/golden/h2c_golden.json).
+  reference's own runs in tests/golden/ref_golden.NN.npz and by tests/golden/h2c_golden.json).
 
 Pins: tests/test_ec_cpu.py checks this arithmetic against OpenSSL's
 independent P-256 (EC_POINT_mul / EC_POINT_add) and against the group law

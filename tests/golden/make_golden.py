@@ -11,7 +11,7 @@ These vectors are the independent-implementation pin.  The reference's OWN
 code produces the other set: tests/golden/make_ref_golden.py imports
 util/param.py, util/util.py, util/crypto and agent/flamingo/SA_*Agent.py from
 /root/reference under a dependency shim (tests/golden/refshim.py) and records
-whole protocol rounds (ref_golden.json / ref_golden.npz), which
+whole protocol rounds (ref_golden.json / ref_golden.NN.npz), which
 tests/test_ref_golden_{cpu,gpu}.py compare against the oracle and the HIP path.
 
 Outputs:

@@ -19,7 +19,7 @@ No kernel event loop: a stub kernel queues each message and this script
 delivers them in protocol order (VECTORs of the chosen offline clients are
 dropped, which is how a late message looks to the server, :207-224).
 
-Recorded (tests/golden/ref_golden.json + ref_golden.npz):
+Recorded (tests/golden/ref_golden.json + ref_golden.NN.npz, part files of under 1 MiB each):
   * per client and iteration: m_i, the neighbour set in the reference's own
     iteration order, r_ij, h_ijt, s_ij, and the SHA-256 of the masked vector y_i;
   * per iteration on the server: arrival order, recon_symbol in order, the
@@ -352,8 +352,10 @@ def main():
     out["runs"] = runs
     with open(os.path.join(HERE, "ref_golden.json"), "w") as f:
         json.dump(out, f, separators=(",", ":"))
-    np.savez_compressed(os.path.join(HERE, "ref_golden.npz"), **arrays)
-    print("wrote ref_golden.json / ref_golden.npz")
+    sys.path.insert(0, os.path.dirname(HERE))
+    from refgold import save_parts   # part files under 1 MiB each; tests/refgold.load_parts reads them
+    parts = save_parts(os.path.join(HERE, "ref_golden"), arrays)
+    print("wrote ref_golden.json /", " ".join(os.path.basename(p) for p in parts))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 """Shared loaders for the reference-produced fixtures (tests/golden/make_ref_golden.py)."""
 from __future__ import annotations
 
+import glob
 import hashlib
 import json
 import os
@@ -18,9 +19,58 @@ def ref():
         return json.load(f)
 
 
+PART_BYTES = 900_000   # array bytes per part file: the keys are random, so a part compresses to about this
+
+
+def save_parts(prefix: str, arrays: dict, limit: int = PART_BYTES) -> list:
+    """Write `arrays` as prefix.00.npz, prefix.01.npz, ... of at most `limit` array bytes each
+    (every committed fixture stays under 1 MiB).  A larger array is cut along axis 0 into chunks
+    stored as name#0, name#1, ...; load_parts puts them together again."""
+    for old in glob.glob(prefix + ".[0-9][0-9].npz"):
+        os.remove(old)
+    pieces = []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.nbytes <= limit:
+            pieces.append((name, a))
+            continue
+        rows = max(1, limit // (a.nbytes // a.shape[0]))
+        pieces += [(f"{name}#{k}", a[r:r + rows]) for k, r in enumerate(range(0, a.shape[0], rows))]
+    parts, size = [{}], 0
+    for name, a in pieces:
+        if parts[-1] and size + a.nbytes > limit:
+            parts.append({})
+            size = 0
+        parts[-1][name] = a
+        size += a.nbytes
+    paths = [f"{prefix}.{i:02d}.npz" for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
+
+
+def load_parts(prefix: str) -> dict:
+    """The arrays save_parts wrote under `prefix`, chunks concatenated in order."""
+    paths = sorted(glob.glob(prefix + ".[0-9][0-9].npz"))
+    if not paths:
+        raise FileNotFoundError(prefix + ".00.npz")
+    whole, chunks = {}, {}
+    for path in paths:
+        with np.load(path) as z:
+            for key in z.files:
+                if "#" in key:
+                    name, k = key.split("#")
+                    chunks.setdefault(name, {})[int(k)] = z[key]
+                else:
+                    whole[key] = z[key]
+    for name, c in chunks.items():
+        whole[name] = np.concatenate([c[k] for k in range(len(c))])
+    return whole
+
+
 @pytest.fixture(scope="module")
 def refnpz():
-    return dict(np.load(os.path.join(HERE, "golden", "ref_golden.npz")))
+    return load_parts(os.path.join(HERE, "golden", "ref_golden"))
 
 
 def digest(v) -> str:

@@ -97,6 +97,35 @@ def test_pmc_csv_sums_instances_per_dispatch(tmp_path):
     assert bench.pmc_per_dispatch(str(tmp_path / "none"), "FETCH_SIZE") == (None, {})
 
 
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_is_exact_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: uint32 slots as float64, bit for bit (also above 2^31, where the int32 the
+    round computes in is negative); a vector over the directory's byte cap becomes the same
+    seeded sample of its slots in every run; at G > 1 every rank writes a file of its own."""
+    import numpy as np
+    import torch
+    v = np.array([0, 1, 1024, 2**31, 2**32 - 1], np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(v.view(np.int32)), 0, 1)
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 2 * (100 + 16))      # 100 slots for each of 2 ranks
+    big = torch.arange(1000, dtype=torch.int32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 1, 2)
+    b, c = np.load(tmp_path / "b" / "out_rank1.npy"), np.load(tmp_path / "c" / "out_rank1.npy")
+    assert b.shape == (100,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and b.max() < 1000                     # distinct slots, in order
+    assert os.path.getsize(tmp_path / "b" / "out_rank1.npy") * 2 <= 8 * 2 * (100 + 16)
+
+
 def test_pmc_child_env_leaves_the_ranks_group():
     """A rank's profiling child runs as world 1: torchrun's per-rank variables are dropped."""
     env = bench.child_env({"RANK": "0", "WORLD_SIZE": "8", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1",

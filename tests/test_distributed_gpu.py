@@ -39,6 +39,32 @@ def test_sharded_reconstruction(nproc, backend):
     assert "sharded reconstruction ok=True" in r.stdout
 
 
+def test_plain_bench_times_its_steps_and_dumps_its_output(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` (no --full): the headline line with
+    ms_per_step and none of the other legs, and with --dump-outputs the last timed round's output
+    vector, out == |U| in every slot, as float64."""
+    import json
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--log2-L", "16", "--total-clients", "64", "--settle-ms", "0", "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=dict(os.environ, OMP_NUM_THREADS="4"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == 1 and res["steps"] == 3 and res["warmup"] == 1 and res["correct"] is True
+    assert res["unit"] == "GB/s" and res["higher_is_better"] is True and res["dtype"] == "u32"
+    assert res["ms_per_step"] > 0
+    assert abs(res["value"] - (4.0 * 64 + 4.0) * (1 << 16) / (res["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * res["value"] + 0.01
+    for leg in ("cpu_baseline", "other_configs", "group", "variants", "with_copy", "prg_expand", "pair_seed_h2c"):
+        assert leg not in res, leg
+    assert res["checked_against_oracle"] is None and "practical_peak" not in res["roofline"]
+    assert "same_run_ceiling" not in res["roofline_valu"] and "traffic_live" not in res["roofline"]
+    assert os.listdir(tmp_path / "dump") == ["out.npy"]
+    out = np.load(tmp_path / "dump" / "out.npy")
+    assert out.dtype == np.float64 and out.shape == (1 << 16,) and np.all(out == 64.0)
+
+
 def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` (no torchrun around it) starts two ranks itself and reports
     n_gpus 2 from a correct round; gloo lets both ranks share the box's one GPU."""

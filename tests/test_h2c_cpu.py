@@ -3,7 +3,7 @@
 ec_oracle.hash_str_to_curve is what the GPU table (flm_hash_to_curve_decimal) is compared with.
 Pins: the reference's own ecchash.hash_str_to_curve output for every v < 2^16 (table digest and
 sampled points, tests/golden/make_h2c_golden.py) and the h2c points logged inside the reference
-agents' runs (tests/golden/ref_golden.npz, make_ref_golden.py)."""
+agents' runs (tests/golden/ref_golden.NN.npz, make_ref_golden.py)."""
 import json
 import os
 from multiprocessing import Pool

@@ -5,4 +5,6 @@
 # table and the out == |U| invariant across ranks, not the timing.
 mkdir -p gpurun_out
 export HIP_VISIBLE_DEVICES=0
-timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 8 --steps 3 --warmup 1 --dist-backend gloo > gpurun_out/bench_g8_gloo.log 2>&1
+O=${FLM_OUT_DIR:-bench_out}   # where the log goes
+mkdir -p "$O"
+timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 8 --steps 3 --warmup 1 --dist-backend gloo > "$O/bench_g8_gloo.log" 2>&1

@@ -5,9 +5,9 @@
 #   tests        pytest -m gpu (whole GPU suite)          -> gpurun_out/TAG_pytest_gpu.log
 #   tests:EXPR   pytest -m gpu -k EXPR                     -> gpurun_out/TAG_pytest_gpu_k.log
 #   smoke        __graft_entry__.smoke()                   -> gpurun_out/TAG_smoke.log
-#   bench        python bench.py (N=1 default line)        -> gpurun_out/TAG_bench.json/.err
-#   bench2       bench.py --gpus 2 --dist-backend gloo (self-launched ranks sharing the GPU)
-#   benchG:N     bench.py --gpus N --dist-backend gloo --steps 3 (N self-launched ranks on the one GPU:
+#   bench        python bench.py --full (N=1 line, every leg)  -> TAG_bench.json/.err
+#   bench2       bench.py --full --gpus 2 --dist-backend gloo (self-launched ranks sharing the GPU)
+#   benchG:N     bench.py --full --gpus N --dist-backend gloo --steps 3 (N self-launched ranks on the one GPU:
 #                the sharded c4 and c5 paths end to end, correctness only)
 #   sim          ABIDES simulations c1 (n=128) and n=1024 x 2 iterations -> TAG_sim_*.log
 #   simc3 / simc5 / simc5r   the agents at BASELINE c3, c5 (n=4096, L=2^20, 10 iterations, 1 % dropouts), reduced c5
@@ -49,15 +49,15 @@ for step in "$@"; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/${TAG}_smoke.log" 2>&1 || exit 1 ;;
     bench)
-      timeout -k 10 900 python bench.py > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || { tail -20 "$O/${TAG}_bench.err"; exit 1; }
+      timeout -k 10 900 python bench.py --full > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || { tail -20 "$O/${TAG}_bench.err"; exit 1; }
       cat "$O/${TAG}_bench.json" ;;
     bench2)
-      timeout -k 10 600 python bench.py --gpus 2 --dist-backend gloo --no-cpu --no-configs --no-group \
+      timeout -k 10 600 python bench.py --full --gpus 2 --dist-backend gloo --no-cpu --no-configs --no-group \
         > "$O/${TAG}_bench2_gloo.json" 2> "$O/${TAG}_bench2_gloo.err" || { tail -20 "$O/${TAG}_bench2_gloo.err"; exit 1; }
       cat "$O/${TAG}_bench2_gloo.json" ;;
     benchG:*)
       n=${step#benchG:}
-      timeout -k 10 900 python bench.py --gpus "$n" --dist-backend gloo --steps 3 --warmup 1 \
+      timeout -k 10 900 python bench.py --full --gpus "$n" --dist-backend gloo --steps 3 --warmup 1 \
         > "$O/${TAG}_bench_g${n}_gloo.json" 2> "$O/${TAG}_bench_g${n}_gloo.err" || { tail -20 "$O/${TAG}_bench_g${n}_gloo.err"; exit 1; }
       cut -c1-400 "$O/${TAG}_bench_g${n}_gloo.json" ;;
     sim)
