@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <hip/hip_runtime.h>
 
+#include "flm_host_layout.h"
+
 namespace flm {
 
 // b"abcd" as a little-endian word (util/param.py:12).
@@ -182,3 +184,7 @@ void comm_release(flm_ctx *ctx);  // flm_comm.hip: drop the context's communicat
 // then destroy them (flm_group_free)
 void comm_release_clique(flm_ctx *const *ctxs, int n);
 }  // namespace flm
+// The host-copy layout (flm_host_layout.h) of n spans, for the CPU tests: no context, no HIP call.
+// route, pitch and offset get n entries each, *total the bounce bytes.
+extern "C" int flm_host_layout(int n, const uint64_t *width, const uint64_t *rows, const int *may_in_place,
+                               int *route, uint64_t *pitch, uint64_t *offset, uint64_t *total);

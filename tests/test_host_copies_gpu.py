@@ -139,7 +139,20 @@ def test_host_calls_at_the_in_place_boundary():
         for n in (1, 63, (32 << 20) - 1, 32 << 20):
             data = bytes(g.integers(0, 256, n, dtype=np.uint8))
             assert eng.chacha20_encrypt(seeds[0].tobytes(), data) == O.chacha20_encrypt(seeds[0].tobytes(), data), n
-        for K, L in ((2, (4 << 20) - 4), (2, 4 << 20), (1, 7)):  # K x L words: just under, at 32 MiB; tiny
+        # K x L words: just under, at 32 MiB; tiny; K rows in place at a ragged pitch (the rows' pitch
+        # in the bounce buffer is round_up(L, 4) words, the caller's L); and the gap where the packed
+        # K x L x 4 is under 32 MiB and the padded in-place plane is not (DMA through the bounce buffer)
+        for K, L in ((2, (4 << 20) - 4), (2, 4 << 20), (1, 7), (3, 7), (3, 1021), (3, 2796201), (2, (4 << 20) - 1)):
             e = eng.prg_expand(seeds[:K], L)
             for k in range(K):
                 assert np.array_equal(e[k], O.prg(seeds[k].tobytes(), L, 0)), (K, L, k)
+        # two planes (x and y) in the same gap
+        seg2, L = np.array([0, 2, 3], np.int64), (4 << 20) - 1
+        x = g.integers(0, 2**32, (2, L), dtype=np.uint32)
+        assert np.array_equal(eng.client_mask(seg2, seeds, signs, L, x=x), O.client_mask(seg2, seeds, signs, L, x=x))
+        # three rows in place at a ragged pitch, one of them with no seeds
+        seg3 = np.array([0, 1, 1, 3], np.int64)
+        for L in (5, 1021):
+            x = g.integers(0, 2**32, (3, L), dtype=np.uint32)
+            assert np.array_equal(eng.client_mask(seg3, seeds, signs, L, x=x),
+                                  O.client_mask(seg3, seeds, signs, L, x=x)), L
