@@ -905,7 +905,7 @@ struct RowField {
         JacT<E> R;
         R.X = sub(sqr(alpha), add(beta4, beta4));
         R.Z = sub(sub(sqr(add(P.Y, P.Z)), gamma), delta);
-        const E g2 = sqr(gamma), g4 = add(g2, g2), g8 = add(g4, g4);
+        const E g1 = sqr(gamma), g2 = add(g1, g1), g4 = add(g2, g2), g8 = add(g4, g4);  // 8 gamma^2
         R.Y = sub(mul(alpha, sub(beta4, R.X)), g8);
         return R;
     }

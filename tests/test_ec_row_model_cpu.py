@@ -3,7 +3,8 @@ ec_mul_row_kernel) as its Python model tools/ec_row_model.py: the product column
 with its 8x8 coefficient matrix and the signed carry passes give a value congruent mod p and below
 2^256 on random and edge inputs, and the carry loops end after about one pass.  The GPU kernel is
 checked end to end by tests/test_ec_gpu.py (the "row" parametrisation) and bit for bit against Python
-integers by tools/probes/ec_row_probe.py."""
+integers, on edge limbs and exceptional additions, by tests/test_ec_edges_gpu.py (its inputs are
+replayed over this model first by tests/test_ec_cases_cpu.py)."""
 import os
 import sys
 
