@@ -56,6 +56,9 @@ def parse(argv):
     ap.add_argument("--dropout", type=float, default=0.0)
     ap.add_argument("--latency", choices=("cubic", "deterministic"), default="cubic")
     ap.add_argument("--committee_size", type=int, default=P.committee_size)
+    # the clients' m_i dealing and AES-GCM sealing per client on the host, not batched on the GPU
+    # (protocol.configure(gpu_deal=False)): same messages, for A/B timing
+    ap.add_argument("--host_deal", action="store_true")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -102,7 +105,8 @@ def _run(args):
     root = bytes.fromhex(args.root_seed_hex) if args.root_seed_hex else None
     if args.committee_size > args.num_clients:
         raise ValueError("committee_size cannot exceed num_clients")
-    param.configure(root=root, L=args.vector_len, committee=args.committee_size)
+    param.configure(root=root, L=args.vector_len, committee=args.committee_size,
+                    gpu_deal=False if args.host_deal else None)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
     offline_its = offline_schedule(n, args.num_iterations, offline, args.dropout)
     print(f"Silent mode: {log.silent_mode}")

@@ -11,8 +11,11 @@ and sends the masked vector
     y_i = x_i + PRG(m_i) + sum_{j in N(i), j > i} PRG(s_ij) - sum_{j < i} PRG(s_ij)
 
 (:304-324; x_i = all ones, :304).  GPU work: the mask expansion and
-composition (MaskEngine.client_mask) and every batch of P-256 scalar
-multiplications (ECDH, ElGamal, decryption shares: MaskEngine.ec_mul_wire).
+composition (MaskEngine.client_mask), every batch of P-256 scalar
+multiplications (ECDH, ElGamal, decryption shares: MaskEngine.ec_mul_wire),
+and the dealing and AES-GCM sealing of the m_i shares of all clients of an
+iteration (protocol.mi_shares; the host path stays behind
+protocol.configure(gpu_deal=False)).
 Committee members sign the offline set (ECDSA, :351-368) and answer DEC with
 sk_j * c0 for each dropout ciphertext plus their decrypted m_i shares
 (:370-431).
@@ -168,11 +171,15 @@ class SA_ClientAgent(Agent):
             self.committee_keys = self._aes_keys(committee)
 
         # m_i, its Shamir shares, one AES-GCM ciphertext per committee member (:214-244)
-        mi_bytes = bytes(self.random_state.randint(0, 256, size=self.key_length, dtype=np.uint8))
+        # GPU path: the draws happen here all the same (protocol.mi_draw, the host path's order), and
+        # the shares of every client of the iteration are dealt and sealed further down (mi_shares)
+        gpu_deal = param.deal_on_gpu()
+        mi_bytes = param.mi_draw(self, self.current_iteration)[0] if gpu_deal else \
+            bytes(self.random_state.randint(0, 256, size=self.key_length, dtype=np.uint8))
         mi_number = int.from_bytes(mi_bytes, "big")
         threshold = int(param.fraction * len(self.user_committee))
-        shares = shamir_share(mi_number, max(1, threshold), len(committee), self.prime,
-                              rng=_PyRandom(self.random_state))
+        shares = [] if gpu_deal else shamir_share(mi_number, max(1, threshold), len(committee), self.prime,
+                                                  rng=_PyRandom(self.random_state))
         enc_mi_shares = []
         for (_, y), cid in zip(shares, committee):
             nonce = bytes(self.random_state.randint(0, 256, size=16, dtype=np.uint8))
@@ -194,6 +201,8 @@ class SA_ClientAgent(Agent):
         c0 = C.points_from_wire(rg) if nb else []
         c1 = C.points_from_wire(c1w) if nb else []
         cipher = {(self.id, j): (c0[k], c1[k]) for k, j in enumerate(nb)}
+        if gpu_deal:      # after elgamal_masks: every client's r's are drawn before the batch draws for it
+            enc_mi_shares = param.mi_shares(self, self.current_iteration)
 
         x = None if self.input_vector is None else np.asarray(self.input_vector, np.uint32)[None, :]
         vec = param.engine().client_mask(np.array([0, len(seeds)], np.int64), seeds, signs, self.vector_len, x=x)[0]
@@ -222,10 +231,20 @@ class SA_ClientAgent(Agent):
         _, c0w, _ = wire.elgamal_json_to_wire(dec_target_pairwise)
         sk = self.committee_shared_sk[1]
         dec_w, _ = param.engine().ec_mul_wire(c0w, C.scalars_to_wire([sk] * c0w.shape[0]))
-        # decrypt this member's m_i shares (:402-420)
-        dec_mi = []
-        for cid, (ct, nonce) in zip(client_id_list, wire.deserialize_tuples_bytes(dec_target_mi)):
-            dec_mi.append(int.from_bytes(C.aes_gcm_decrypt(self.symmetric_keys[cid], ct, nonce), "big"))
+        # decrypt this member's m_i shares (:402-420): one GPU launch for all of them, or one
+        # OpenSSL context each on the host path
+        sealed = list(zip(client_id_list, wire.deserialize_tuples_bytes(dec_target_mi)))
+        if sealed and param.deal_on_gpu():
+            if len({(len(ct), len(nonce)) for _, (ct, nonce) in sealed}) != 1:
+                raise RuntimeError("m_i share ciphertexts of one DEC differ in length")
+            as_rows = lambda parts: np.frombuffer(b"".join(parts), np.uint8).reshape(len(sealed), -1)  # noqa: E731
+            opened = param.engine().aes_gcm_xor_wire(as_rows(self.symmetric_keys[cid] for cid, _ in sealed),
+                                                     as_rows(nonce for _, (_, nonce) in sealed),
+                                                     as_rows(ct for _, (ct, _) in sealed))
+            dec_mi = [int.from_bytes(row.tobytes(), "big") for row in opened]
+        else:
+            dec_mi = [int.from_bytes(C.aes_gcm_decrypt(self.symmetric_keys[cid], ct, nonce), "big")
+                      for cid, (ct, nonce) in sealed]
         self.sendMessage(self.serviceAgentID, Message({
             "msg": "SHARED_RESULT", "iteration": self.current_iteration, "sender": self.id,
             "shared_result_pairwise": wire.wire_to_ecp_json(dec_w),

@@ -40,11 +40,22 @@ _clients: dict = {}       # id -> client agent (for the batched ElGamal draws)
 _elgamal: dict = {}       # (root, iteration, id) -> (r list, (deg, 64) rG wire, (deg, 64) c1 = H + r pk wire)
 _pair_keys: dict = {}     # (root, N, min(i,j), max(i,j)) -> r_ij = SHA-256(a_i A_j)[:32] (symmetric)
 _pair_mat: dict = {}      # (root, iteration, N, nsize) -> {id: PairMaterial}
+# The clients' m_i shares are dealt and sealed for the whole iteration in two GPU launches
+# (mi_shares); False takes the host path per client (seeds.shamir_share, crypto.aes_gcm_*), which
+# sends byte-identical messages: the A/B switch of tools/deal_bench.py and tests/test_deal_gpu.py.
+_gpu_deal: bool = True    # configure(gpu_deal=...)
+_mi_draws: dict = {}      # (root, iteration, id) -> (m_i bytes, T-1 coefficients, C nonces)
+_mi_shares: dict = {}     # (root, iteration, id) -> [(ciphertext, nonce)] in committee order
 
 
-def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None):
+def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
+              gpu_deal: bool | None = None):
     """Reset the protocol parameters (between simulations / in tests)."""
-    global root_seed, vector_len, committee_size, _h2c_table
+    global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal
+    if gpu_deal is not None:
+        _gpu_deal = bool(gpu_deal)
+    _mi_draws.clear()
+    _mi_shares.clear()
     if root is not None:
         if len(root) != 32:
             raise ValueError("root seed must be 32 bytes")
@@ -345,3 +356,93 @@ def elgamal_masks(agent, iteration: int, nb: list):
         for k in [k for k in _elgamal if k[1] < iteration - 1]:
             del _elgamal[k]
     return _elgamal.pop(key)
+
+
+# ------------------------------------------------ m_i shares: dealt and sealed in one batch
+def deal_on_gpu() -> bool:
+    """True when the clients' m_i shares go through mi_shares (configure(gpu_deal=True), the
+    default).  An engine object that brings no dealing calls (a CPU test double, as for
+    vector_store) leaves the agents on the host path, which sends the same bytes."""
+    return _gpu_deal and hasattr(engine(), "shamir_deal_wire") and hasattr(engine(), "aes_gcm_xor_wire")
+
+
+def _mi_shape(agent) -> tuple:
+    """(threshold T, committee size C) of the m_i dealing (SA_ClientAgent.py:216-220)."""
+    C = len(agent.user_committee)
+    return max(1, int(fraction * C)), C
+
+
+def _draw_mi(agent) -> tuple:
+    """m_i, the T - 1 polynomial coefficients and the C nonces from the client's own random state,
+    in the reference's order (SA_ClientAgent.py:214-240): 32 bytes, 40 bytes mod n per coefficient
+    (client_agent._PyRandom), 16 bytes per nonce.  RandomState.randint(0, 256, dtype=uint8) spends
+    one 32-bit word of the stream per four bytes and keeps none between calls, so with every size a
+    multiple of four ONE draw of all the bytes is the same stream as the 1 + (T - 1) + C separate
+    draws of the host path (tests/test_deal_cpu.py holds the two against each other)."""
+    import numpy as np
+    from .seeds import P256_N
+    T, C = _mi_shape(agent)
+    kl, rs = agent.key_length, agent.random_state
+    if kl % 4 == 0:
+        buf = bytes(rs.randint(0, 256, size=kl + 40 * (T - 1) + 16 * C, dtype=np.uint8))
+    else:
+        buf = b"".join(bytes(rs.randint(0, 256, size=s, dtype=np.uint8)) for s in [kl] + [40] * (T - 1) + [16] * C)
+    o = kl + 40 * (T - 1)
+    return (buf[:kl], [int.from_bytes(buf[kl + 40 * j: kl + 40 * j + 40], "big") % P256_N for j in range(T - 1)],
+            [buf[o + 16 * k: o + 16 * k + 16] for k in range(C)])
+
+
+def mi_draw(agent, iteration: int) -> tuple:
+    """(m_i bytes, coefficients, nonces) of this client in `iteration`: drawn here, where
+    sendVectors reaches SA_ClientAgent.py:214, unless mi_shares' batch drew them for it already."""
+    key = (root_seed, iteration, agent.id)
+    if key not in _mi_draws:
+        _mi_draws[key] = _draw_mi(agent)
+    return _mi_draws[key]
+
+
+def mi_shares(agent, iteration: int) -> list:
+    """This client's enc_mi_shares [(ciphertext, nonce), ...] in committee order
+    (SA_ClientAgent.py:218-244): the Shamir shares of m_i at x = 1..C, each AES-128-GCM encrypted
+    (tag dropped) under the key shared with that member (client_agent._aes_keys).  The first
+    client to ask in an iteration deals every registered, online client's shares in ONE
+    flm_shamir_deal launch and seals them in ONE flm_aes_gcm_xor launch.
+
+    Every client's random state sees the draws of the host path in the same order, so the VECTOR
+    messages stay byte-identical: a client draws its own m_i, coefficients and nonces through
+    mi_draw at the start of sendVectors, and calls this after elgamal_masks, which has by then
+    drawn every client's ElGamal r's; the batch draws here for the clients that have not reached
+    sendVectors yet (their r's come first on the host path too), and they pick those values up
+    from mi_draw instead of drawing again."""
+    import numpy as np
+    key = (root_seed, iteration, agent.id)
+    if key not in _mi_shares:
+        batch = [c for cid, c in sorted(_clients.items())
+                 if iteration not in c.offline_iterations and (root_seed, iteration, cid) not in _mi_shares]
+        if agent.id not in [c.id for c in batch]:
+            batch.append(agent)
+        T, C = _mi_shape(agent)
+        members = sorted(agent.user_committee)
+        if any(c.key_length != 32 or _mi_shape(c) != (T, C) for c in batch):
+            raise RuntimeError("m_i shares are dealt as 32-byte values over one committee")
+        draws = [mi_draw(c, iteration) for c in batch]
+        M = len(batch)
+        coeffs = np.empty((T, M, 32), np.uint8)
+        coeffs[0] = np.frombuffer(b"".join(d[0] for d in draws), np.uint8).reshape(M, 32)
+        if T > 1:
+            coeffs[1:] = np.frombuffer(b"".join(v.to_bytes(32, "big") for d in draws for v in d[1]),
+                                       np.uint8).reshape(M, T - 1, 32).transpose(1, 0, 2)
+        shares = engine().shamir_deal_wire(coeffs, np.arange(1, C + 1, dtype=np.uint32))      # (C, M, 32)
+        for c in batch:
+            if not c.committee_keys:
+                c.committee_keys = c._aes_keys(members)
+        keys = np.frombuffer(b"".join(c.committee_keys[m] for c in batch for m in members), np.uint8).reshape(M * C, 16)
+        nonces = np.frombuffer(b"".join(n for d in draws for n in d[2]), np.uint8).reshape(M * C, 16)
+        ct = engine().aes_gcm_xor_wire(keys, nonces, np.ascontiguousarray(shares.transpose(1, 0, 2)).reshape(M * C, 32))
+        for i, (c, d) in enumerate(zip(batch, draws)):
+            b = ct[i * C:(i + 1) * C].tobytes()
+            _mi_shares[(root_seed, iteration, c.id)] = [(b[32 * k: 32 * k + 32], d[2][k]) for k in range(C)]
+        for cache in (_mi_shares, _mi_draws):
+            for k in [k for k in cache if k[1] < iteration - 1]:
+                del cache[k]
+    return _mi_shares[key]

@@ -2,7 +2,8 @@
 
 The reference shares two secrets this way:
 * each client's self-mask seed m_i, dealt to the committee
-  (SA_ClientAgent.py:214-244) and recovered by the server from the first
+  (SA_ClientAgent.py:214-244; on the GPU, for all clients of an iteration:
+  MaskEngine.shamir_deal_wire through protocol.mi_shares) and recovered by the server from the first
   `threshold` decrypted shares (SA_ServiceAgent.py:506-526; on the GPU:
   MaskEngine.shamir_combine);
 * the system decryption key, dealt by the server at setup

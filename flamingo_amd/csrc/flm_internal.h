@@ -124,6 +124,12 @@ hipError_t launch_ec_mul(const uint8_t *d_points, const uint8_t *d_scalars, int 
 int ec_mul_groups(int T, int terms);
 hipError_t launch_shamir_combine(const uint8_t *d_shares, const uint8_t *d_lambdas, int T, int M, uint8_t *d_out,
                                  hipStream_t stream);
+// d_out[c][i] = sum_j d_coeffs[j][i] xs[c]^j mod n (shamir_deal_kernel): coeffs T x M x 32, out C x M x 32
+hipError_t launch_shamir_deal(const uint8_t *d_coeffs, int T, int M, const uint32_t *d_xs, int C, uint8_t *d_out,
+                              hipStream_t stream);
+// d_out = d_in ^ AES-128-GCM keystream of (key i, nonce i), n messages of len bytes (aes_gcm_xor_kernel)
+hipError_t launch_aes_gcm_xor(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_in,
+                              uint8_t *d_out, uint32_t len, int n, hipStream_t stream);
 hipError_t launch_ec_finish(const uint8_t *d_base, const uint32_t *d_jac, int T, int D, int negate,
                             uint8_t *d_points_out, uint8_t *d_digests_out, uint32_t *d_flags, hipStream_t stream);
 // hash_str_to_curve of n messages (d_msgs: n x 64 bytes + d_lens), or of the decimal strings of

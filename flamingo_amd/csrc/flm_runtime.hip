@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/flamingo_hip.h"
+#include "flm_deal_args.h"
 #include "flm_internal.h"
 
 using flm::Item;
@@ -1417,7 +1418,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.4 gfx950 items_kernel<S={1,4,16}>"; }
+const char *flm_version(void) { return "flamingo_hip 0.5 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor)"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -2019,6 +2020,78 @@ int flm_shamir_combine(flm_ctx *ctx, const uint8_t *shares, const uint8_t *lambd
     if (int rc = hc.begin()) return rc;
     FLM_HIP(ctx, flm::launch_shamir_combine(ctx->ec_in.as<uint8_t>(), ctx->ec_scal.as<uint8_t>(), T, M,
                                             ctx->ec_dig.as<uint8_t>(), s));
+    return hc.finish();
+}
+
+int flm_shamir_deal_dev(flm_ctx *ctx, const uint8_t *d_coeffs, int T, int M, const uint32_t *d_xs, int C,
+                        uint8_t *d_shares_out, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::shamir_deal_dims_error(T, M, C))
+        return fail(ctx, FLM_EINVAL, "shamir deal (T=%d, M=%d, C=%d): %s", T, M, C, why);
+    if (M == 0) return 0;
+    if (!d_coeffs || !d_xs || !d_shares_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (((uintptr_t)d_coeffs | (uintptr_t)d_shares_out) & 15)
+        return fail(ctx, FLM_EINVAL, "coeffs and shares_out must be 16-byte aligned");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_shamir_deal(d_coeffs, T, M, d_xs, C, d_shares_out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_shamir_deal(flm_ctx *ctx, const uint8_t *coeffs, int T, int M, const uint32_t *xs, int C,
+                    uint8_t *shares_out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::shamir_deal_dims_error(T, M, C))
+        return fail(ctx, FLM_EINVAL, "shamir deal (T=%d, M=%d, C=%d): %s", T, M, C, why);
+    if (!xs) return fail(ctx, FLM_EINVAL, "NULL argument");
+    const int zero = flm::rt::shamir_deal_zero_x(xs, C);
+    if (zero >= 0) return fail(ctx, FLM_EINVAL, "xs[%d] is 0: a share at x = 0 would be the secret itself", zero);
+    if (M == 0) return 0;
+    if (!coeffs || !shares_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    hipStream_t s = ctx->stream;
+    const flm::rt::ShamirDealBytes nb = flm::rt::shamir_deal_bytes(T, M, C);
+    HostCopies hc(ctx, s);
+    hc.in(coeffs, nb.coeffs, ctx->ec_in);
+    hc.in(xs, nb.xs, ctx->ec_scal);
+    hc.out(shares_out, nb.shares, ctx->ec_out);
+    if (int rc = hc.begin()) return rc;
+    FLM_HIP(ctx, flm::launch_shamir_deal(ctx->ec_in.as<uint8_t>(), T, M, ctx->ec_scal.as<uint32_t>(), C,
+                                         ctx->ec_out.as<uint8_t>(), s));
+    return hc.finish();
+}
+
+int flm_aes_gcm_xor_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
+                        const uint8_t *d_in, uint8_t *d_out, size_t len, int n, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::aes_gcm_dims_error(nonce_len, len, n))
+        return fail(ctx, FLM_EINVAL, "aes gcm xor (nonce_len=%d, len=%zu, n=%d): %s", nonce_len, len, n, why);
+    if (n == 0) return 0;
+    if (!d_keys || !d_nonces || !d_in || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_aes_gcm_xor(d_keys, d_nonces, nonce_len, d_in, d_out, (uint32_t)len, n,
+                                         static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *in,
+                    uint8_t *out, size_t len, int n) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::aes_gcm_dims_error(nonce_len, len, n))
+        return fail(ctx, FLM_EINVAL, "aes gcm xor (nonce_len=%d, len=%zu, n=%d): %s", nonce_len, len, n, why);
+    if (n == 0) return 0;
+    if (!keys || !nonces || !in || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    hipStream_t s = ctx->stream;
+    const flm::rt::AesGcmBytes nb = flm::rt::aes_gcm_bytes(nonce_len, len, n);
+    HostCopies hc(ctx, s);
+    hc.in(keys, nb.keys, ctx->ec_scal);
+    hc.in(nonces, nb.nonces, ctx->ec_base);
+    // read and written in place in the bounce buffer when it fits (flm_chacha20_xor); in == out is fine
+    const HostCopies::Span *hi = hc.in(in, nb.data, ctx->bytes_in, HostCopies::kMayRunInPlace);
+    const HostCopies::Span *ho = hc.out(out, nb.data, ctx->bytes_out, HostCopies::kMayRunInPlace);
+    if (int rc = hc.begin()) return rc;
+    FLM_HIP(ctx, flm::launch_aes_gcm_xor(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len,
+                                         hi->as<const uint8_t>(), ho->as<uint8_t>(), (uint32_t)len, n, s));
     return hc.finish();
 }
 

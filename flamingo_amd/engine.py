@@ -13,6 +13,9 @@ numpy/pycryptodomex loops:
   viewed as uint32 (SA_ClientAgent.py:248-250).
 * ``chacha20_encrypt`` -- ChaCha20.new(key, nonce).encrypt(data) for the
   PRF/PRG calls of util/param.py:44-46, 63-76.
+* ``shamir_deal`` / ``aes_gcm_xor_wire`` -- the clients' dealing and AES-GCM sealing of their
+  m_i shares (SA_ClientAgent.py:218-220, 227-244) and the committee's opening of them
+  (:402-420), batched over clients.
 * ``*_dev`` -- the same on device-resident torch tensors (bench, multi-GPU).
 
 Errors surface as RuntimeError with the library's message, like the
@@ -522,6 +525,92 @@ class MaskEngine:
                                              ctypes.c_void_p(seeds_out.data_ptr()), self._stream_handle(stream))
         self._check(rc, "flm_shamir_combine_dev")
         return seeds_out
+
+    def shamir_deal_wire(self, coeffs_w, xs) -> np.ndarray:
+        """flm_shamir_deal on wire arrays: coeffs (T, M, 32) uint8 big endian (term 0 the secrets, any
+        value < 2^256), xs C non-zero points -> shares (C, M, 32) uint8, each < n; row c is ready to
+        be a shares[j] of shamir_combine.  No Python big ints on the way."""
+        cw = np.ascontiguousarray(coeffs_w, np.uint8)
+        if cw.ndim != 3 or cw.shape[2] != 32:
+            raise RuntimeError("coeffs must be (T, M, 32)")
+        T, M = cw.shape[0], cw.shape[1]
+        x = np.asarray(xs)
+        if x.ndim != 1 or (x.size and (x.dtype.kind not in "ui" or x.min() < 0 or x.max() > 0xFFFFFFFF)):
+            raise RuntimeError("xs must be a 1-D sequence of integers below 2^32")
+        x = np.ascontiguousarray(x, np.uint32)
+        out = np.zeros((x.shape[0], M, 32), np.uint8)
+        rc = self.lib.flm_shamir_deal(self.ctx, p_u8(cw), T, M, p_u32(x), x.shape[0], p_u8(out))
+        self._check(rc, "flm_shamir_deal")
+        return out
+
+    def shamir_deal(self, coeffs_by_term, xs) -> list:
+        """y[c][i] = sum_j coeffs_by_term[j][i] * xs[c]^j mod n (SA_ClientAgent.py:218-220, the
+        inverse of shamir_combine).  coeffs_by_term: T sequences of M integers (< 2^256), term 0 the
+        secrets; xs: C non-zero integers (< 2^32).  Returns C lists of M integers."""
+        from .crypto import scalars_to_wire
+        T = len(coeffs_by_term)
+        M = len(coeffs_by_term[0]) if T else 0
+        if any(len(c) != M for c in coeffs_by_term):
+            raise RuntimeError("coefficient lists differ in length")
+        if any(not 0 <= int(v) < (1 << 256) for c in coeffs_by_term for v in c):
+            raise RuntimeError("coefficients must be in [0, 2^256)")
+        if any(not 0 <= int(v) < (1 << 32) for v in xs):
+            raise RuntimeError("xs must be in [1, 2^32)")
+        cw = (np.stack([scalars_to_wire(c) for c in coeffs_by_term]) if T and M
+              else np.zeros((T, M, 32), np.uint8))
+        out = self.shamir_deal_wire(cw, np.array([int(v) for v in xs], np.uint32))
+        return [[int.from_bytes(bytes(r), "big") for r in row] for row in out]
+
+    def shamir_deal_dev(self, coeffs, xs, shares_out, stream=None):
+        """Device form: coeffs (T, M, 32) uint8, xs (C,) int32 (non-zero; read as uint32) CUDA tensors
+        -> shares_out (C, M, 32) uint8, enqueued on `stream`."""
+        _need(coeffs.dim() == 3, "coeffs must be (T, M, 32)")
+        T, M = coeffs.shape[0], coeffs.shape[1]
+        C = xs.numel() if xs is not None else 0
+        _dev_bytes(coeffs, "coeffs", 32, T * M)
+        _dev_bytes(xs, "xs", 1, C, 4)
+        _dev_bytes(shares_out, "shares_out", 32, C * M)
+        rc = self.lib.flm_shamir_deal_dev(self.ctx, ctypes.c_void_p(coeffs.data_ptr()), T, M,
+                                          ctypes.c_void_p(xs.data_ptr()), C,
+                                          ctypes.c_void_p(shares_out.data_ptr()), self._stream_handle(stream))
+        self._check(rc, "flm_shamir_deal_dev")
+        return shares_out
+
+    def aes_gcm_xor_wire(self, keys, nonces, data) -> np.ndarray:
+        """AES.new(key, AES.MODE_GCM, nonce=nonce).encrypt(data) with the tag dropped, for n messages
+        (flm_aes_gcm_xor; SA_ClientAgent.py:227-244, and the decryption of :402-420 -- the same XOR).
+        keys (n, 16), nonces (n, 12 or 16), data (n, len) uint8 with 1 <= len <= 256 -> (n, len)."""
+        k = np.ascontiguousarray(keys, np.uint8)
+        nc = np.ascontiguousarray(nonces, np.uint8)
+        d = np.ascontiguousarray(data, np.uint8)
+        if k.ndim != 2 or k.shape[1] != 16 or nc.ndim != 2 or d.ndim != 2:
+            raise RuntimeError("keys must be (n, 16), nonces (n, nonce_len), data (n, len)")
+        n = k.shape[0]
+        if nc.shape[0] != n or d.shape[0] != n:
+            raise RuntimeError(f"{n} keys for {nc.shape[0]} nonces and {d.shape[0]} messages")
+        out = np.zeros_like(d)
+        rc = self.lib.flm_aes_gcm_xor(self.ctx, p_u8(k), p_u8(nc), nc.shape[1], p_u8(d), p_u8(out), d.shape[1], n)
+        self._check(rc, "flm_aes_gcm_xor")
+        return out
+
+    def aes_gcm_xor_dev(self, keys, nonces, data, out=None, stream=None):
+        """Device form: keys (n, 16), nonces (n, 12 or 16), data (n, len) uint8 CUDA tensors -> out
+        (n, len), which may be `data` itself (the default: in place); enqueued on `stream`."""
+        _need(keys.dim() == 2 and nonces.dim() == 2 and data.dim() == 2,
+              "keys must be (n, 16), nonces (n, nonce_len), data (n, len)")
+        out = data if out is None else out
+        n, ln = data.shape
+        _dev_bytes(keys, "keys", 16, n)
+        _dev_bytes(nonces, "nonces", nonces.shape[1], n)
+        _dev_bytes(data, "data", ln, n)
+        _dev_bytes(out, "out", ln, n)
+        _need(keys.shape[0] == n and nonces.shape[0] == n, f"{keys.shape[0]} keys and {nonces.shape[0]} nonces "
+              f"for {n} messages")
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        rc = self.lib.flm_aes_gcm_xor_dev(self.ctx, vp(keys), vp(nonces), nonces.shape[1], vp(data), vp(out), ln, n,
+                                          self._stream_handle(stream))
+        self._check(rc, "flm_aes_gcm_xor_dev")
+        return out
 
     def ec_combine_dev(self, c1, shares, lambdas, seeds_out, flags, points_out=None, negate: bool = True,
                        stream=None):

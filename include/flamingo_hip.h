@@ -259,6 +259,35 @@ int flm_shamir_combine(flm_ctx *ctx, const uint8_t *shares, const uint8_t *lambd
                        uint8_t *seeds_out);
 int flm_shamir_combine_dev(flm_ctx *ctx, const uint8_t *d_shares, const uint8_t *d_lambdas, int T, int M,
                            uint8_t *d_seeds_out, void *stream);
+/* Shamir dealing of the self-mask seeds, batched over M clients: replaces
+ * secret_int_to_points at SA_ClientAgent.py:218-220 (the inverse of flm_shamir_combine):
+ *   shares_out[c][i] = (sum_{j<T} coeffs[j][i] * xs[c]^j mod n).to_bytes(32, 'big')
+ * for c < C, i < M, n the P-256 group order.  coeffs: T*M*32 bytes, term-major and big
+ * endian (the layout of flm_shamir_combine's shares), term 0 the secret m_i, every value
+ * < 2^256 accepted and reduced mod n (m_i is 32 random bytes).  xs: C evaluation points,
+ * each non-zero (the protocol's 1..C).  shares_out: C*M*32 bytes, point-major, every value
+ * < n: row c is a shares[j] of flm_shamir_combine as it stands.
+ * FLM_EINVAL for T < 1, C < 1 or (host form) an x of 0; M = 0 succeeds and launches nothing.
+ * _dev: device pointers (coeffs and shares 16-byte aligned, xs non-zero -- not checked),
+ * enqueued on `stream`; nothing is staged or synchronised. */
+int flm_shamir_deal(flm_ctx *ctx, const uint8_t *coeffs, int T, int M, const uint32_t *xs, int C,
+                    uint8_t *shares_out);
+int flm_shamir_deal_dev(flm_ctx *ctx, const uint8_t *d_coeffs, int T, int M, const uint32_t *d_xs, int C,
+                        uint8_t *d_shares_out, void *stream);
+/* AES-128-GCM with the tag dropped, n messages per call: what
+ * AES.new(key, AES.MODE_GCM, nonce=nonce).encrypt(data) returns, replacing the per-share
+ * encryption of SA_ClientAgent.py:227-244 (the tag is discarded at :242) and the per-share
+ * decryption of :402-420 (no tag is checked, :423-425) -- so both directions are
+ *   out[i] = in[i] ^ E_k(inc32(J0)) || E_k(inc32^2(J0)) || ...      (first len bytes)
+ * with J0 = nonce || 0x00000001 for a 12-byte nonce and GHASH_H(nonce || 0^64 || [128]_64),
+ * H = E_k(0^128), for a 16-byte one (pycryptodome's default, which the protocol uses).
+ * keys: n*16 bytes; nonces: n*nonce_len, nonce_len 12 or 16; in, out: n*len, 1 <= len <= 256
+ * (the protocol: 32); all dense; in == out is allowed.  FLM_EINVAL for another nonce_len or
+ * len; n = 0 succeeds and launches nothing.  _dev: device pointers, enqueued on `stream`. */
+int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *in,
+                    uint8_t *out, size_t len, int n);
+int flm_aes_gcm_xor_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
+                        const uint8_t *d_in, uint8_t *d_out, size_t len, int n, void *stream);
 /* Batched scalar multiplication out[i] = scalars[i] * points[i]: the ECDH
  * (SA_ClientAgent.py:256-263), ElGamal (:434-447) and decryption-share
  * (:397-400) products, n independent elements per call. */

@@ -32,6 +32,8 @@ for _name, _res, _args in (
         ("flm_aggregate_unmask", _int, [_vp, ctypes.POINTER(_u32p), _int, _u8p, _i8p, _int, _sz, _u32p]),
         ("flm_client_mask", _int, [_vp, _u32p, _int, _i64p, _u8p, _i8p, _sz, _u32p]),
         ("flm_shamir_combine", _int, [_vp, _u8p, _u8p, _int, _int, _u8p]),
+        ("flm_shamir_deal", _int, [_vp, _u8p, _int, _int, _u32p, _int, _u8p]),
+        ("flm_aes_gcm_xor", _int, [_vp, _u8p, _u8p, _int, _u8p, _u8p, _sz, _int]),
         ("flm_ec_combine", _int, [_vp, _u8p, _u8p, _u8p, _int, _int, _int, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
         ("flm_group_init", _int, [ctypes.POINTER(_vp), _int, ctypes.POINTER(_int)]),
         ("flm_group_last_error", ctypes.c_char_p, [_vp]),
@@ -135,6 +137,37 @@ def shamir_combine(shares_by_member, coeffs):
     _check(_lib.flm_shamir_combine(_context(), sh.ctypes.data_as(_u8p), _be(coeffs).ctypes.data_as(_u8p), T, M,
                                    out.ctypes.data_as(_u8p)))
     return [out[32 * i:32 * i + 32].tobytes() for i in range(M)]
+
+
+def shamir_deal(coeffs_by_term, xs):
+    """[[sum_j coeffs_by_term[j][i] * x^j % n for each secret i] for x in xs]: the dealing of
+    SA_ClientAgent.py:218-220 (secret_int_to_points) for a batch of clients, term 0 the secrets
+    (any value below 2^256), xs the non-zero evaluation points (the reference's 1..num_points)."""
+    T, M, C = len(coeffs_by_term), len(coeffs_by_term[0]), len(xs)
+    co = np.concatenate([_be(c) for c in coeffs_by_term]) if M else np.zeros(32, np.uint8)
+    x = np.asarray([int(v) for v in xs], np.uint32)
+    out = np.empty(max(1, C * M * 32), np.uint8)
+    _check(_lib.flm_shamir_deal(_context(), co.ctypes.data_as(_u8p), T, M, x.ctypes.data_as(_u32p), C,
+                                out.ctypes.data_as(_u8p)))
+    return [[int.from_bytes(out[32 * (c * M + i):32 * (c * M + i) + 32].tobytes(), "big") for i in range(M)]
+            for c in range(C)]
+
+
+def aes_gcm_xor(keys, nonces, datas):
+    """[AES.new(key, AES.MODE_GCM, nonce=nonce).encrypt(data)] for a batch of equally long messages
+    (at most 256 bytes) and equally long nonces (12 or 16 bytes), tags dropped: the per-share
+    encryption of SA_ClientAgent.py:227-244 and, being the same XOR, the decryption of :402-420."""
+    n = len(datas)
+    if n == 0:
+        return []
+    k, nc, d = (np.frombuffer(b"".join(bytes(v) for v in part), np.uint8) for part in (keys, nonces, datas))
+    ln, nl = len(datas[0]), len(nonces[0])
+    if k.size != 16 * n or nc.size != nl * n or d.size != ln * n:
+        raise RuntimeError("keys must be 16 bytes each; nonces, and messages, of one length")
+    out = np.empty(ln * n, np.uint8)
+    _check(_lib.flm_aes_gcm_xor(_context(), k.ctypes.data_as(_u8p), nc.ctypes.data_as(_u8p), nl,
+                                d.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), ln, n))
+    return [out[ln * i:ln * i + ln].tobytes() for i in range(n)]
 
 
 def ec_combine(c1_points, shares_by_member, coeffs):
