@@ -59,6 +59,12 @@ def parse(argv):
     # the clients' m_i dealing and AES-GCM sealing per client on the host, not batched on the GPU
     # (protocol.configure(gpu_deal=False)): same messages, for A/B timing
     ap.add_argument("--host_deal", action="store_true")
+    # committee members verify the signatures forwarded in DEC before they release decryption shares
+    # (protocol.configure(check_signatures=True)); off by default
+    ap.add_argument("--check_signatures", action="store_true")
+    # ... in one GPU call per member (protocol.configure(gpu_verify=True)), not row by row on the host
+    # (OpenSSL), which is the default: same verdicts, no faster at a member's 61 rows
+    ap.add_argument("--gpu_verify", action="store_true")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -106,7 +112,9 @@ def _run(args):
     if args.committee_size > args.num_clients:
         raise ValueError("committee_size cannot exceed num_clients")
     param.configure(root=root, L=args.vector_len, committee=args.committee_size,
-                    gpu_deal=False if args.host_deal else None)
+                    gpu_deal=False if args.host_deal else None,
+                    check_signatures=True if args.check_signatures else None,
+                    gpu_verify=True if args.gpu_verify else None)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
     offline_its = offline_schedule(n, args.num_iterations, offline, args.dropout)
     print(f"Silent mode: {log.silent_mode}")

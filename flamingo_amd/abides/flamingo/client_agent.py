@@ -18,7 +18,9 @@ iteration (protocol.mi_shares; the host path stays behind
 protocol.configure(gpu_deal=False)).
 Committee members sign the offline set (ECDSA, :351-368) and answer DEC with
 sk_j * c0 for each dropout ciphertext plus their decrypted m_i shares
-(:370-431).
+(:370-431).  With protocol.configure(check_signatures=True) they first verify
+the server's signature and a quorum of the forwarded committee signatures
+(signaturesHold: the check the reference leaves as a comment, :387).
 """
 from __future__ import annotations
 
@@ -73,6 +75,7 @@ class SA_ClientAgent(Agent):
         self.key_length = key_length
         self.neighbors_list = set()
         self.cipher_stored = None
+        self.signed_payload = None   # what this member signed in the current iteration (signSendLabels)
         self.user_committee = param.committee(self.num_clients)
         self.committee_shared_sk = None
         self.committee_member_idx = None
@@ -133,8 +136,10 @@ class SA_ClientAgent(Agent):
                 t0 = pd.Timestamp("now")
                 if self.cipher_stored is not None and self.cipher_stored.body["iteration"] == self.current_iteration:
                     b = self.cipher_stored.body
-                    self.decryptSendShares(b["dec_target_pairwise"], b["dec_target_mi"], b["client_id_list"])
+                    if not param.check_signatures_on() or self.signaturesHold(b["labels"], body["labels"]):
+                        self.decryptSendShares(b["dec_target_pairwise"], b["dec_target_mi"], b["client_id_list"])
                 self.cipher_stored = None
+                self.signed_payload = None
                 self.recordTime(t0, "RECONSTRUCTION")
         elif body["msg"] == "REQ" and self.current_iteration != 0:
             self.current_iteration += 1
@@ -214,11 +219,30 @@ class SA_ClientAgent(Agent):
 
     def signSendLabels(self, currentTime, msg_to_sign):
         payload = repr(msg_to_sign).encode()          # the reference signs dill.dumps(msg) (:352-356)
+        self.signed_payload = payload
         sig = C.ecdsa_sign(self.secret_key, self.public_key, payload)
         self.sendMessage(self.serviceAgentID, Message({
             "msg": "SIGN", "iteration": self.current_iteration, "sender": self.id,
             "signed_labels": (payload, sig), "committee_member_idx": self.committee_member_idx}),
             tag="comm_sign_client")
+
+    def signaturesHold(self, server_labels, dec_labels) -> bool:
+        """The check the reference leaves as `# CHECK SIGNATURES` (:387), behind
+        protocol.configure(check_signatures=True): the server's signature over the offline set this
+        member was shown, and a quorum of committee signatures over the very payload it signed
+        itself -- so a server that shows different offline sets to different decryptors gets no
+        shares from them.  One batched verification per DEC (protocol.check_dec_signatures).  A
+        member that refuses says so and sends no shares; the server's threshold check then decides."""
+        server_ok, valid, needed = param.check_dec_signatures(self.num_clients, server_labels, dec_labels,
+                                                              self.signed_payload)
+        if server_ok and valid >= needed:
+            return True
+        self.logger.info(f"client {self.id}: signature check failed in iteration {self.current_iteration} "
+                         f"(server {'ok' if server_ok else 'BAD'}, {valid} of {needed} committee signatures)")
+        self.sendMessage(self.serviceAgentID, Message({
+            "msg": "SIG_CHECK_FAILED", "iteration": self.current_iteration, "sender": self.id,
+            "valid": valid, "needed": needed}), tag="sig_check_failed")
+        return False
 
     def decryptSendShares(self, dec_target_pairwise, dec_target_mi, client_id_list):
         """dec_target_pairwise: serialize_dim1_elgamal JSON; dec_target_mi: serialize_tuples_bytes JSON."""

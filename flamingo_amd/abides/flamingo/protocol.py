@@ -46,14 +46,31 @@ _pair_mat: dict = {}      # (root, iteration, N, nsize) -> {id: PairMaterial}
 _gpu_deal: bool = True    # configure(gpu_deal=...)
 _mi_draws: dict = {}      # (root, iteration, id) -> (m_i bytes, T-1 coefficients, C nonces)
 _mi_shares: dict = {}     # (root, iteration, id) -> [(ciphertext, nonce)] in committee order
+# The committee's check of the signatures the server forwards in DEC (the reference's
+# `# CHECK SIGNATURES`, SA_ClientAgent.py:387): off by default, so a run sends what it always sent.
+_check_signatures: bool = False        # configure(check_signatures=...)
+# A member's 61 rows take as long in one GPU call as in the host loop (one wave's 2.6 ms chain against
+# 61 x 43 us of OpenSSL), so the members verify on the host unless told otherwise.
+_gpu_verify: bool = False              # configure(gpu_verify=True): one MaskEngine.ecdsa_verify call per DEC
+_signature_quorum = 2 / 3               # configure(signature_quorum=...): the share of the committee whose
+                                        # signatures over the same labels must verify
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
-              gpu_deal: bool | None = None):
+              gpu_deal: bool | None = None, check_signatures: bool | None = None,
+              signature_quorum: float | None = None, gpu_verify: bool | None = None):
     """Reset the protocol parameters (between simulations / in tests)."""
-    global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal
+    global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
     if gpu_deal is not None:
         _gpu_deal = bool(gpu_deal)
+    if check_signatures is not None:
+        _check_signatures = bool(check_signatures)
+    if gpu_verify is not None:
+        _gpu_verify = bool(gpu_verify)
+    if signature_quorum is not None:
+        if not 0 < float(signature_quorum) <= 1:
+            raise ValueError("signature_quorum must be in (0, 1]")
+        _signature_quorum = float(signature_quorum)
     _mi_draws.clear()
     _mi_shares.clear()
     if root is not None:
@@ -364,6 +381,60 @@ def deal_on_gpu() -> bool:
     default).  An engine object that brings no dealing calls (a CPU test double, as for
     vector_store) leaves the agents on the host path, which sends the same bytes."""
     return _gpu_deal and hasattr(engine(), "shamir_deal_wire") and hasattr(engine(), "aes_gcm_xor_wire")
+
+
+# ------------------------------------------------ the committee's signature check
+def check_signatures_on() -> bool:
+    """True when a committee member verifies the signatures of a DEC before it releases its
+    decryption shares (configure(check_signatures=True); off by default)."""
+    return _check_signatures
+
+
+def signatures_needed(committee_members: int) -> int:
+    """ceil(signature_quorum x committee size): how many members' signatures over the labels a
+    member signed itself must verify before it goes on."""
+    from fractions import Fraction
+    import math
+    return max(1, math.ceil(Fraction(_signature_quorum).limit_denominator(1 << 20) * committee_members))
+
+
+def verify_signatures(pubs, msgs, sigs) -> list:
+    """One verdict per (public key, message, signature) row: crypto.ecdsa_verify row by row (the
+    default: at a member's 61 rows the GPU call is no faster), or after configure(gpu_verify=True)
+    the engine's batched GPU call (MaskEngine.ecdsa_verify, one launch for the whole DEC) where the
+    engine has it (a CPU test double does not)."""
+    from ... import crypto as C
+    batch = getattr(engine(), "ecdsa_verify", None) if _gpu_verify else None
+    if batch is not None:
+        return [bool(v) for v in batch(pubs, msgs, sigs)]
+    return [pub is not None and len(sig) == 64 and C.ecdsa_verify(pub, msg, sig)
+            for pub, msg, sig in zip(pubs, msgs, sigs)]
+
+
+def check_dec_signatures(num_clients: int, server_labels, dec_labels, own_payload) -> tuple:
+    """What a committee member checks when DEC arrives (SA_ClientAgent.py:387, the server's side at
+    SA_ServiceAgent.py:382-386).  server_labels: the (labels, signature) pair of the SIGN message it
+    stored; dec_labels: sender -> (payload, signature) as forwarded; own_payload: what this member
+    signed.  All rows -- the server's signature under pki.server_pk, every entry under its sender's
+    key -- go through ONE verify_signatures call.  An entry counts when its signature verifies, its
+    sender sits on the committee and its payload is the member's own.
+    Returns (server_ok, count, needed)."""
+    keys = pki(num_clients)
+    members = committee(num_clients)
+    entries = []
+    for sender, signed in (dec_labels or {}).items():
+        if (isinstance(sender, int) and 0 <= sender < num_clients and isinstance(signed, (tuple, list))
+                and len(signed) == 2 and all(isinstance(b, (bytes, bytearray)) for b in signed)):
+            entries.append((sender, bytes(signed[0]), bytes(signed[1])))
+    try:
+        labels, server_sig = bytes(server_labels[0]), bytes(server_labels[1])
+    except (TypeError, IndexError, ValueError):
+        labels, server_sig = b"", b""
+    verdicts = verify_signatures([keys.server_pk] + [keys.client_pk[s] for s, _, _ in entries],
+                                 [labels] + [p for _, p, _ in entries], [server_sig] + [g for _, _, g in entries])
+    count = sum(1 for ok, (sender, payload, _) in zip(verdicts[1:], entries)
+                if ok and sender in members and payload == own_payload)
+    return bool(verdicts[0]), count, signatures_needed(len(members))
 
 
 def _mi_shape(agent) -> tuple:

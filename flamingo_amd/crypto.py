@@ -319,14 +319,25 @@ def ecdsa_sign(d: int, pub, msg: bytes) -> bytes:
     return out
 
 
-def ecdsa_verify(pub, msg: bytes, signature: bytes) -> bool:
+def ecdsa_verify_digest(pub, digest: bytes, signature: bytes) -> bool:
+    """ECDSA_do_verify of r || s over a digest as it is (no hashing here); a key OpenSSL refuses
+    (off the curve, infinity) verifies nothing."""
     c = _lib()
-    k = _eckey(0, pub)
+    if pub is None or len(signature) != 64:
+        return False
+    try:
+        k = _eckey(0, pub)
+    except (ValueError, OverflowError):
+        return False
     sig = c.ECDSA_SIG_new()
     r = c.BN_bin2bn(signature[:32], 32, None)
     s = c.BN_bin2bn(signature[32:], 32, None)
     c.ECDSA_SIG_set0(sig, r, s)
-    ok = c.ECDSA_do_verify(hashlib.sha256(msg).digest(), 32, sig, k)
+    ok = c.ECDSA_do_verify(digest, len(digest), sig, k)
     c.ECDSA_SIG_free(sig)
     c.EC_KEY_free(k)
     return ok == 1
+
+
+def ecdsa_verify(pub, msg: bytes, signature: bytes) -> bool:
+    return ecdsa_verify_digest(pub, hashlib.sha256(msg).digest(), signature)

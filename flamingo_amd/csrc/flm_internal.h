@@ -130,6 +130,9 @@ hipError_t launch_shamir_deal(const uint8_t *d_coeffs, int T, int M, const uint3
 // d_out = d_in ^ AES-128-GCM keystream of (key i, nonce i), n messages of len bytes (aes_gcm_xor_kernel)
 hipError_t launch_aes_gcm_xor(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_in,
                               uint8_t *d_out, uint32_t len, int n, hipStream_t stream);
+// d_ok[i] = ECDSA verdict of (pubkey i, digest i, signature i); d_flags n words or NULL (ecdsa_verify_kernel)
+hipError_t launch_ecdsa_verify(const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs, int n,
+                               uint8_t *d_ok, uint32_t *d_flags, hipStream_t stream);
 hipError_t launch_ec_finish(const uint8_t *d_base, const uint32_t *d_jac, int T, int D, int negate,
                             uint8_t *d_points_out, uint8_t *d_digests_out, uint32_t *d_flags, hipStream_t stream);
 // hash_str_to_curve of n messages (d_msgs: n x 64 bytes + d_lens), or of the decimal strings of

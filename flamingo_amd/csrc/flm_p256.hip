@@ -340,8 +340,10 @@ __device__ __forceinline__ void bg_lin(uint32_t (&r)[9], const uint32_t (&a)[8],
     r[8] = (uint32_t)((int32_t)x[8] >> 30);
 }
 
-// (u * f + v * g) / 2^30 mod p, into [0, p): the sum plus q p with q its low 30 bits is divisible
-// by 2^30; |u f + v g| <= p 2^30 (|f| + |g| <= 2^30), so the quotient lies in [-p, 2p]
+// (u * f + v * g) / 2^30 mod m, into [0, m), for the modulus m = MOD (p, or the group order n): the
+// sum plus q m with q its low 30 bits times NINV30 = -m^-1 mod 2^30 (1 for p) is divisible by 2^30;
+// |u f + v g| <= m 2^30 (|f| + |g| <= 2^30), so the quotient lies in [-m, 2m]
+template <const uint32_t (&MOD)[8], uint32_t NINV30>
 __device__ __forceinline__ void bg_lin_modp(uint32_t (&r)[8], const uint32_t (&u)[8], int32_t f,
                                             const uint32_t (&v)[8], int32_t g) {
     uint32_t x[9], y[9], c = 0;
@@ -349,11 +351,11 @@ __device__ __forceinline__ void bg_lin_modp(uint32_t (&r)[8], const uint32_t (&u
     bg_mul_s32(y, v, g);
 #pragma unroll
     for (int i = 0; i < 9; ++i) x[i] = __builtin_addc(x[i], y[i], c, &c);
-    const uint32_t q = x[0] & 0x3fffffffu;
+    const uint32_t q = (x[0] * NINV30) & 0x3fffffffu;
     uint64_t m = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        m = (uint64_t)kP[i] * q + (m >> 32);
+        m = (uint64_t)MOD[i] * q + (m >> 32);
         y[i] = (uint32_t)m;
     }
     y[8] = (uint32_t)(m >> 32);
@@ -368,24 +370,27 @@ __device__ __forceinline__ void bg_lin_modp(uint32_t (&r)[8], const uint32_t (&u
     const uint32_t neg = (int32_t)w[8] < 0 ? 0xffffffffu : 0u;
     c = 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = __builtin_addc(w[i], kP[i] & neg, c, &c);
+    for (int i = 0; i < 8; ++i) w[i] = __builtin_addc(w[i], MOD[i] & neg, c, &c);
     w[8] = __builtin_addc(w[8], 0u, c, &c);  // the sign word wraps to 0 when p was added
     // [p, 2p] -> - p
     uint32_t d[8], br = 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = __builtin_subc(w[i], kP[i], br, &br);
+    for (int i = 0; i < 8; ++i) d[i] = __builtin_subc(w[i], MOD[i], br, &br);
     const bool take = w[8] != 0 || !br;
 #pragma unroll
     for (int i = 0; i < 8; ++i) r[i] = take ? d[i] : w[i];
 }
 
-// x^-1 mod p for 0 < x < p (plain integers: the caller's Montgomery form is just an integer here)
-__device__ Fe fe_inv_bingcd(const Fe &x) {
+// x^-1 mod m for 0 < x < m (plain integers: the caller's Montgomery form is just an integer here).
+// MOD is the odd 256-bit modulus and NINV30 = -m^-1 mod 2^30 (1 for p); the 18 x 30 steps cover any
+// modulus below 2^256 (tools/bingcd_model.py runs the schedule for both p and the group order n).
+template <const uint32_t (&MOD)[8], uint32_t NINV30>
+__device__ Fe inv_bingcd(const Fe &x) {
     uint32_t a[8], b[8], u[8], v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         a[i] = x.v[i];
-        b[i] = kP[i];
+        b[i] = MOD[i];
         u[i] = i == 0 ? 1u : 0u;
         v[i] = 0u;
     }
@@ -448,8 +453,8 @@ __device__ Fe fe_inv_bingcd(const Fe &x) {
         if (nga) { f0 = -f0; g0 = -g0; }
         if (ngb) { f1 = -f1; g1 = -g1; }
         uint32_t nu[8], nv[8];
-        bg_lin_modp(nu, u, f0, v, g0);
-        bg_lin_modp(nv, u, f1, v, g1);
+        bg_lin_modp<MOD, NINV30>(nu, u, f0, v, g0);
+        bg_lin_modp<MOD, NINV30>(nv, u, f1, v, g1);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             u[i] = nu[i];
@@ -458,9 +463,11 @@ __device__ Fe fe_inv_bingcd(const Fe &x) {
     }
     Fe r;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = v[i];  // b = 1 = v x (mod p)
+    for (int i = 0; i < 8; ++i) r.v[i] = v[i];  // b = 1 = v x (mod m)
     return r;
 }
+
+__device__ Fe fe_inv_bingcd(const Fe &x) { return inv_bingcd<kP, 1u>(x); }
 
 // -------------------------------------------------------------- points (a = -3)
 __device__ __forceinline__ Jac jac_inf() {
@@ -1458,6 +1465,208 @@ __global__ __launch_bounds__(kEcThreads) void shamir_deal_kernel(const uint8_t *
     store_be(out + g * 32, acc);
 }
 
+// ------------------------------------------------------------- ECDSA verification
+// The signatures a committee member must check before it releases decryption shares: the
+// server's over the offline set and the other members' over the same labels, forwarded in DEC
+// (SA_ServiceAgent.py:382-386; the reference leaves the check as the comment
+// `# CHECK SIGNATURES`, SA_ClientAgent.py:387).  One lane per signature, the verdict of FIPS 186-4
+// section 6.4.2 and of OpenSSL's ECDSA_do_verify:
+//     r, s in [1, n-1];  Q a point of the curve, not infinity;
+//     w = s^-1 mod n,  u1 = (e mod n) w,  u2 = r w,  R = u1 G + u2 Q != infinity,  x(R) mod n == r.
+//
+// u1 and u2 differ from row to row, so a wNAF's sparse digits would send the lanes of a wave down
+// different branches and every step would run both additions anyway.  The scalars are recoded
+// regularly instead: an odd k < 2^256 is 2^256 + sum_{i<64} d_i 16^i with
+//     d_i = 2 ((k >> (4 i + 1)) & 15) - 15,   odd, in [-15, 15], never zero
+// (every bit b_j of k written as the digit 2 b_{j+1} - 1 of weight 2^j, a top digit of +1), and an
+// even k is taken as n - k with the point negated.  Every lane then runs the same schedule: one
+// chain of 256 doublings shared by both scalars (Straus) and 65 x (one mixed addition from the
+// constant affine table of G's odd multiples + one addition from the lane's Jacobian table of
+// Q's), about 3,800 field multiplications with no divergence.  jac_add's exceptional cases stay:
+// u1 G = +-u2 Q and keys that are small multiples of G reach them.
+constexpr uint32_t kNInv30 = kN0 & 0x3fffffffu;  // -n^-1 mod 2^30
+
+// (2t+1) G, t = 0..7, affine x then y, Montgomery form (oracle/ec_oracle.py mul(2t+1) times 2^256 mod
+// p; tests/test_ecdsa_cpu.py recomputes the table)
+__device__ constexpr uint32_t kGOdd[8][16] = {
+    {0x18a9143cu, 0x79e730d4u, 0x5fedb601u, 0x75ba95fcu, 0x77622510u, 0x79fb732bu, 0xa53755c6u, 0x18905f76u,
+     0xce95560au, 0xddf25357u, 0xba19e45cu, 0x8b4ab8e4u, 0xdd21f325u, 0xd2e88688u, 0x25885d85u, 0x8571ff18u},  // 1G
+    {0x4eebc127u, 0xffac3f90u, 0x087d81fbu, 0xb027f84au, 0x87cbbc98u, 0x66ad77ddu, 0xb6ff747eu, 0x26936a3fu,
+     0xc983a7ebu, 0xb04c5c1fu, 0x0861fe1au, 0x583e47adu, 0x1a2ee98eu, 0x78820831u, 0xe587cc07u, 0xd5f06a29u},  // 3G
+    {0xc45c61f5u, 0xbe1b8aaeu, 0x94b9537du, 0x90ec649au, 0xd076c20cu, 0x941cb5aau, 0x890523c8u, 0xc9079605u,
+     0xe7ba4f10u, 0xeb309b4au, 0xe5eb882bu, 0x73c568efu, 0x7e7a1f68u, 0x3540a987u, 0x2dd1e916u, 0x73a076bbu},  // 5G
+    {0xa0173b4fu, 0x0746354eu, 0xd23c00f7u, 0x2bd20213u, 0x0c23bb08u, 0xf43eaab5u, 0xc3123e03u, 0x13ba5119u,
+     0x3f5b9d4du, 0x2847d030u, 0x5da67bddu, 0x6742f2f2u, 0x77c94195u, 0xef933bdcu, 0x6e240867u, 0xeaedd915u},  // 7G
+    {0x264e20e8u, 0x75c96e8fu, 0x59a7a841u, 0xabe6bfedu, 0x44c8eb00u, 0x2cc09c04u, 0xf0c4e16bu, 0xe05b3080u,
+     0xa45f3314u, 0x1eb7777au, 0xce5d45e3u, 0x56af7bedu, 0x88b12f1au, 0x2b6e019au, 0xfd835f9bu, 0x086659cdu},  // 9G
+    {0x6245e404u, 0xea7d260au, 0x6e7fdfe0u, 0x9de40795u, 0x8dac1ab5u, 0x1ff3a415u, 0x649c9073u, 0x3e7090f1u,
+     0x2b944e88u, 0x1a768561u, 0xe57f61c8u, 0x250f939eu, 0x1ead643du, 0x0c0daa89u, 0xe125b88eu, 0x68930023u},  // 11G
+    {0x4b2ed709u, 0xccc42563u, 0x856fd30du, 0x0e356769u, 0x559e9811u, 0xbcbcd43fu, 0x5395b759u, 0x738477acu,
+     0xc00ee17fu, 0x35752b90u, 0x742ed2e3u, 0x68748390u, 0xbd1f5bc1u, 0x7cd06422u, 0xc9e7b797u, 0xfbc08769u},  // 13G
+    {0xbc60055bu, 0x72bcd8b7u, 0x56e27e4bu, 0x03cc23eeu, 0xe4819370u, 0xee337424u, 0x0ad3da09u, 0xe2aa0e43u,
+     0x6383c45du, 0x40b8524fu, 0x42a41b25u, 0xd7663554u, 0x778a4797u, 0x64efa6deu, 0x7079adf4u, 0x2042170au},  // 15G
+};
+
+// a < n for a canonical input
+__device__ __forceinline__ bool sc_lt_n(const Fe &a) {
+    uint32_t b = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) (void)__builtin_subc(a.v[i], kN[i], b, &b);
+    return b != 0;
+}
+
+// madd-2007-bl: P + (x2, y2) for an affine second point (Z2 = 1), exceptional cases as jac_add
+__device__ __forceinline__ Jac jac_add_affine(const Jac &P, const Fe &x2, const Fe &y2) {
+    Jac Q;
+    Q.X = x2;
+    Q.Y = y2;
+    Q.Z = fe_const(kOne);
+    if (fe_is_zero(P.Z)) return Q;
+    Fe z1z1 = fe_sqr(P.Z);
+    Fe u2 = fe_mul(x2, z1z1);
+    Fe s2 = fe_mul(fe_mul(y2, P.Z), z1z1);
+    Fe h = fe_sub(u2, P.X);
+    Fe r = fe_sub(s2, P.Y);
+    if (fe_is_zero(h)) {
+        if (fe_is_zero(r)) return jac_dbl(Q);
+        return jac_inf();
+    }
+    r = fe_add(r, r);
+    Fe hh = fe_sqr(h);
+    Fe i = fe_add(hh, hh);
+    i = fe_add(i, i);
+    Fe j = fe_mul(h, i);
+    Fe v = fe_mul(P.X, i);
+    Jac R;
+    R.X = fe_sub(fe_sub(fe_sqr(r), j), fe_add(v, v));
+    Fe y1j = fe_mul(P.Y, j);
+    R.Y = fe_sub(fe_mul(r, fe_sub(v, R.X)), fe_add(y1j, y1j));
+    R.Z = fe_sub(fe_sub(fe_sqr(fe_add(P.Z, h)), z1z1), hh);
+    return R;
+}
+
+// A scalar k < n under the regular recoding above: odd |k| stored as k >> 1 with the digits taken
+// from the top nibble, neg = the point's sign.
+struct Regular {
+    uint32_t k[8];
+    bool neg;
+};
+
+__device__ __forceinline__ Regular regular_recode(const Fe &k) {
+    Regular r;
+    r.neg = (k.v[0] & 1u) == 0;  // even (0 included): n - k is odd, and (n - k)(-P) = k P
+    uint32_t d[8], b = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) d[i] = __builtin_subc(kN[i], k.v[i], b, &b);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) d[i] = r.neg ? d[i] : k.v[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.k[i] = (d[i] >> 1) | (i < 7 ? d[i + 1] << 31 : 0u);
+    return r;
+}
+
+// the next digit from the top, as (table index t, negative): digit = +-(2t + 1), sign already
+// folded with the scalar's
+__device__ __forceinline__ void regular_next(Regular &r, int &t, bool &negative) {
+    const int d = 2 * (int)(r.k[7] >> 28) - 15;
+#pragma unroll
+    for (int i = 7; i > 0; --i) r.k[i] = (r.k[i] << 4) | (r.k[i - 1] >> 28);
+    r.k[0] <<= 4;
+    t = (d < 0 ? -d : d) >> 1;
+    negative = (d < 0) != r.neg;
+}
+
+// pubkeys n x 64 wire bytes, digests n x 32, sigs n x 64 (r || s), all big endian.
+// ok[i] = 1 accept / 0 reject; flags[i] (may be NULL): bit 0 r or s outside [1, n-1], bit 1 Q not a
+// valid point, bit 2 u1 G + u2 Q at infinity.
+__global__ __launch_bounds__(kEcThreads) void ecdsa_verify_kernel(const uint8_t *__restrict__ pubkeys,
+                                                                  const uint8_t *__restrict__ digests,
+                                                                  const uint8_t *__restrict__ sigs, int n,
+                                                                  uint8_t *__restrict__ ok_out,
+                                                                  uint32_t *__restrict__ flags) {
+    __builtin_amdgcn_s_setprio(3);  // one wave's issue chain sets the time, as the other EC kernels
+    const size_t g = (size_t)blockIdx.x * kEcThreads + threadIdx.x;
+    if (g >= (size_t)n) return;
+    const Fe r = load_be(sigs + g * 64), s = load_be(sigs + g * 64 + 32);
+    uint32_t fl = 0;
+    if (fe_is_zero(r) || fe_is_zero(s) || !sc_lt_n(r) || !sc_lt_n(s)) fl |= 1u;
+    Jac Q;
+    bool q_ok = load_point(pubkeys + g * 64, Q);  // (0, 0), the wire form of infinity, is off the curve
+    {
+        const uint4 *qw = reinterpret_cast<const uint4 *>(pubkeys + g * 64);
+        uint32_t any = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) any |= qw[k].x | qw[k].y | qw[k].z | qw[k].w;
+        if (any == 0) q_ok = false;  // infinity, rejected explicitly
+    }
+    if (!q_ok) fl |= 2u;
+    bool accept = false;
+    if (fl == 0) {
+        const Fe zero = {};
+        const Fe e = sc_add(load_be(digests + g * 32), zero);  // e < 2^256 < 2n: one subtraction
+        const Fe w = inv_bingcd<kN, kNInv30>(s);
+        const Fe wm = sc_mul(w, fe_const(kR2N));  // w R mod n, so sc_mul(x, wm) = x w
+        Regular k1 = regular_recode(sc_mul(e, wm));
+        Regular k2 = regular_recode(sc_mul(r, wm));
+
+        Jac tab[8];  // tab[t] = (2t+1) Q
+        tab[0] = Q;
+        const Jac Q2 = jac_dbl(Q);
+#pragma unroll 1
+        for (int t = 1; t < 8; ++t) tab[t] = jac_add(tab[t - 1], Q2);
+
+        // top digits (+1 each, weight 2^256): acc = +-G +- Q
+        Jac acc = Q;
+        if (k2.neg) acc.Y = fe_neg(acc.Y);
+        {
+            Fe gx, gy;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                gx.v[k] = kGOdd[0][k];
+                gy.v[k] = kGOdd[0][8 + k];
+            }
+            if (k1.neg) gy = fe_neg(gy);
+            acc = jac_add_affine(acc, gx, gy);
+        }
+#pragma unroll 1
+        for (int wnd = 0; wnd < 64; ++wnd) {
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) acc = jac_dbl(acc);  // doubling infinity keeps Z = 0
+            int t;
+            bool negative;
+            regular_next(k1, t, negative);
+            Fe gx, gy;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                gx.v[k] = kGOdd[t][k];
+                gy.v[k] = kGOdd[t][8 + k];
+            }
+            if (negative) gy = fe_neg(gy);
+            acc = jac_add_affine(acc, gx, gy);
+            regular_next(k2, t, negative);
+            Jac A = tab[t];
+            if (negative) A.Y = fe_neg(A.Y);
+            acc = jac_add(acc, A);
+        }
+        if (fe_is_zero(acc.Z)) {
+            fl |= 4u;
+        } else {
+            // x(R) = X / Z^2 mod p, and x(R) mod n == r iff x(R) is r, or r + n where that is below p
+            const Fe z2 = fe_sqr(acc.Z);
+            accept = fe_eq(fe_mul(to_mont(r), z2), acc.X);
+            uint32_t rn[8], c = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) rn[k] = __builtin_addc(r.v[k], kN[k], c, &c);
+            Fe r2;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) r2.v[k] = rn[k];
+            if (!accept && c == 0 && fe_lt_p(r2)) accept = fe_eq(fe_mul(to_mont(r2), z2), acc.X);
+        }
+    }
+    ok_out[g] = accept ? 1 : 0;
+    if (flags) flags[g] = fl;
+}
+
 // ------------------------------------------------------------- AES-128-GCM keystream
 // The m_i shares travel AES-128-GCM encrypted with the tag dropped (SA_ClientAgent.py:227-244,
 // opened at :402-425 without a tag check), so both directions are data XOR keystream:
@@ -1946,6 +2155,14 @@ hipError_t launch_aes_gcm_xor(const uint8_t *d_keys, const uint8_t *d_nonces, in
     if (n <= 0 || len == 0) return hipSuccess;
     hipLaunchKernelGGL(aes_gcm_xor_kernel, dim3((unsigned)(((size_t)n + kAesThreads - 1) / kAesThreads)),
                        dim3(kAesThreads), 0, stream, d_keys, d_nonces, nonce_len, d_in, d_out, len, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_ecdsa_verify(const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs, int n,
+                               uint8_t *d_ok, uint32_t *d_flags, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ecdsa_verify_kernel, dim3((unsigned)(((size_t)n + kEcThreads - 1) / kEcThreads)),
+                       dim3(kEcThreads), 0, stream, d_pubkeys, d_digests, d_sigs, n, d_ok, d_flags);
     return hipGetLastError();
 }
 

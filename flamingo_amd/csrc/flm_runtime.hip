@@ -24,6 +24,7 @@
 
 #include "../../include/flamingo_hip.h"
 #include "flm_deal_args.h"
+#include "flm_ecdsa_args.h"
 #include "flm_internal.h"
 
 using flm::Item;
@@ -2092,6 +2093,42 @@ int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, in
     if (int rc = hc.begin()) return rc;
     FLM_HIP(ctx, flm::launch_aes_gcm_xor(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len,
                                          hi->as<const uint8_t>(), ho->as<uint8_t>(), (uint32_t)len, n, s));
+    return hc.finish();
+}
+
+int flm_ecdsa_verify_dev(flm_ctx *ctx, const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs,
+                         int n, uint8_t *d_ok_out, uint32_t *d_flags, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::ecdsa_verify_dims_error(n)) return fail(ctx, FLM_EINVAL, "ecdsa verify (n=%d): %s", n, why);
+    if (n == 0) return 0;
+    if (!d_pubkeys || !d_digests || !d_sigs || !d_ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (!flm::rt::ecdsa_verify_aligned((uintptr_t)d_pubkeys, (uintptr_t)d_digests, (uintptr_t)d_sigs))
+        return fail(ctx, FLM_EINVAL, "pubkeys, digests and sigs must be 16-byte aligned");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_ecdsa_verify(d_pubkeys, d_digests, d_sigs, n, d_ok_out, d_flags,
+                                          static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_ecdsa_verify(flm_ctx *ctx, const uint8_t *pubkeys, const uint8_t *digests, const uint8_t *sigs, int n,
+                     uint8_t *ok_out, uint32_t *flags_out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::ecdsa_verify_dims_error(n)) return fail(ctx, FLM_EINVAL, "ecdsa verify (n=%d): %s", n, why);
+    if (n == 0) return 0;
+    if (!pubkeys || !digests || !sigs || !ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    hipStream_t s = ctx->stream;
+    const flm::rt::EcdsaVerifyBytes nb = flm::rt::ecdsa_verify_bytes(n);
+    HostCopies hc(ctx, s);
+    hc.in(pubkeys, nb.pubkeys, ctx->ec_in);
+    hc.in(digests, nb.digests, ctx->ec_base);
+    hc.in(sigs, nb.sigs, ctx->ec_scal);
+    hc.out(ok_out, nb.ok, ctx->ec_out);
+    if (flags_out) hc.out(flags_out, nb.flags, ctx->ec_flags);
+    if (int rc = hc.begin()) return rc;
+    FLM_HIP(ctx, flm::launch_ecdsa_verify(ctx->ec_in.as<uint8_t>(), ctx->ec_base.as<uint8_t>(),
+                                          ctx->ec_scal.as<uint8_t>(), n, ctx->ec_out.as<uint8_t>(),
+                                          flags_out ? ctx->ec_flags.as<uint32_t>() : nullptr, s));
     return hc.finish();
 }
 

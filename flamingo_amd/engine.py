@@ -16,6 +16,8 @@ numpy/pycryptodomex loops:
 * ``shamir_deal`` / ``aes_gcm_xor_wire`` -- the clients' dealing and AES-GCM sealing of their
   m_i shares (SA_ClientAgent.py:218-220, 227-244) and the committee's opening of them
   (:402-420), batched over clients.
+* ``ecdsa_verify`` / ``ecdsa_verify_wire`` -- ECDSA P-256 verification of a batch of signatures: the
+  committee's check of the server's and the members' signatures (SA_ClientAgent.py:387).
 * ``*_dev`` -- the same on device-resident torch tensors (bench, multi-GPU).
 
 Errors surface as RuntimeError with the library's message, like the
@@ -611,6 +613,63 @@ class MaskEngine:
                                           self._stream_handle(stream))
         self._check(rc, "flm_aes_gcm_xor_dev")
         return out
+
+    def ecdsa_verify_wire(self, pk_w, digests_w, sigs_w):
+        """flm_ecdsa_verify on wire arrays: public keys (n, 64) x||y, digests (n, 32), signatures (n, 64)
+        r||s, uint8 big endian -> (ok (n,) bool, flags (n,) uint32).  The verdict of FIPS 186-4 /
+        OpenSSL's ECDSA_do_verify; flags bit 0: r or s outside [1, n-1], bit 1: key not a valid point
+        (64 zero bytes included), bit 2: u1 G + u2 Q at infinity.  An invalid row is a result, not an
+        error (the committee's check the reference leaves out, SA_ClientAgent.py:387)."""
+        pk = np.ascontiguousarray(pk_w, np.uint8)
+        dg = np.ascontiguousarray(digests_w, np.uint8)
+        sg = np.ascontiguousarray(sigs_w, np.uint8)
+        if pk.ndim != 2 or pk.shape[1] != 64 or dg.ndim != 2 or dg.shape[1] != 32 or sg.ndim != 2 or sg.shape[1] != 64:
+            raise RuntimeError("public keys must be (n, 64), digests (n, 32), signatures (n, 64)")
+        n = pk.shape[0]
+        if dg.shape[0] != n or sg.shape[0] != n:
+            raise RuntimeError(f"{n} keys for {dg.shape[0]} digests and {sg.shape[0]} signatures")
+        ok = np.zeros(n, np.uint8)
+        fl = np.zeros(n, np.uint32)
+        rc = self.lib.flm_ecdsa_verify(self.ctx, p_u8(pk), p_u8(dg), p_u8(sg), n, p_u8(ok), p_u32(fl))
+        self._check(rc, "flm_ecdsa_verify")
+        return ok.astype(bool), fl
+
+    def ecdsa_verify(self, pubs, msgs, sigs) -> list:
+        """ECDSA-SHA256 verification of n (public key, message, 64-byte r||s signature) rows in one
+        launch: what crypto.ecdsa_verify answers row by row.  pubs: affine (x, y) integer pairs; None
+        (infinity), coordinates outside [0, 2^256) and signatures of another length are invalid."""
+        import hashlib
+        n = len(pubs)
+        if len(msgs) != n or len(sigs) != n:
+            raise RuntimeError(f"{n} keys for {len(msgs)} messages and {len(sigs)} signatures")
+        pk = np.zeros((n, 64), np.uint8)
+        dg = np.zeros((n, 32), np.uint8)
+        sg = np.zeros((n, 64), np.uint8)
+        for i, (pub, msg, sig) in enumerate(zip(pubs, msgs, sigs)):
+            if pub is None or len(sig) != 64 or not all(0 <= int(c) < (1 << 256) for c in pub):
+                continue    # the row stays zero: key 0^64 and r = s = 0 are both refused
+            pk[i] = np.frombuffer(int(pub[0]).to_bytes(32, "big") + int(pub[1]).to_bytes(32, "big"), np.uint8)
+            dg[i] = np.frombuffer(hashlib.sha256(bytes(msg)).digest(), np.uint8)
+            sg[i] = np.frombuffer(bytes(sig), np.uint8)
+        ok, _ = self.ecdsa_verify_wire(pk, dg, sg)
+        return [bool(v) for v in ok]
+
+    def ecdsa_verify_dev(self, pubkeys, digests, sigs, ok_out, flags=None, stream=None):
+        """Device form: pubkeys (n, 64), digests (n, 32), sigs (n, 64) uint8 CUDA tensors -> ok_out (n,)
+        uint8 and, unless None, flags (n,) int32, enqueued on `stream` (nothing staged or awaited)."""
+        _need(pubkeys.dim() == 2, "pubkeys must be (n, 64)")
+        n = pubkeys.shape[0]
+        _dev_bytes(pubkeys, "pubkeys", 64, n)
+        _dev_bytes(digests, "digests", 32, n)
+        _dev_bytes(sigs, "sigs", 64, n)
+        _dev_bytes(ok_out, "ok_out", 1, n)
+        if flags is not None:
+            _dev_bytes(flags, "flags", 1, n, 4)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        rc = self.lib.flm_ecdsa_verify_dev(self.ctx, vp(pubkeys), vp(digests), vp(sigs), n, vp(ok_out), vp(flags),
+                                           self._stream_handle(stream))
+        self._check(rc, "flm_ecdsa_verify_dev")
+        return ok_out
 
     def ec_combine_dev(self, c1, shares, lambdas, seeds_out, flags, points_out=None, negate: bool = True,
                        stream=None):

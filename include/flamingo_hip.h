@@ -288,6 +288,26 @@ int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, in
                     uint8_t *out, size_t len, int n);
 int flm_aes_gcm_xor_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
                         const uint8_t *d_in, uint8_t *d_out, size_t len, int n, void *stream);
+/* Batched ECDSA verification on P-256, the check the reference leaves as the comment
+ * `# CHECK SIGNATURES` at SA_ClientAgent.py:387: before a committee member releases its
+ * decryption shares it must verify the server's signature over the offline set and the
+ * members' signatures the server forwards in DEC (SA_ServiceAgent.py:382-386), or a server
+ * could show different offline sets to different decryptors.  Row i: pubkeys[i] 64 wire bytes
+ * x || y, digests[i] the 32-byte message digest e (any value, 0 and values >= n included; the
+ * protocol's is SHA-256), sigs[i] = r || s, 2 x 32 bytes; all big endian.  The verdict is that of
+ * FIPS 186-4 and OpenSSL's ECDSA_do_verify: ok_out[i] = 1 iff r, s are in [1, n-1], Q is a point
+ * of the curve (not infinity), R = (e/s) G + (r/s) Q is not infinity and x(R) mod n == r; else 0.
+ * flags_out (n words, may be NULL): bit 0 r or s out of range, bit 1 Q invalid (a coordinate
+ * >= p, off the curve, or 64 zero bytes), bit 2 R at infinity.  An invalid signature is a
+ * result, not an error: the call returns 0.  n = 0 succeeds and launches nothing; FLM_EINVAL
+ * for n < 0 or n above 2^26.
+ * _dev: device pointers (pubkeys, digests, sigs 16-byte aligned; d_flags may be NULL), enqueued
+ * on `stream`; nothing is staged or synchronised, and the call returns without waiting for
+ * earlier work on the stream. */
+int flm_ecdsa_verify(flm_ctx *ctx, const uint8_t *pubkeys, const uint8_t *digests, const uint8_t *sigs, int n,
+                     uint8_t *ok_out, uint32_t *flags_out);
+int flm_ecdsa_verify_dev(flm_ctx *ctx, const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs,
+                         int n, uint8_t *d_ok_out, uint32_t *d_flags, void *stream);
 /* Batched scalar multiplication out[i] = scalars[i] * points[i]: the ECDH
  * (SA_ClientAgent.py:256-263), ElGamal (:434-447) and decryption-share
  * (:397-400) products, n independent elements per call. */

@@ -34,6 +34,7 @@ for _name, _res, _args in (
         ("flm_shamir_combine", _int, [_vp, _u8p, _u8p, _int, _int, _u8p]),
         ("flm_shamir_deal", _int, [_vp, _u8p, _int, _int, _u32p, _int, _u8p]),
         ("flm_aes_gcm_xor", _int, [_vp, _u8p, _u8p, _int, _u8p, _u8p, _sz, _int]),
+        ("flm_ecdsa_verify", _int, [_vp, _u8p, _u8p, _u8p, _int, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
         ("flm_ec_combine", _int, [_vp, _u8p, _u8p, _u8p, _int, _int, _int, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
         ("flm_group_init", _int, [ctypes.POINTER(_vp), _int, ctypes.POINTER(_int)]),
         ("flm_group_last_error", ctypes.c_char_p, [_vp]),
@@ -168,6 +169,30 @@ def aes_gcm_xor(keys, nonces, datas):
     _check(_lib.flm_aes_gcm_xor(_context(), k.ctypes.data_as(_u8p), nc.ctypes.data_as(_u8p), nl,
                                 d.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), ln, n))
     return [out[ln * i:ln * i + ln].tobytes() for i in range(n)]
+
+
+def ecdsa_verify(public_keys, messages, signatures):
+    """[DSS.new(key, 'fips-186-3').verify(SHA256.new(msg), sig) succeeded] for a batch: the check
+    SA_ClientAgent.py:387 leaves as `# CHECK SIGNATURES`, over the server's signature of the offline
+    set and the committee signatures it forwards in DEC (SA_ServiceAgent.py:382-386).  public_keys:
+    EccPoint-like objects (.x, .y), e.g. ECC.import_key(...).pointQ; messages: the signed bytes;
+    signatures: 64 bytes r || s each.  A forged signature is a False in the list, not an exception."""
+    import hashlib
+    n = len(signatures)
+    if n == 0:
+        return []
+    if len(public_keys) != n or len(messages) != n:
+        raise RuntimeError("one public key and one message per signature")
+    sg = np.zeros((n, 64), np.uint8)
+    for i, s in enumerate(signatures):
+        if len(s) == 64:                       # another length: r = s = 0, refused
+            sg[i] = np.frombuffer(bytes(s), np.uint8)
+    pk = _be([c for p in public_keys for c in (int(p.x), int(p.y))])
+    dg = np.frombuffer(b"".join(hashlib.sha256(bytes(m)).digest() for m in messages), np.uint8)
+    ok = np.zeros(n, np.uint8)
+    _check(_lib.flm_ecdsa_verify(_context(), pk.ctypes.data_as(_u8p), dg.ctypes.data_as(_u8p),
+                                 sg.ctypes.data_as(_u8p), n, ok.ctypes.data_as(_u8p), None))
+    return [bool(v) for v in ok]
 
 
 def ec_combine(c1_points, shares_by_member, coeffs):

@@ -4,8 +4,10 @@ import random
 P = 2**256 - 2**224 + 2**192 + 2**96 - 1
 M64 = (1 << 64) - 1
 
-def inv(x, outer=18, trace=None):
-    a, b, u, v = x, P, 1, 0
+def inv(x, outer=18, trace=None, mod=P):
+    """x^-1 mod `mod` (odd, below 2^256): p by default, the group order n for the ECDSA kernel"""
+    a, b, u, v = x, mod, 1, 0
+    ninv30 = (-pow(mod, -1, 1 << 30)) % (1 << 30)           # 1 for p
     for it in range(outer):
         n = max(a.bit_length(), b.bit_length(), 64)
         sh = n - 64
@@ -29,24 +31,25 @@ def inv(x, outer=18, trace=None):
         if nb < 0: nb, f1, g1 = -nb, -f1, -g1
         a, b = na, nb
         w0, w1 = u * f0 + v * g0, u * f1 + v * g1
-        q0, q1 = w0 % (1 << 30), w1 % (1 << 30)      # -p^-1 = 1 mod 2^30
-        u, v = (w0 + q0 * P) >> 30, (w1 + q1 * P) >> 30
-        assert -P <= u <= 2 * P and -P <= v <= 2 * P, (u, v)
-        u %= P; v %= P
+        q0, q1 = w0 * ninv30 % (1 << 30), w1 * ninv30 % (1 << 30)      # -p^-1 = 1 mod 2^30
+        assert (w0 + q0 * mod) % (1 << 30) == 0 and (w1 + q1 * mod) % (1 << 30) == 0
+        u, v = (w0 + q0 * mod) >> 30, (w1 + q1 * mod) >> 30
+        assert -mod <= u <= 2 * mod and -mod <= v <= 2 * mod, (u, v)
+        u %= mod; v %= mod
         if trace is not None and a == 0 and trace.get('done') is None: trace['done'] = it + 1
     assert a == 0 and b == 1, (x, a, b)
     return v
 
-def check(n_random=20000, seed=5):
+def check(n_random=20000, seed=5, mod=P):
     """Every input converges within the 18 outer steps and matches Fermat; returns the worst
     number of outer steps any input needed."""
     rng = random.Random(seed)
-    cases = [1, 2, 3, P - 1, P - 2, 2**255, 2**224, 2**96 - 1, (P - 1) // 2, 2**64 - 1, 2**30 + 1] + [rng.randrange(1, P) for _ in range(n_random)]
+    cases = [1, 2, 3, mod - 1, mod - 2, 2**255, 2**224, 2**96 - 1, (mod - 1) // 2, 2**64 - 1, 2**30 + 1] + [rng.randrange(1, mod) for _ in range(n_random)]
     worst = 0
     for x in cases:
         tr = {}
-        r = inv(x, trace=tr)
-        assert r == pow(x, P - 2, P), x
+        r = inv(x, trace=tr, mod=mod)
+        assert r == pow(x, mod - 2, mod), x
         worst = max(worst, tr['done'])
     return len(cases), worst
 
