@@ -754,10 +754,13 @@ bool signs_ok(const int8_t *signs, int K, int *nneg) {
     return true;
 }
 
-int check_range(flm_ctx *ctx, uint64_t slot_hi) {
-    if (slot_hi > (1ull << 36))
-        return fail(ctx, FLM_ERANGE, "PRG slot range ends at %llu > 2^36 (block counter high word must stay 0)",
-                    (unsigned long long)slot_hi);
+// The one rule for a PRG window of n slots from slot0: it must end at or below 2^36 (slot / 16 is the
+// 32-bit block counter).  Compared without forming slot0 + n, which wraps for a slot0 near 2^64.
+int check_range(flm_ctx *ctx, uint64_t slot0, uint64_t n) {
+    constexpr uint64_t kSlotLimit = 1ull << 36;
+    if (slot0 > kSlotLimit || n > kSlotLimit - slot0)
+        return fail(ctx, FLM_ERANGE, "PRG slots [%llu, +%llu) end beyond 2^36 (block counter high word must stay 0)",
+                    (unsigned long long)slot0, (unsigned long long)n);
     return 0;
 }
 
@@ -1393,7 +1396,7 @@ int host_round_async(flm_ctx *ctx, const uint32_t *const *rows, int N, const uin
     if (N < 0 || K < 0) return fail(ctx, FLM_EINVAL, "negative N or K");
     if ((N > 0 && !rows) || (K > 0 && (!seeds || !signs)) || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (!signs_ok(signs, K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, L)) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     const uint64_t pitch = round_up(L, 64);
     if (int rc = upload_rows(ctx, rows, N, L, pitch)) return rc;
@@ -1499,7 +1502,7 @@ int flm_aggregate_unmask(flm_ctx *ctx, const uint32_t *const *rows, int N, const
     if (L == 0) return 0;
     if (!out || (N > 0 && !rows) || (K > 0 && (!seeds || !signs))) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (!signs_ok(signs, K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, L)) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     const uint64_t pitch = round_up(L, 64);
     if (int rc = upload_rows(ctx, rows, N, L, pitch)) return rc;
@@ -1524,7 +1527,7 @@ static int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row
         return fail(ctx, FLM_EINVAL, "mask window [%zu,%zu) outside [0,%zu)", mask_lo, mask_hi, L);
     if ((mask_hi > mask_lo && mask_lo % 16) || prg_slot0 % 16)
         return fail(ctx, FLM_EINVAL, "mask_lo and prg_slot0 must be multiples of 16");
-    if (int rc = check_range(ctx, prg_slot0 + mask_hi)) return rc;
+    if (int rc = check_range(ctx, prg_slot0, mask_hi)) return rc;
     if (N > 0 && !d_rows) return fail(ctx, FLM_EINVAL, "rows is NULL");
     if (!d_out) return fail(ctx, FLM_EINVAL, "out is NULL");
     return 0;
@@ -1598,7 +1601,7 @@ int flm_client_mask(flm_ctx *ctx, const uint32_t *x, int N, const int64_t *seg, 
     if (K > 0 && (!seeds || !signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
     if (K > 0x7fffffff) return fail(ctx, FLM_EINVAL, "too many seeds");
     if (!signs_ok(signs, (int)K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, L)) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     const uint64_t pitch = round_up(L, 64);
     // one client's call (c5: 4 MiB in, 4 MiB out) runs in place: the kernel reads x from and writes y to the pinned
@@ -1630,7 +1633,7 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
     if (K > 0x7fffffff) return fail(ctx, FLM_EINVAL, "too many seeds");
     if (K > 0 && (!d_seeds || !signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
     if (!signs_ok(signs, (int)K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, L)) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
     // small batches (c2: 128 clients x ~15 seeds x 16384 slots): one launch of the small-round
@@ -1665,7 +1668,7 @@ int flm_prg_expand(flm_ctx *ctx, const uint8_t *seeds, int K, size_t L, uint64_t
     if (K == 0 || L == 0) return 0;
     if (!seeds || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (slot0 % 16) return fail(ctx, FLM_EINVAL, "slot0 must be a multiple of 16");
-    if (int rc = check_range(ctx, slot0 + L)) return rc;
+    if (int rc = check_range(ctx, slot0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     const uint64_t pitch = round_up(L, 64);
     HostCopies hc(ctx, ctx->stream);
@@ -1684,7 +1687,7 @@ int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, ui
     if (slot0 % 16) return fail(ctx, FLM_EINVAL, "slot0 must be a multiple of 16");
     if (pitch % 4 || pitch < round_up(L, 4)) return fail(ctx, FLM_EINVAL, "pitch must be a multiple of 4 and >= L");
     if ((uintptr_t)d_out & 15) return fail(ctx, FLM_EINVAL, "out must be 16-byte aligned");
-    if (int rc = check_range(ctx, slot0 + L)) return rc;
+    if (int rc = check_range(ctx, slot0, L)) return rc;
     if ((uint64_t)K * ((L + 1023) / 1024) > 0xFFFFFFFFull)
         return fail(ctx, FLM_EINVAL, "K=%d x %zu slots: more than 2^32 1024-slot units", K, L);
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
@@ -1724,7 +1727,7 @@ int flm_mask_accumulate(flm_ctx *ctx, const uint8_t *seeds, const int8_t *signs,
     if (!acc || (K > 0 && (!seeds || !signs))) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (slot0 % 16) return fail(ctx, FLM_EINVAL, "slot0 must be a multiple of 16");
     if (!signs_ok(signs, K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, slot0 + L)) return rc;
+    if (int rc = check_range(ctx, slot0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     const uint64_t pitch = round_up(L, 64);
     HostCopies hc(ctx, ctx->stream);
@@ -1767,6 +1770,7 @@ int flm_plan_aggregate(int subtiles, int pairing, size_t row_pitch, int N, int K
                        int *plan_flags) {
     if (N < 0 || K < 0 || mask_hi > L || mask_lo > mask_hi || !n_items)
         return fail(nullptr, FLM_EINVAL, "flm_plan_aggregate: bad arguments");
+    if (int rc = check_range(nullptr, prg_slot0, mask_hi)) return rc;
     std::vector<Item> items;
     Plan plan;
     build_aggregate_items(subtiles, pairing, row_pitch, N, K, L, mask_lo, mask_hi, prg_slot0, items, plan);

@@ -53,7 +53,8 @@ extern "C" {
 #define FLM_EINVAL (-1)   /* bad argument (length mismatch, sign not +-1, alignment) */
 #define FLM_EHIP (-2)     /* HIP runtime error */
 #define FLM_ENOMEM (-3)   /* device or pinned allocation failed */
-#define FLM_ERANGE (-4)   /* slot range beyond 2^36 (block counter high word must be 0) */
+#define FLM_ERANGE (-4)   /* slot range beyond 2^36 (block counter high word must be 0): a window of n slots from
+                             slot0 needs slot0 <= 2^36 and n <= 2^36 - slot0 (no 64-bit sum that could wrap) */
 
 typedef struct flm_ctx flm_ctx;
 
@@ -202,7 +203,8 @@ int flm_get_tuning(const flm_ctx *ctx, const char *key, int *value);
  * aggregate kernel would run for this round shape.  items_out receives up to
  * max_items 64-byte items (layout: flm_internal.h Item); *n_items the total;
  * *plan_flags bit0 zero-fill, bit1 atomics, bit2 single-tile, bit3 seed-light,
- * bits 8.. sub-tiles per workgroup.  subtiles/pairing as flm_set_tuning. */
+ * bits 8.. sub-tiles per workgroup.  subtiles/pairing as flm_set_tuning.
+ * FLM_ERANGE for a mask window past 2^36 slots, by the device entry points' own rule. */
 int flm_plan_aggregate(int subtiles, int pairing, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
                        size_t mask_hi, uint64_t prg_slot0, void *items_out, int max_items, int *n_items,
                        int *plan_flags);

@@ -5,6 +5,11 @@ seeds.shamir_share's arithmetic (Python Horner mod n), the AES cases by crypto.a
 (OpenSSL, tag dropped).  ``python tests/golden/make_deal_golden.py`` rewrites deal_golden.json;
 tests/test_deal_cpu.py re-runs it in memory.
 
+AES cases: every length of AES_LENS at n = 1 and 65; batches around one and two 256-message
+workgroups (AES_BATCH_NS); and the counter-wrap cases (aes_wrap_case), whose first rows carry
+16-byte nonces solved in GF(2^128) so that J0's low word is at the top of its range and inc32 wraps
+inside the message.  Their expected bytes are OpenSSL's like all the others.
+
 A byte field of the JSON has one of three forms, so that the file stays small:
   base64 text                               the bytes (edge inputs, expected outputs up to 1 KiB);
   {"prg", "n", "set": [[offset, b64]...]}   seeded random inputs: SHA-256 in counter mode over the
@@ -129,8 +134,93 @@ def aes_case(nl: int, ln: int, n: int, kind: int) -> dict:
     return case
 
 
+# ---- counter wrap: 16-byte nonces solved for a chosen J0 (NIST SP 800-38D, 7.1: keystream block m is
+# E_k(inc32^m(J0)), and inc32 wraps the low 32 bits without a carry into the upper 96)
+GCM_R = 0xE1 << 120
+AES_BATCH_NS = (255, 256, 257, 513)            # around one and two workgroups of the kernel (256 messages each)
+WRAP_LENS, WRAP_N = (17, 32, 256), 65
+WRAP_HIGH = 0x0123456789ABCDEFFFFFFFFF          # J0's upper 96 bits: a 64- or 128-bit increment would carry into them
+WRAP_LOWS = (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFF0)
+
+
+def gf_mul(x: int, y: int) -> int:
+    """x * y in GF(2^128) as GCM orders its bits (bit 0 = the top bit of byte 0)."""
+    z = 0
+    for i in range(127, -1, -1):
+        if (x >> i) & 1:
+            z ^= y
+        y = (y >> 1) ^ (GCM_R if y & 1 else 0)
+    return z
+
+
+def gf_inv(x: int) -> int:
+    """x^(2^128 - 2): square and multiply from the one, 1 || 0^127."""
+    r, e = 1 << 127, (1 << 128) - 2
+    while e:
+        if e & 1:
+            r = gf_mul(r, x)
+        x, e = gf_mul(x, x), e >> 1
+    return r
+
+
+def aes_ecb_block(key16: bytes, block16: bytes) -> bytes:
+    """E_k(block) through OpenSSL's EVP_aes_128_ecb (bound here: the product never needs it)."""
+    import ctypes
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from flamingo_amd import crypto as C
+    c = C._lib()
+    c.EVP_aes_128_ecb.restype, c.EVP_aes_128_ecb.argtypes = ctypes.c_void_p, []
+    ctx = c.EVP_CIPHER_CTX_new()
+    try:
+        assert c.EVP_EncryptInit_ex(ctx, c.EVP_aes_128_ecb(), None, key16, None) == 1
+        out, n = ctypes.create_string_buffer(32), ctypes.c_int(0)
+        assert c.EVP_EncryptUpdate(ctx, out, ctypes.byref(n), block16, 16) == 1 and n.value == 16
+        return out.raw[:16]
+    finally:
+        c.EVP_CIPHER_CTX_free(ctx)
+
+
+def gcm_j0(key16: bytes, nonce16: bytes) -> int:
+    """J0 = GHASH_H(nonce || 0^64 || [128]_64) of a 16-byte nonce, H = E_k(0^128)."""
+    h = int.from_bytes(aes_ecb_block(key16, bytes(16)), "big")
+    return gf_mul(gf_mul(int.from_bytes(nonce16, "big"), h) ^ 128, h)
+
+
+def nonce_for_j0(key16: bytes, j0: int) -> bytes:
+    """The 16-byte nonce whose J0 is j0: ((j0 H^-1) ^ [128]) H^-1."""
+    hi = gf_inv(int.from_bytes(aes_ecb_block(key16, bytes(16)), "big"))
+    return gf_mul(gf_mul(j0, hi) ^ 128, hi).to_bytes(16, "big")
+
+
+def wrap_lows(ln: int) -> tuple:
+    """The low words of J0 of a wrap case's crafted rows, three rows (keys) each: WRAP_LOWS, then the
+    last one that still wraps for this length -- the counter of the final block is 0."""
+    return WRAP_LOWS + ((1 << 32) - (ln + 15) // 16,)
+
+
+def aes_wrap_case(ln: int) -> dict:
+    """nonce_len 16, n = 65.  Row 3 q + kind has J0 = WRAP_HIGH || wrap_lows(ln)[q] under the all-zero
+    key (kind 0), the all-0xFF key (1) or the row's own seeded key (2); the other rows are seeded."""
+    label, n, lows = f"aes-wrap-{ln}", WRAP_N, wrap_lows(ln)
+    rows = 3 * len(lows)
+    keys = bytearray(prg(label + "-k", 16 * n))
+    kp, np_ = [], []
+    for i in range(rows):
+        if i % 3 < 2:
+            kp.append((16 * i, (b"\x00", b"\xff")[i % 3] * 16))
+            keys[16 * i:16 * i + 16] = kp[-1][1]
+        np_.append((16 * i, nonce_for_j0(bytes(keys[16 * i:16 * i + 16]), (WRAP_HIGH << 32) | lows[i // 3])))
+    case = {"name": f"aes_wrap_len{ln}_n{n}", "nonce_len": 16, "len": ln, "n": n, "wrap_rows": rows,
+            "keys": prg_field(label + "-k", 16 * n, kp), "nonces": prg_field(label + "-n", 16 * n, np_),
+            "data": prg_field(label + "-d", ln * n)}
+    case["out"] = out_field(aes_expected(case))
+    return case
+
+
 def generate() -> dict:
     aes = [aes_case(nl, ln, n, q % 3) for nl in (12, 16) for q, ln in enumerate(AES_LENS) for n in (1, 65)]
+    aes += [aes_case(nl, 32, n, 0) for nl in (12, 16) for n in AES_BATCH_NS]
+    aes += [aes_wrap_case(ln) for ln in WRAP_LENS]
     return {"n": hex(N), "shamir": [shamir_case(*k) for k in SHAMIR], "aes": aes}
 
 

@@ -78,8 +78,13 @@ def test_shamir_cases_recover_the_secret(fixture):
 
 def test_aes_cases_decrypt_back(fixture):
     from flamingo_amd import crypto as C
-    assert {(c["nonce_len"], c["len"], c["n"]) for c in fixture["aes"]} == \
-        {(nl, ln, n) for nl in (12, 16) for ln in G.AES_LENS for n in (1, 65)}
+    plain = [c for c in fixture["aes"] if "wrap_rows" not in c]
+    assert sorted((c["nonce_len"], c["len"], c["n"]) for c in plain) == \
+        sorted([(nl, ln, n) for nl in (12, 16) for ln in G.AES_LENS for n in (1, 65)]
+               + [(nl, 32, n) for nl in (12, 16) for n in G.AES_BATCH_NS])
+    assert [(c["nonce_len"], c["len"], c["n"]) for c in fixture["aes"] if "wrap_rows" in c] == \
+        [(16, ln, G.WRAP_N) for ln in G.WRAP_LENS]
+    assert len({c["name"] for c in fixture["aes"]}) == len(fixture["aes"])
     for case in fixture["aes"]:
         nl, ln, n = case["nonce_len"], case["len"], case["n"]
         k, nc, d = (G.field_bytes(case[f]) for f in ("keys", "nonces", "data"))
@@ -90,6 +95,62 @@ def test_aes_cases_decrypt_back(fixture):
                 d[ln * i:ln * i + ln], (case["name"], i)
     big = [c for c in fixture["aes"] if c["n"] == 65]
     assert all(G.field_bytes(c["keys"])[:32] == bytes(16) + b"\xff" * 16 for c in big)
+
+
+def _ghash_mul(x: int, h: int) -> int:
+    """x * h in GF(2^128), NIST SP 800-38D algorithm 1 on integers (bit 0 = the top bit)."""
+    z, v = 0, h
+    for i in range(128):
+        if x & (1 << (127 - i)):
+            z ^= v
+        v = (v >> 1) ^ (0xE1000000000000000000000000000000 if v & 1 else 0)
+    return z
+
+
+def _ctr_stream(key: bytes, j0: int, blocks: int, bits: int) -> bytes:
+    """E_k(J0 + 1) || ... || E_k(J0 + blocks), the sum taken in the low `bits` bits of J0."""
+    mask = (1 << bits) - 1
+    return b"".join(G.aes_ecb_block(key, ((j0 & ~mask) | ((j0 + m) & mask)).to_bytes(16, "big"))
+                    for m in range(1, blocks + 1))
+
+
+def test_wrap_cases_wrap_and_discriminate(fixture):
+    """The crafted rows of the counter-wrap cases: J0, recomputed from the committed nonce with a plain
+    GHASH, is 0x0123456789abcdef_ffffffff || w, and OpenSSL's bytes are the inc32 keystream.
+
+    A row wraps when the counter of its last block, w + ceil(len / 16), passes 0xffffffff.  The low
+    words 0xffffffff and 0xfffffffe wrap at every length of the fixture, 0xfffffff0 only at len = 256
+    (0xfffffff0 + 2 < 2^32: at len 17 and 32 those three rows run just below the wrap, and there inc32
+    and a 128-bit increment must agree); the rows with w = 2^32 - ceil(len / 16) wrap in their last block
+    at every length.  Every row that wraps with len >= 32 has expected bytes that differ from the
+    keystream of a 128-bit increment of J0, so a kernel that carried out of the low word fails there."""
+    wraps = [c for c in fixture["aes"] if "wrap_rows" in c]
+    assert [c["len"] for c in wraps] == list(G.WRAP_LENS)
+    xor = lambda a, b: bytes(p ^ q for p, q in zip(a, b))  # noqa: E731
+    for case in wraps:
+        ln, n, rows = case["len"], case["n"], case["wrap_rows"]
+        blocks, lows = (ln + 15) // 16, G.wrap_lows(ln)
+        assert rows == 3 * len(lows) and lows[:3] == (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFF0)
+        k, nc, d = (G.field_bytes(case[f]) for f in ("keys", "nonces", "data"))
+        out = G.expected(case)
+        assert k[:32] == bytes(16) + b"\xff" * 16
+        wrapped = 0
+        for i in range(rows):
+            key, data, want = k[16 * i:16 * i + 16], d[ln * i:ln * i + ln], out[ln * i:ln * i + ln]
+            assert key == (bytes(16), b"\xff" * 16, G.prg(case["keys"]["prg"], 16 * n)[16 * i:16 * i + 16])[i % 3]
+            h = int.from_bytes(G.aes_ecb_block(key, bytes(16)), "big")
+            j0 = _ghash_mul(_ghash_mul(int.from_bytes(nc[16 * i:16 * i + 16], "big"), h) ^ 128, h)
+            w = lows[i // 3]
+            assert j0 == (0x0123456789ABCDEFFFFFFFFF << 32) | w, (case["name"], i)
+            assert want == xor(data, _ctr_stream(key, j0, blocks, 32)), (case["name"], i)
+            wide = xor(data, _ctr_stream(key, j0, blocks, 128))
+            if w + blocks >= 1 << 32:
+                wrapped += 1
+                if ln >= 32:
+                    assert want != wide, (case["name"], i)
+            else:
+                assert (w, ln) in ((0xFFFFFFF0, 17), (0xFFFFFFF0, 32)) and want == wide, (case["name"], i)
+        assert wrapped == (rows if ln == 256 else rows - 3), case["name"]
 
 
 @pytest.mark.parametrize("committee,seed", [(9, 1), (60, 2), (4, 3), (1, 4)])

@@ -129,6 +129,35 @@ def test_plan_modes():
     assert gaps.max() <= 3
 
 
+def test_plan_range_rule():
+    """One rule for every PRG window (check_range in flm_runtime.hip, which flm_plan_aggregate
+    shares with the device entry points): prg_slot0 <= 2^36 and mask_hi <= 2^36 - prg_slot0, else
+    FLM_ERANGE.  The earlier guard tested prg_slot0 + mask_hi > 2^36 on the 64-bit sum, which wraps:
+    (2^64 - 16) + 32 = 16 and (2^64 - 2064) + 2064 = 0 both passed, and the launch ran with the
+    counter (uint32_t)(prg_slot0 / 16)."""
+    from flamingo_amd import _lib
+    lib = _lib.load()
+    FLM_ERANGE, top = -4, 1 << 36
+
+    def rc(prg_slot0, hi, L=None):
+        n = ctypes.c_int()
+        L = hi if L is None else L
+        return lib.flm_plan_aggregate(0, 1, (L + 63) // 64 * 64, 3, 5, L, 0, hi, ctypes.c_uint64(prg_slot0), None, 0,
+                                      ctypes.byref(n), None)
+
+    for slot0, hi in ((2**64 - 16, 32), (2**64 - 2064, 2064), (2**64 - 16, 16)):
+        assert (slot0 + hi) % 2**64 <= top                     # what the old expression compared with 2^36
+        assert rc(slot0, hi) == FLM_ERANGE, (slot0, hi)
+        assert b"2^36" in lib.flm_last_error(None)
+    assert rc(top - 2064, 2064) == 0                           # ends exactly at 2^36
+    assert rc(top - 16, 16) == 0
+    assert rc(top - 2064, 2064, L=4096) == 0                   # the row is longer, the window is not
+    assert rc(top, 0, L=64) == 0                               # an empty window at the limit
+    assert rc(top - 2048, 2064) == FLM_ERANGE                  # 2^36 + 16
+    assert rc(top + 16, 0, L=64) == FLM_ERANGE
+    assert rc(top, 16) == FLM_ERANGE
+
+
 def test_pick_cus_balances_xcds():
     """ServerReconstruction's EC CU set: CU-mask bit i selects XCD i % 8 (profiles/r01_cu_map_probe.log),
     so "first k" takes k/8 CUs from every XCD; the complement is what the unmask runs on."""
