@@ -12,9 +12,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(HERE, "csrc", f) for f in ("flm_kernels.hip", "flm_runtime.hip", "flm_p256.hip", "flm_comm.hip",
                                                         "flm_store.hip")]
-HDRS = [os.path.join(HERE, "csrc", "flm_internal.h"), os.path.join(HERE, "csrc", "flm_host_layout.h"),
-        os.path.join(HERE, "csrc", "flm_deal_args.h"), os.path.join(HERE, "csrc", "flm_ecdsa_args.h"),
-        os.path.join(os.path.dirname(HERE), "include", "flamingo_hip.h")]
+# every header makes the library stale: no list to keep by hand (tests/test_lib_abi.py checks the includes)
+HDRS = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith(".h")) + \
+    [os.path.join(os.path.dirname(HERE), "include", "flamingo_hip.h")]
 OUT = os.path.join(HERE, "lib", "libflamingo_hip.so")
 ARCH = os.environ.get("FLM_OFFLOAD_ARCH", "gfx950")
 

@@ -3,7 +3,7 @@
 // The seed recovery of one G = 8 rank (SA_ServiceAgent.py:542-585 over ceil(D/8) pairs) is a few
 // hundred waves on 1,024 SIMDs: a latency chain, and a lone wave issues one VALU instruction per
 // ~8 cycles, so its time is the instruction count on the critical path.  The
-// per-lane field multiplication of flm_p256.hip is ~258 instructions on one lane.  Here one field
+// per-lane field multiplication of flm_fe256.h is ~258 instructions on one lane.  Here one field
 // element occupies a DPP row: lane r = lane & 15 holds 32-bit limb r (little endian) for r < 8 and
 // 0 for r >= 8, so a multiplication is ~90 instructions per lane:
 //   * product scanning, one column per lane: lane t accumulates sum_i a_i b_(t-i) with a_i broadcast
@@ -92,7 +92,7 @@ __device__ __forceinline__ uint32_t snorm(int64_t v, const Ctx &K) {
 }
 
 // acc (64-bit) += a * b, carry out of the 64 bits counted in hi: one asm statement (v_mad_u64_u32's
-// own carry-out feeds one v_addc), as the per-lane product columns of flm_p256.hip.
+// own carry-out feeds one v_addc), as the per-lane product columns of flm_fe256.h.
 __device__ __forceinline__ void mad_carry(uint64_t &acc, uint32_t &hi, uint32_t a, uint32_t b) {
     uint64_t c;
     asm("v_mad_u64_u32 %[acc], %[c], %[a], %[b], %[acc]\n\t"

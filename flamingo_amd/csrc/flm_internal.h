@@ -116,7 +116,8 @@ hipError_t launch_shard_sum(const uint32_t *const *d_parts, int G, uint64_t lo, 
 hipError_t launch_chacha20_xor(const uint32_t key[8], const uint32_t nonce[2], uint64_t counter,
                                const uint8_t *d_in, uint8_t *d_out, size_t n, hipStream_t stream);
 
-// P-256 (flm_p256.hip). d_jac holds T*D Jacobian results as SoA planes [T][24][D].
+// P-256 (flm_p256.hip: the launchers and kernels; its device layers are the flm_fe256.h,
+// flm_jac256.h, flm_sha256.h and flm_aes128.h headers it alone includes). d_jac holds T*D Jacobian results as SoA planes [T][24][D].
 hipError_t launch_ec_mul(const uint8_t *d_points, const uint8_t *d_scalars, int per_element, int T, int D,
                          uint32_t *d_jac, uint32_t *d_flags, hipStream_t stream, int threads, int waves,
                          int coop = 0, int terms = 1, unsigned lds_pad = 0);

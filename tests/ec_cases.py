@@ -1,4 +1,4 @@
-"""Deterministic edge inputs for the P-256 kernels (flamingo_amd/csrc/flm_p256.hip, flm_fe_row.h) and
+"""Deterministic edge inputs for the P-256 kernels (flamingo_amd/csrc/flm_p256.hip over flm_fe256.h, flm_jac256.h and flm_fe_row.h) and
 their expected results from the big-int oracle (oracle/ec_oracle.py).  No test functions: the
 premises are checked without a GPU by tests/test_ec_cases_cpu.py, the kernels against them by
 tests/test_ec_edges_gpu.py.
@@ -37,7 +37,7 @@ ZERO_SEED = hashlib.sha256(bytes(64)).digest()
 
 # ------------------------------------------------------------------ the wNAF chain
 def naf5(k: int) -> list:
-    """wnaf5 of flm_p256.hip: NAF_LEN digits, least significant first, each 0 or odd in [-15, 15]."""
+    """wnaf5 of flm_jac256.h: NAF_LEN digits, least significant first, each 0 or odd in [-15, 15]."""
     assert 0 <= k < 2**256
     d = []
     for _ in range(NAF_LEN):

@@ -1,4 +1,4 @@
-"""The binary-GCD inversion schedule ec_finish_kernel runs (flm_p256.hip fe_inv_bingcd: 18 outer
+"""The binary-GCD inversion schedule ec_finish_kernel runs (flm_fe256.h fe_inv_bingcd: 18 outer
 steps of 30 inner steps, int32 update factors, 64-bit approximations), as its Python model
 tools/bingcd_model.py: it must converge within the 18 steps and agree with Fermat's a^(p-2).
 The GPU kernel itself is checked end to end by tests/test_ec_gpu.py (every combine inverts Z)."""

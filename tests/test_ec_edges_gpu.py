@@ -1,4 +1,4 @@
-"""The P-256 kernels (flamingo_amd/csrc/flm_p256.hip, flm_fe_row.h) where random inputs do not reach:
+"""The P-256 kernels (flamingo_amd/csrc/flm_p256.hip over flm_fe256.h, flm_jac256.h and flm_fe_row.h) where random inputs do not reach:
 the acc == Q and acc == -Q branches of the additions, field elements with all-zero / all-one / single-
 bit limbs, every compiled ec_mul_kernel<TPB, WPE>, batch sizes around every packing factor, the auto
 routing's thresholds, and the per-element flags of bad inputs with exact neighbours.

@@ -67,8 +67,12 @@ def test_crypto_verify_digest_is_openssl_on_the_digest():
 
 # ------------------------------------------------------------------ the kernel's constants and models
 def _hip_source() -> str:
-    with open(os.path.join(ROOT, "flamingo_amd", "csrc", "flm_p256.hip")) as f:
-        return f.read()
+    """flm_p256.hip (kGOdd) with the headers of its layers (kN0 is in flm_fe256.h)"""
+    src = ""
+    for name in ("flm_p256.hip", "flm_fe256.h", "flm_jac256.h"):
+        with open(os.path.join(ROOT, "flamingo_amd", "csrc", name)) as f:
+            src += f.read()
+    return src
 
 
 def test_constant_table_of_g_is_the_oracles():

@@ -57,6 +57,25 @@ def test_gfx950_code_object(lib):
     assert b"items_kernel" in data
 
 
+def test_every_included_project_header_makes_the_library_stale():
+    """Each #include "..." in csrc/*.hip and csrc/*.h resolves (beside the file, or under include/)
+    to a header in build.HDRS, so editing it rebuilds the library.  Reads files only."""
+    from flamingo_amd import build
+    csrc = os.path.join(ROOT, "flamingo_amd", "csrc")
+    hdrs = {os.path.realpath(h) for h in build.HDRS}
+    seen = 0
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, name)).read(), flags=re.M):
+            found = [p for p in (os.path.join(csrc, inc), os.path.join(ROOT, "include", inc)) if os.path.exists(p)]
+            assert found, (name, inc)
+            assert os.path.realpath(found[0]) in hdrs, (name, inc)
+            seen += 1
+    assert seen >= 10
+    assert all(os.path.exists(h) for h in build.HDRS)
+
+
 def test_round5_entry_points_reject_null_handles(lib):
     """flm_comm_destroy, flm_hash_to_curve*, flm_store_unmask_ms: a NULL context / store is an
     FLM_EINVAL with a message, before any device call (no GPU needed)."""

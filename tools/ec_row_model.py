@@ -7,7 +7,7 @@ the cooperative scalar multiplication's latency chain (DESIGN.md section 10.2, V
    and the number of carry passes each loop takes (the kernel loops while any lane of the wave
    carries, so the passes are part of the instruction count).
 2. VALU instructions per field operation for both layouts: the per-lane Montgomery field of
-   flm_p256.hip (gfx950 ISA counts, DESIGN.md section 5: fe_mul 258, fe_sqr 265, fe_add 28, fe_sub
+   flm_fe256.h (gfx950 ISA counts, DESIGN.md section 5: fe_mul 258, fe_sqr 265, fe_add 28, fe_sub
    20) and the row field (ISA counts of tools/probes/ec_row_probe.hip's chains, plus the carry
    passes from 1.).
 3. The critical path of the cooperative formulas (coop_dbl_w: 3 multiplication levels; coop_add_w: 5
@@ -106,7 +106,7 @@ def mean(h):
 
 
 # VALU instructions per operation on one wave's critical path.
-# Per-lane Montgomery field, gfx950 ISA of flm_p256.hip.
+# Per-lane Montgomery field, gfx950 ISA of flm_fe256.h.
 LANE = {"M": 258, "S": 265, "A": 28, "B": 20, "Z": 9}
 # Row field, ISA of tools/probes/ec_row_probe.hip (hipcc -O3, gfx950): the carry loops are
 # do-while (the first pass unconditional, then a wave-wide vote), so the multiply chain's loop is 93
