@@ -1,11 +1,15 @@
-// flm_host_layout.h -- where each array of a host-pointer call goes (HostCopies, flm_runtime.hip).
-// Plain C++ with no HIP in it, so the rule is checked on the CPU (tests/test_host_layout_cpu.py).
+// flm_host_layout.h -- where each array of a host-pointer call goes (HostCopies, flm_runtime.hip),
+// and how a large one is cut into staging-buffer pieces.  Plain C++ with no HIP in it, so the rules
+// are checked on the CPU (tests/test_host_layout_cpu.py, tools/planner_check.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 namespace flm {
-namespace rt {
+namespace rt __attribute__((visibility("hidden"))) {  // the library exports nothing of this header
 
 // One pinned staging buffer; also the size from which a copy skips the bounce buffer.
 constexpr size_t kStageBytes = size_t(32) << 20;
@@ -39,6 +43,22 @@ inline size_t host_layout(HostSpan *spans, int n) {
         total += (s.route == kRouteRing ? 0 : (s.rows * s.pitch + 255) / 256 * 256);
     }
     return total;
+}
+
+// Pieces of at most kStageBytes of a rows x width copy: whole rows, or one row's columns.
+struct Piece {
+    size_t r, c, w, nr;  // first row, first column, bytes per row, rows
+};
+inline std::vector<Piece> pieces(size_t width, size_t rows) {
+    std::vector<Piece> v;
+    if (width > kStageBytes) {
+        for (size_t r = 0; r < rows; ++r)
+            for (size_t c = 0; c < width; c += kStageBytes) v.push_back({r, c, std::min(kStageBytes, width - c), 1});
+    } else {
+        const size_t per = kStageBytes / width;
+        for (size_t r = 0; r < rows; r += per) v.push_back({r, 0, width, std::min(per, rows - r)});
+    }
+    return v;
 }
 
 }  // namespace rt

@@ -1,9 +1,10 @@
 // flm_runtime.hip -- host runtime and C ABI of libflamingo_hip.so (include/flamingo_hip.h).
 //
 // Owns one GPU per context: its stream, grow-on-demand device buffers, the
-// per-shape launch plans (work-item tables) and the error string.  The launch
-// planner turns a round's shape into Items (flm_internal.h) so that every
-// workgroup carries an equal share of row streaming and mask generation.
+// per-shape launch plans (work-item tables), their stream-ordering bookkeeping
+// (StreamMarks) and the error string.  What needs no device is in HIP-free headers:
+// the launch planner (flm_planner.h: a round's shape into Items), the CPU side of
+// the host copies (flm_copy_pool.h) and their layout (flm_host_layout.h).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -13,22 +14,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
 #include <map>
-#include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <tuple>
 #include <vector>
 
 #include "../../include/flamingo_hip.h"
+#include "flm_copy_pool.h"
 #include "flm_deal_args.h"
 #include "flm_ecdsa_args.h"
 #include "flm_internal.h"
+#include "flm_planner.h"
 
 using flm::Item;
 using flm::SeedRec;
+using flm::plan::PlanShape;
+using flm::rt::CopyPool;
 
 namespace {
 
@@ -62,27 +63,83 @@ struct DevBuf {
     T *as() const { return static_cast<T *>(p); }
 };
 
-// One contiguous job of the planner: out[out_base + l] for l in [0, L) gets the
-// sum of `nrows` rows (rows_base + r*pitch + l) and, for l in [mask_lo, mask_hi),
-// seeds [k0, k0+nseeds) at PRG slot prg_slot0 + l, plus mask_bias.
-struct Job {
-    uint64_t out_base = 0, rows_base = 0;
-    uint32_t nrows = 0;
-    uint64_t L = 0;
-    uint32_t k0 = 0, nseeds = 0;
-    uint64_t mask_lo = 0, mask_hi = 0, prg_slot0 = 0;
-    uint32_t mask_bias = 0;
-    bool bias_nneg = false;
+// True when the event has completed (or was never recorded); false while it is pending.  The one
+// place that queries an event.  After a not-ready query it clears the thread's last error, the
+// caller's sticky one included (fixable here, for every user at once).
+bool event_done(hipEvent_t e) {
+    if (!e) return true;
+    const hipError_t q = hipEventQuery(e);
+    if (q == hipSuccess) return true;
+    (void)hipGetLastError();  // hipErrorNotReady (an error status would surface at the next launch)
+    return false;
+}
+
+// The last use of one thing (a plan's items, a seed table) on every stream that used it: one
+// event per stream, recorded after each use there and reused.  Adds no dependency between the
+// streams by itself; the owner asks, waits or synchronises when it wants to rewrite the thing.
+class StreamMarks {
+  public:
+    StreamMarks() = default;
+    StreamMarks(const StreamMarks &) = delete;
+    StreamMarks &operator=(const StreamMarks &) = delete;
+    ~StreamMarks() { for (auto &m : marks_) (void)hipEventDestroy(m.second); }
+    // The work enqueued on s so far is the thing's last use on s.  Many streams over time: from
+    // kPrune entries a new stream first drops the entries already completed.
+    hipError_t record(hipStream_t s) {
+        hipEvent_t ev = event_of(s);
+        if (!ev) {
+            if (marks_.size() >= kPrune) {
+                size_t kept = 0;
+                for (const Mark &m : marks_) {
+                    if (event_done(m.second)) (void)hipEventDestroy(m.second);
+                    else marks_[kept++] = m;
+                }
+                marks_.erase(marks_.begin() + kept, marks_.end());
+            }
+            const hipError_t c = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (c != hipSuccess) return c;
+            marks_.emplace_back(s, ev);
+        }
+        return hipEventRecord(ev, s);
+    }
+    // the event of the last use on s, or NULL
+    hipEvent_t event_of(hipStream_t s) const {
+        for (const auto &m : marks_)
+            if (m.first == s) return m.second;
+        return nullptr;
+    }
+    // a use on a stream other than s has not completed yet
+    bool pending_elsewhere(hipStream_t s) const {
+        for (const auto &m : marks_)
+            if (m.first != s && !event_done(m.second)) return true;
+        return false;
+    }
+    // s waits, on the device, for the uses on every other stream
+    hipError_t wait_elsewhere(hipStream_t s) const {
+        hipError_t e = hipSuccess;
+        for (const auto &m : marks_)
+            if (e == hipSuccess && m.first != s) e = hipStreamWaitEvent(s, m.second, 0);
+        return e;
+    }
+    // the host waits for every use (up to the first error: the device has failed then)
+    hipError_t sync_all() const {
+        hipError_t e = hipSuccess;
+        for (const auto &m : marks_)
+            if (e == hipSuccess) e = hipEventSynchronize(m.second);
+        return e;
+    }
+    void swap(StreamMarks &o) { marks_.swap(o.marks_); }
+
+  private:
+    using Mark = std::pair<hipStream_t, hipEvent_t>;
+    static constexpr size_t kPrune = 8;
+    std::vector<Mark> marks_;
 };
 
 struct Plan {
     DevBuf items;
     int n_items = 0;
-    int subtiles = 1;
-    bool needs_zero = false;
-    int atomics = 0;
-    bool single_tile = true;  // every item writes one tile (merged accumulator legal)
-    bool seed_light = false;  // mask work small next to row streaming
+    PlanShape shape;  // what the planner said of the items (flm_planner.h)
     // a cached plan's items are copied in on the stream of its first launch; a launch on
     // another stream waits for that copy (`ready`) until it is known to have completed
     hipEvent_t ready = nullptr;
@@ -90,7 +147,7 @@ struct Plan {
     bool ready_known = true;
     // the plan's last launch on each stream it ran on (recorded by run_plan), and when it was last
     // used: the cache recycles its least recently used plan's buffers once those have completed
-    std::vector<std::pair<hipStream_t, hipEvent_t>> done;
+    StreamMarks done;
     uint64_t last_use = 0;
 };
 
@@ -128,91 +185,8 @@ struct SeedTable {
     hipEvent_t written = nullptr;
     bool written_valid = false;  // `written` was recorded after the last write (else a read on w_stream covers it)
     hipStream_t w_stream = nullptr;
-    std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
+    StreamMarks readers;
     uint64_t last_use = 0;
-};
-
-// Host copies between the caller's pageable arrays and the pinned bounce buffer (HostCopies), split
-// over a context's few worker threads and the calling thread: a 4 MiB in + 4 MiB out client mask
-// takes 0.34 ms of wall this way against 0.47 ms with one thread (profiles/r06_host_path_ab.txt).
-// Cutting the copies into 1 MiB pieces pipelined with the DMA, with workers spinning between pieces,
-// measured the same (0.34 ms) and was dropped.  Workers start lazily, on the first large copy.
-class CopyPool {
-  public:
-    static constexpr int kWorkers = 3;                      // + the calling thread
-    static constexpr size_t kMinSplit = size_t(256) << 10;  // below it the calling thread copies alone
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            stop_ = true;
-        }
-        work_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    // rows x width bytes, src rows at spitch, dst rows at dpitch; returns once every byte is copied
-    void copy2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows) {
-        const size_t n = width * rows;
-        if (n < kMinSplit) return part(dst, dpitch, src, spitch, width, 0, n);
-        std::lock_guard<std::mutex> one_job(call_);  // a context's callers are one thread, a store's adds too
-        if (th_.empty())
-            for (int i = 0; i < kWorkers; ++i) th_.emplace_back([this, i] { run(i + 1); });
-        {
-            std::lock_guard<std::mutex> g(m_);
-            job_ = {dst, dpitch, src, spitch, width, n};
-            pending_ = kWorkers;
-            ++gen_;
-        }
-        work_.notify_all();
-        slice(0);
-        std::unique_lock<std::mutex> l(m_);
-        done_.wait(l, [this] { return pending_ == 0; });
-    }
-
-  private:
-    struct Job {
-        void *dst;
-        size_t dpitch;
-        const void *src;
-        size_t spitch, width, n;
-    };
-    // bytes [b, e) of the packed rows x width range
-    static void part(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t b, size_t e) {
-        while (b < e) {
-            const size_t r = b / width, c = b % width, m = std::min(width - c, e - b);
-            std::memcpy(static_cast<uint8_t *>(dst) + r * dpitch + c, static_cast<const uint8_t *>(src) + r * spitch + c, m);
-            b += m;
-        }
-    }
-    void slice(int i) {  // slice i of kWorkers + 1, 4 KiB-aligned bounds
-        const size_t per = ((job_.n + kWorkers) / (kWorkers + 1) + 4095) / 4096 * 4096;
-        const size_t b = std::min(job_.n, per * i), e = std::min(job_.n, b + per);
-        part(job_.dst, job_.dpitch, job_.src, job_.spitch, job_.width, b, e);
-    }
-    void run(int i) {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> l(m_);
-                work_.wait(l, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-            }
-            slice(i);
-            bool last;
-            {
-                std::lock_guard<std::mutex> g(m_);
-                last = --pending_ == 0;
-            }
-            if (last) done_.notify_one();
-        }
-    }
-    std::mutex call_, m_;
-    std::condition_variable work_, done_;
-    std::vector<std::thread> th_;
-    Job job_{};
-    uint64_t gen_ = 0;
-    int pending_ = 0;
-    bool stop_ = false;
 };
 
 }  // namespace
@@ -251,7 +225,7 @@ struct flm_ctx {
     int table_k = -1;  // seeds in the published device seed table (pub_table), -1 = none
     int tune_variant = -1;   // items_kernel variant, -1 = auto
     int tune_subtiles = 0;   // aggregate sub-tiles per workgroup, 0 = auto
-    int tune_min_items = 1024;  // planner target for work items per aggregate launch (kDefaultMinItems)
+    int tune_min_items = flm::plan::kDefaultMinItems;  // planner target for work items per aggregate launch
     int tune_ec_threads = 64;   // ec_mul workgroup size (64/128/256; 64 measured best, 3.29 vs 3.43 ms)
     int tune_ec_waves = 1;      // ec_mul register budget as min waves/SIMD (1 = uncapped, 4, 8)
     int tune_ec_spread = 0;     // KiB of LDS reserved per 64-lane EC workgroup (0 = none): caps EC waves per CU
@@ -302,16 +276,46 @@ int fail(flm_ctx *ctx, int code, const char *fmt, ...) {
 
 inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
+// The tuning keys: the context member behind each, the values it takes and the refusal of any
+// other (which may print the value).  flm_set_tuning and flm_get_tuning read this one table.
+struct TuneKey {
+    const char *name;
+    int flm_ctx::*member;
+    bool (*accepts)(int);
+    const char *refusal;
+};
+template <int Lo, int Hi> bool within(int v) { return v >= Lo && v <= Hi; }
+template <int... V> bool one_of(int v) { return ((v == V) || ...); }
+const TuneKey kTuneKeys[] = {
+    {"variant", &flm_ctx::tune_variant, within<-1, flm::kVarCount - 1>, "variant %d out of range"},
+    {"pairing", &flm_ctx::tune_pairing, within<0, 2>, "pairing must be 0, 1 or 2"},
+    {"subtiles", &flm_ctx::tune_subtiles, one_of<0, 1, 4, 16>, "subtiles must be 0 (auto), 1, 4 or 16"},
+    {"ec_waves", &flm_ctx::tune_ec_waves, one_of<1, 4, 8>, "ec_waves must be 1, 4 or 8"},
+    {"small", &flm_ctx::tune_small, within<0, 2>, "small must be 0 (never), 1 (auto) or 2 (when legal)"},
+    {"min_items", &flm_ctx::tune_min_items, within<64, 1 << 20>, "min_items must be in [64, 2^20]"},
+    {"ec_spread", &flm_ctx::tune_ec_spread, within<0, 64>, "ec_spread must be in [0, 64] KiB"},
+    {"ec_terms", &flm_ctx::tune_ec_terms, one_of<1, 2, 4>, "ec_terms must be 1, 2 or 4"},
+    {"ec_coop", &flm_ctx::tune_ec_coop, within<-1, 2>, "ec_coop must be -1, 0, 1 or 2"},
+    {"expand_waves", &flm_ctx::tune_expand_waves, within<1, 256>, "expand_waves must be in [1, 256]"},
+    {"ec_threads", &flm_ctx::tune_ec_threads, one_of<64, 128, 256>, "ec_threads must be 64, 128 or 256"},
+};
+const TuneKey *tune_key(const char *key) {
+    for (const TuneKey &t : kTuneKeys)
+        if (!std::strcmp(key, t.name)) return &t;
+    return nullptr;
+}
+
+// What flm_last_plan reports: the launch just enqueued.
+void set_last_plan(flm_ctx *ctx, int items, int tile_slots, int atomics, int variant) {
+    ctx->last_items = items, ctx->last_tile = tile_slots, ctx->last_atomics = atomics, ctx->last_variant = variant;
+}
+
 // A staging slot of >= `bytes` that no queued work reads any more (StageSlot).  The host
 // waits only when all kStageSlots slots are still queued: then for the oldest.
 StageSlot *stage_acquire(flm_ctx *ctx, size_t bytes, int *rc) {
     StageSlot *best = nullptr, *free_small = nullptr, *oldest = nullptr;
     for (StageSlot *s : ctx->slots) {
-        if (s->busy) {
-            const hipError_t q = hipEventQuery(s->done);
-            if (q == hipSuccess) s->busy = false;
-            else if (q != hipErrorNotReady) (void)hipGetLastError();
-        }
+        if (s->busy && event_done(s->done)) s->busy = false;
         if (s->busy) {
             if (!oldest || s->last < oldest->last) oldest = s;
         } else if (s->cap >= bytes) {
@@ -393,151 +397,6 @@ hipError_t stage_commit(StageSlot *slot, hipStream_t s) {
     return e;
 }
 
-// ------------------------------------------------------------------ planner
-// Split a job into row units (tiles x row parts) and mask units (tiles x seed
-// parts) of equal weight, then pair unit i of each list into one Item, so one
-// workgroup streams rows (HBM) while it generates masks (VALU).
-struct Unit {
-    uint64_t tile;  // out slot of the tile start (relative to job)
-    uint32_t a, n;  // row or seed sub-range
-    uint32_t valid;
-    uint32_t part;
-};
-
-void plan_job(const Job &j, uint64_t pitch, int subtiles, int parts_r, int parts_m, bool dual_tile,
-              std::vector<Item> &items, bool &needs_zero, int &atomics, bool &single_tile) {
-    const uint64_t W = (uint64_t)flm::kWaveSlots * subtiles;
-    std::vector<Unit> R, M;
-    if (j.nrows > 0 && j.L > 0) {
-        for (uint64_t t = 0; t < j.L; t += W)
-            for (int p = 0; p < parts_r; ++p) {
-                uint32_t a = (uint32_t)((uint64_t)j.nrows * p / parts_r);
-                uint32_t b = (uint32_t)((uint64_t)j.nrows * (p + 1) / parts_r);
-                if (b > a) R.push_back({t, a, b - a, (uint32_t)std::min<uint64_t>(W, j.L - t), (uint32_t)p});
-            }
-    }
-    if (j.nseeds > 0 && j.mask_hi > j.mask_lo) {
-        for (uint64_t t = j.mask_lo; t < j.mask_hi; t += W)
-            for (int p = 0; p < parts_m; ++p) {
-                uint32_t a = (uint32_t)((uint64_t)j.nseeds * p / parts_m);
-                uint32_t b = (uint32_t)((uint64_t)j.nseeds * (p + 1) / parts_m);
-                if (b > a)
-                    M.push_back({t, a, b - a, (uint32_t)std::min<uint64_t>(W, j.mask_hi - t), (uint32_t)p});
-            }
-    }
-    // A tile written by exactly one Item is stored; otherwise every contributor
-    // adds atomically into a zeroed output.  Rows and masks share one Item per
-    // tile ("same tile") in whole-vector rounds whose rows and seeds are cut into
-    // the same number of parts: unit i of each list then covers the same tile, and
-    // the item keeps the merged single-accumulator kernel (atomic when parts > 1).
-    const bool both = !R.empty() && !M.empty();
-    bool paired_same = both && parts_r == parts_m && j.mask_lo == 0 && j.mask_hi == j.L && R.size() == M.size();
-    for (size_t i = 0; paired_same && i < R.size(); ++i) paired_same = R[i].tile == M[i].tile;
-    const bool atomic = parts_r > 1 || parts_m > 1 || (both && !paired_same);
-    if (atomic) needs_zero = true;
-    if (R.empty() && (j.mask_lo > 0 || j.mask_hi < j.L || M.empty())) needs_zero = true;
-    atomics |= atomic ? 1 : 0;
-
-    // Rows and masks on different tiles: either pair them into dual-tile items
-    // (one workgroup streams rows of tile A while generating masks of tile B), or
-    // emit single-kind items interleaved R0 M0 R1 M1 ... so row and mask
-    // workgroups share CUs and each can use the merged-accumulator kernel.
-    if (both && !paired_same && !dual_tile) {
-        const size_t n2 = std::max(R.size(), M.size());
-        for (size_t i = 0; i < n2; ++i) {
-            if (i < R.size()) {
-                Item it;
-                std::memset(&it, 0, sizeof it);
-                const Unit &u = R[i];
-                it.flags = flm::kHasRows | flm::kRowAtomic;
-                it.row_in = j.rows_base + (uint64_t)u.a * pitch + u.tile;
-                it.nrows = u.n;
-                it.row_out = j.out_base + u.tile;
-                it.row_valid = u.valid;
-                items.push_back(it);
-            }
-            if (i < M.size()) {
-                Item it;
-                std::memset(&it, 0, sizeof it);
-                const Unit &u = M[i];
-                it.flags = flm::kHasMask | flm::kMaskAtomic;
-                it.k0 = j.k0 + u.a;
-                it.nseeds = u.n;
-                it.mask_out = j.out_base + u.tile;
-                it.mask_ctr = (j.prg_slot0 + u.tile) / 16;
-                it.mask_valid = u.valid;
-                if (u.part == 0) {
-                    it.mask_bias = j.mask_bias;
-                    if (j.bias_nneg) it.flags |= flm::kMaskBiasNneg;
-                }
-                items.push_back(it);
-            }
-        }
-        return;
-    }
-    if (both && !paired_same) single_tile = false;
-
-    const size_t n = std::max(R.size(), M.size());
-    for (size_t i = 0; i < n; ++i) {
-        Item it;
-        std::memset(&it, 0, sizeof it);
-        if (i < R.size()) {
-            const Unit &u = R[i];
-            it.flags |= flm::kHasRows | (atomic ? flm::kRowAtomic : 0u);
-            it.row_in = j.rows_base + (uint64_t)u.a * pitch + u.tile;
-            it.nrows = u.n;
-            it.row_out = j.out_base + u.tile;
-            it.row_valid = u.valid;
-        }
-        if (i < M.size()) {
-            const Unit &u = M[i];
-            it.flags |= flm::kHasMask | (atomic ? flm::kMaskAtomic : 0u);
-            it.k0 = j.k0 + u.a;
-            it.nseeds = u.n;
-            it.mask_out = j.out_base + u.tile;
-            it.mask_ctr = (j.prg_slot0 + u.tile) / 16;
-            it.mask_valid = u.valid;
-            if (u.part == 0) {  // per-slot constants are added exactly once
-                it.mask_bias = j.mask_bias;
-                if (j.bias_nneg) it.flags |= flm::kMaskBiasNneg;
-            }
-            if (paired_same && i < R.size() && R[i].tile == u.tile) it.flags |= flm::kSameTile;
-        }
-        items.push_back(it);
-    }
-}
-
-int choose_parts(uint64_t tiles_r, uint64_t tiles_m, uint32_t nrows, uint32_t nseeds, int &pr, int &pm,
-                 uint64_t kTarget = 1024) {
-    // Balance mask units against row units, then split both until the grid
-    // has a few workgroups per CU (16 waves each), keeping >= 16 rows/seeds
-    // per item so every wave of a workgroup has work.
-    pr = 1;
-    pm = 1;
-    if (tiles_r && tiles_m && tiles_r > tiles_m) pm = (int)std::min<uint64_t>(nseeds, (tiles_r + tiles_m - 1) / tiles_m);
-    if (tiles_r && tiles_m && tiles_m > tiles_r) pr = (int)std::min<uint64_t>(nrows, (tiles_m + tiles_r - 1) / tiles_r);
-    auto units = [&] { return std::max(tiles_r * pr, tiles_m * pm); };
-    while (units() < kTarget) {
-        bool grew = false;
-        if (tiles_r && (uint64_t)pr * 2 * 16 <= nrows) { pr *= 2; grew = true; }
-        if (tiles_m && (uint64_t)pm * 2 * 16 <= nseeds) { pm *= 2; grew = true; }
-        if (!grew) break;
-    }
-    return 0;
-}
-
-int pick_variant(const flm_ctx *ctx, const Plan &plan) {
-    int v = ctx->tune_variant;
-    // measured (tools/ab/ab_items.py, profiles/r01_ab_items*.log): merged accumulator
-    // fastest where legal (seeds spread over the rows when seed-light), block next
-    if (v < 0)
-        v = plan.single_tile ? (plan.seed_light ? flm::kVarMergedSpread : flm::kVarMerged)
-                             : (plan.seed_light ? flm::kVarBlockSpread : flm::kVarBlock);
-    if (!plan.single_tile && v >= flm::kVarMerged) v = (v == flm::kVarMergedSpread || v == flm::kVarBlockSpread)
-                                                          ? flm::kVarBlockSpread : flm::kVarBlock;
-    return v;
-}
-
 // The items go through a staging slot on `s` and the plan records `ready` for launches on
 // other streams (run_plan).
 int upload_plan(flm_ctx *ctx, Plan &plan, std::vector<Item> &items, hipStream_t s) {
@@ -561,141 +420,10 @@ int upload_plan(flm_ctx *ctx, Plan &plan, std::vector<Item> &items, hipStream_t 
 void plan_free(Plan *plan) {
     plan->items.release();
     if (plan->ready) (void)hipEventDestroy(plan->ready);
-    for (auto &d : plan->done) (void)hipEventDestroy(d.second);
-    delete plan;
+    delete plan;  // and with it the events of its launches (StreamMarks)
 }
 
 constexpr size_t kPlanCache = 64;        // launch plans kept per context (shapes)
-constexpr int kDefaultMinItems = 1024;   // flm_set_tuning("min_items") default
-constexpr uint64_t kUnsplitTiles = 1024;  // 4 tiles per MI355X CU: from this many a whole-vector round is not split
-constexpr uint64_t kSplitItems = 2048;    // item target of a split whole-vector round (8 per CU)
-constexpr int kWindowItems = 512;         // item target of a windowed (slot-sharded) round: 2 per CU
-
-// A rank of the slot-sharded round as same-tile items (pairing 2).  The shard's 1024-slot tiles
-// carry rows AND seeds, cut into P matching parts (part p of a tile: rows [N p/P, N (p+1)/P) and
-// seeds [K p/P, K (p+1)/P), atomics when P > 1); every other tile is one rows-only item, spread
-// evenly between the heavy items so that row streaming runs beside the ChaCha work from the
-// start.  Every item writes one tile, so the merged single-accumulator kernel runs (63 VGPRs,
-// 8 waves/SIMD) instead of the dual-tile kernel (104 VGPRs, 4 waves/SIMD).  Measured slower than
-// the dual-tile items at G = 2 / 4 / 8 (0.78 / 0.42 / 0.228 ms against 0.69 / 0.36 / 0.188 ms,
-// profiles/r02_ab_window_same.log): a tuning option (flm_set_tuning "pairing" 2), not the default.
-void plan_window_same(uint64_t pitch, int N, int K, uint64_t L, uint64_t mask_lo, uint64_t mask_hi,
-                      uint64_t prg_slot0, uint64_t heavy_target, std::vector<Item> &items, Plan &plan) {
-    const uint64_t W = flm::kWaveSlots;
-    const uint64_t tm = (mask_hi - mask_lo + W - 1) / W;
-    uint64_t P = tm ? (heavy_target + tm - 1) / tm : 1;
-    while (P > 1 && (uint64_t)K < 16 * P) P /= 2;  // >= 16 seeds per part: every wave has work
-    if (P < 1) P = 1;
-    std::vector<Item> heavy, light;
-    for (uint64_t t = mask_lo; t < mask_hi; t += W) {
-        const uint32_t valid = (uint32_t)std::min<uint64_t>(W, mask_hi - t);
-        for (uint64_t p = 0; p < P; ++p) {
-            Item it;
-            std::memset(&it, 0, sizeof it);
-            const uint32_t ra = (uint32_t)((uint64_t)N * p / P), rb = (uint32_t)((uint64_t)N * (p + 1) / P);
-            const uint32_t sa = (uint32_t)((uint64_t)K * p / P), sb = (uint32_t)((uint64_t)K * (p + 1) / P);
-            const uint32_t at = P > 1 ? (flm::kRowAtomic | flm::kMaskAtomic) : 0u;
-            if (rb > ra) {
-                it.flags |= flm::kHasRows | at;
-                it.row_in = (uint64_t)ra * pitch + t;
-                it.nrows = rb - ra;
-                it.row_out = t;
-                it.row_valid = valid;
-            }
-            if (sb > sa) {
-                it.flags |= flm::kHasMask | at | (rb > ra ? flm::kSameTile : 0u);
-                it.k0 = sa;
-                it.nseeds = sb - sa;
-                it.mask_out = t;
-                it.mask_ctr = (prg_slot0 + t) / 16;
-                it.mask_valid = valid;
-                if (p == 0) it.flags |= flm::kMaskBiasNneg;
-            }
-            if (it.flags) heavy.push_back(it);
-        }
-    }
-    auto rows_only = [&](uint64_t a, uint64_t b) {
-        for (uint64_t t = a; t < b; t += W) {
-            Item it;
-            std::memset(&it, 0, sizeof it);
-            it.flags = flm::kHasRows;
-            it.row_in = t;
-            it.nrows = (uint32_t)N;
-            it.row_out = t;
-            it.row_valid = (uint32_t)std::min<uint64_t>(W, b - t);
-            light.push_back(it);
-        }
-    };
-    rows_only(0, mask_lo);
-    rows_only(mask_hi, L);
-    // interleave: light item j goes after heavy item floor((j + 1) * H / (Lt + 1))
-    const size_t H = heavy.size(), Lt = light.size();
-    items.reserve(H + Lt);
-    size_t j = 0;
-    for (size_t h = 0; h < H; ++h) {
-        items.push_back(heavy[h]);
-        while (j < Lt && (j + 1) * H <= (h + 1) * (Lt + 1)) items.push_back(light[j++]);
-    }
-    while (j < Lt) items.push_back(light[j++]);
-    plan.subtiles = 1;
-    plan.seed_light = false;
-    plan.single_tile = true;
-    plan.needs_zero = P > 1;
-    plan.atomics = P > 1 ? 1 : 0;
-}
-
-// Host-only planning of one aggregate round (no device state): fills `items`
-// and the plan's flags.  Shared by aggregate_plan and the flm_plan_aggregate
-// diagnostic entry point.
-void build_aggregate_items(int tune_subtiles, int pairing, uint64_t pitch, int N, int K, uint64_t L, uint64_t mask_lo,
-                           uint64_t mask_hi, uint64_t prg_slot0, std::vector<Item> &items, Plan &plan,
-                           int min_items = 1024) {
-    // ChaCha-heavy rounds keep 1024-slot tiles (16 waves split one tile's seeds);
-    // row-streaming-heavy rounds (few seeds per slot) prefer 4 sub-tiles per
-    // workgroup: 4096-slot tiles, fewer LDS combines (measured 5.77 vs 5.26 TB/s).
-    const bool seed_light = (uint64_t)K * (mask_hi - mask_lo) * 2 < (uint64_t)N * L;
-    // A rank of the slot-sharded round (rows over all of L, masks over a window): 4096-slot
-    // tiles and kWindowItems items, one generation of workgroups on the chip.  One rank of the
-    // strong-scaled c4 round, G = 8: 0.179 -> 0.169 ms; G = 4: 0.364 -> 0.350-0.360 ms; G = 2 the
-    // same (profiles/r02_ab_strong_plan.log).
-    const bool windowed = N > 0 && K > 0 && (mask_lo > 0 || mask_hi < L);
-    if (pairing == 2 && windowed && !seed_light && tune_subtiles <= 0) {
-        plan_window_same(pitch, N, K, L, mask_lo, mask_hi, prg_slot0, (uint64_t)min_items, items, plan);
-        return;
-    }
-    const int subtiles = tune_subtiles > 0 ? tune_subtiles : ((seed_light || windowed) ? 4 : 1);
-    const uint64_t W = (uint64_t)flm::kWaveSlots * subtiles;
-    Job j;
-    j.nrows = (uint32_t)N;
-    j.L = L;
-    j.nseeds = (uint32_t)K;
-    j.mask_lo = mask_lo;
-    j.mask_hi = mask_hi;
-    j.prg_slot0 = prg_slot0;
-    j.bias_nneg = true;
-    const uint64_t tr = N > 0 ? (L + W - 1) / W : 0;
-    const uint64_t tm = (K > 0 && mask_hi > mask_lo) ? (mask_hi - mask_lo + W - 1) / W : 0;
-    int pr, pm;
-    if (!seed_light && min_items == kDefaultMinItems && mask_lo == 0 && mask_hi == L && tr == tm && tm > 0) {
-        // A whole-vector ChaCha-heavy round: rows and seeds are cut into the same number of parts P,
-        // so part p of both lands in one item and the merged single-accumulator kernel runs
-        // (plan_job).  From kUnsplitTiles tiles (4 per CU: c4 / c5, 1024 tiles) one item per tile --
-        // no atomics, no zero-fill; 2048 items measured no faster there.  Fewer tiles (c3, N=1024,
-        // L=2^18: 256 tiles) are split until kSplitItems items: 0.389 ms at P=8 against 0.414 ms
-        // unsplit (one 4-wave/SIMD generation) and 0.410 at P=2 (profiles/r02_ab_split.log).
-        pr = pm = 1;
-        while (tm < kUnsplitTiles && tm * (uint64_t)pr < kSplitItems && (uint64_t)pr * 2 * 16 <= (uint64_t)N &&
-               (uint64_t)pr * 2 * 16 <= (uint64_t)K)
-            pr = pm = pr * 2;
-    } else {
-        const int target = (windowed && !seed_light && tune_subtiles <= 0 && min_items == kDefaultMinItems)
-                               ? kWindowItems : min_items;
-        choose_parts(tr, tm, (uint32_t)N, (uint32_t)K, pr, pm, (uint64_t)target);
-    }
-    plan.subtiles = subtiles;
-    plan.seed_light = seed_light;
-    plan_job(j, pitch, subtiles, pr, pm, pairing != 0, items, plan.needs_zero, plan.atomics, plan.single_tile);
-}
 
 Plan *aggregate_plan(flm_ctx *ctx, uint64_t pitch, int N, int K, uint64_t L, uint64_t mask_lo, uint64_t mask_hi,
                      uint64_t prg_slot0, hipStream_t s, int *rc) {
@@ -717,9 +445,7 @@ Plan *aggregate_plan(flm_ctx *ctx, uint64_t pitch, int N, int K, uint64_t L, uin
         for (auto it = ctx->plans.begin(); it != ctx->plans.end(); ++it)
             if (it->second->last_use < lru->second->last_use) lru = it;
         Plan *old = lru->second;
-        hipError_t e = hipSuccess;
-        for (auto &d : old->done)  // long done, as a rule
-            if (e == hipSuccess) e = hipEventSynchronize(d.second);
+        hipError_t e = old->done.sync_all();  // long done, as a rule
         if (e == hipSuccess && old->ready) e = hipEventSynchronize(old->ready);
         if (e != hipSuccess) {
             *rc = fail(ctx, FLM_EHIP, "plan cache: waiting for a recycled plan failed: %s", hipGetErrorString(e));
@@ -735,8 +461,8 @@ Plan *aggregate_plan(flm_ctx *ctx, uint64_t pitch, int N, int K, uint64_t L, uin
         plan = new Plan();
     }
     std::vector<Item> items;
-    build_aggregate_items(ctx->tune_subtiles, ctx->tune_pairing, pitch, N, K, L, mask_lo, mask_hi, prg_slot0, items,
-                          *plan, ctx->tune_min_items);
+    plan->shape = flm::plan::build_aggregate_items(ctx->tune_subtiles, ctx->tune_pairing, pitch, N, K, L, mask_lo, mask_hi,
+                                                   prg_slot0, items, ctx->tune_min_items);
     *rc = upload_plan(ctx, *plan, items, s);
     if (*rc) { plan_free(plan); return nullptr; }
     plan->last_use = ++ctx->plan_clock;
@@ -754,44 +480,18 @@ bool signs_ok(const int8_t *signs, int K, int *nneg) {
     return true;
 }
 
-// The one rule for a PRG window of n slots from slot0: it must end at or below 2^36 (slot / 16 is the
-// 32-bit block counter).  Compared without forming slot0 + n, which wraps for a slot0 near 2^64.
+// The one rule for a PRG window of n slots from slot0 (flm::plan::slot_range_ok), as an error.
 int check_range(flm_ctx *ctx, uint64_t slot0, uint64_t n) {
-    constexpr uint64_t kSlotLimit = 1ull << 36;
-    if (slot0 > kSlotLimit || n > kSlotLimit - slot0)
+    if (!flm::plan::slot_range_ok(slot0, n))
         return fail(ctx, FLM_ERANGE, "PRG slots [%llu, +%llu) end beyond 2^36 (block counter high word must stay 0)",
                     (unsigned long long)slot0, (unsigned long long)n);
     return 0;
 }
 
-// Workgroup width B (16*B slots) of the one-launch small-round kernel for this round, or 0 to
-// take the seed-schedule + items_kernel path.  Auto (tune_small 1): rounds whose rows and mask
-// words are both <= 2^22 (c2: 2^21 each), where items_kernel's fixed ~10 us dominates.
-int small_round_width(const flm_ctx *ctx, int N, int K, uint64_t L, uint64_t mask_lo, uint64_t mask_hi) {
-    if (ctx->tune_small == 0) return 0;
-    if (mask_lo % 16 || (mask_hi % 16 && mask_hi != L)) return 0;
-    if (ctx->tune_small == 1 && ((uint64_t)N * L > (1ull << 22) || (uint64_t)K * (mask_hi - mask_lo) > (1ull << 22)))
-        return 0;
-    // 2 blocks per 256-thread workgroup keeps 128 seeds per pass (c2: one pass, every lane busy);
-    // longer vectors take 4 (64 slots) so the grid stays near 1024 workgroups
-    return L >= (1ull << 16) ? 4 : 2;
-}
-
-// True when the event has completed (or was never recorded); false while it is pending.
-bool event_done(hipEvent_t e) {
-    if (!e) return true;
-    const hipError_t q = hipEventQuery(e);
-    if (q == hipSuccess) return true;
-    (void)hipGetLastError();  // hipErrorNotReady (an error status would surface at the next launch)
-    return false;
-}
-
 // No read or write of `t` on a stream other than s is still pending: s may rewrite it at once.
 bool table_free_on(const SeedTable *t, hipStream_t s) {
     if (t->w_stream != s && t->written_valid && !event_done(t->written)) return false;
-    for (const auto &r : t->readers)
-        if (r.first != s && !event_done(r.second)) return false;
-    return true;
+    return !t->readers.pending_elsewhere(s);
 }
 
 // A seed table stream s may overwrite, grown to hold K records and `meta_words` sign-count words
@@ -815,8 +515,7 @@ SeedTable *table_acquire(flm_ctx *ctx, int K, size_t meta_words, hipStream_t s, 
             if (c->last_use < t->last_use) t = c;
         hipError_t e = hipSuccess;
         if (t->w_stream != s && t->written_valid) e = hipStreamWaitEvent(s, t->written, 0);
-        for (const auto &r : t->readers)
-            if (e == hipSuccess && r.first != s) e = hipStreamWaitEvent(s, r.second, 0);
+        if (e == hipSuccess) e = t->readers.wait_elsewhere(s);
         if (e != hipSuccess) {
             *rc = fail(ctx, FLM_EHIP, "seed table: hipStreamWaitEvent failed: %s", hipGetErrorString(e));
             return nullptr;
@@ -858,43 +557,21 @@ void table_cover(SeedTable *t, hipStream_t s) {
 hipError_t table_before_read(SeedTable *t, hipStream_t s) {
     if (t->w_stream == s) return hipSuccess;
     if (t->written_valid) return event_done(t->written) ? hipSuccess : hipStreamWaitEvent(s, t->written, 0);
-    for (const auto &r : t->readers)  // (not reached: a write recorded no event only when a read followed)
-        if (r.first == t->w_stream) return hipStreamWaitEvent(s, r.second, 0);
-    return hipSuccess;
+    // (not reached: a write recorded no event only when a read followed)
+    const hipEvent_t read = t->readers.event_of(t->w_stream);
+    return read ? hipStreamWaitEvent(s, read, 0) : hipSuccess;
 }
 
-// A launch that reads t has been enqueued on s: record it as the table's last read on s (one event
-// per stream, reused; entries of finished streams are pruned as in Plan::done).
-hipError_t table_read(SeedTable *t, hipStream_t s) {
-    hipEvent_t *ev = nullptr;
-    for (auto &r : t->readers)
-        if (r.first == s) ev = &r.second;
-    if (!ev) {
-        if (t->readers.size() >= 8) {
-            std::vector<std::pair<hipStream_t, hipEvent_t>> keep;
-            for (auto &r : t->readers) {
-                if (event_done(r.second)) (void)hipEventDestroy(r.second);
-                else keep.push_back(r);
-            }
-            t->readers.swap(keep);
-        }
-        hipEvent_t e = nullptr;
-        const hipError_t c = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        if (c != hipSuccess) return c;
-        t->readers.emplace_back(s, e);
-        ev = &t->readers.back().second;
-    }
-    return hipEventRecord(*ev, s);
-}
+// A launch that reads t has been enqueued on s: record it as the table's last read on s.
+hipError_t table_read(SeedTable *t, hipStream_t s) { return t->readers.record(s); }
 
 void table_free(SeedTable *t) {
     if (t->written && t->written_valid) (void)hipEventSynchronize(t->written);
-    for (auto &r : t->readers) (void)hipEventSynchronize(r.second);
+    (void)t->readers.sync_all();
     t->recs.release();
     t->meta.release();
     if (t->written) (void)hipEventDestroy(t->written);
-    for (auto &r : t->readers) (void)hipEventDestroy(r.second);
-    delete t;
+    delete t;  // and with it the readers' events (StreamMarks)
 }
 
 // The one-launch small round builds no seed table: it reads the raw seeds and only WRITES its sign
@@ -943,46 +620,22 @@ int run_seed_schedule(flm_ctx *ctx, const uint8_t *d_seeds, const int8_t *d_sign
 int run_plan(flm_ctx *ctx, Plan &plan, SeedTable *table, const uint32_t *d_rows, uint64_t pitch, uint32_t *d_out,
              size_t out_elems, hipStream_t s, bool zeroed = false) {
     if (!plan.ready_known) {  // the items' copy was enqueued on another stream: order after it
-        const hipError_t q = hipEventQuery(plan.ready);
-        if (q == hipSuccess) plan.ready_known = true;
-        else if (q != hipErrorNotReady) FLM_HIP(ctx, q);
+        if (event_done(plan.ready)) plan.ready_known = true;
         else if (s != plan.up_stream) FLM_HIP(ctx, hipStreamWaitEvent(s, plan.ready, 0));
     }
-    if (plan.needs_zero && !zeroed) FLM_HIP(ctx, hipMemsetAsync(d_out, 0, out_elems * sizeof(uint32_t), s));
-    const int variant_id = pick_variant(ctx, plan);
+    if (plan.shape.needs_zero && !zeroed) FLM_HIP(ctx, hipMemsetAsync(d_out, 0, out_elems * sizeof(uint32_t), s));
+    const int variant_id = flm::plan::pick_variant(ctx->tune_variant, plan.shape);
     FLM_HIP(ctx, table_before_read(table, s));
-    FLM_HIP(ctx, flm::launch_items(plan.subtiles, variant_id, plan.items.as<Item>(), plan.n_items, d_rows, pitch,
+    FLM_HIP(ctx, flm::launch_items(plan.shape.subtiles, variant_id, plan.items.as<Item>(), plan.n_items, d_rows, pitch,
                                    table->recs.as<SeedRec>(), table->meta.as<uint32_t>(), d_out, s));
     FLM_HIP(ctx, table_read(table, s));
     // one event per stream the plan ran on, after its last launch there: the cache recycles the
     // items only once all of them have completed (no dependency is added between the streams)
-    hipEvent_t *ev = nullptr;
-    for (auto &d : plan.done)
-        if (d.first == s) ev = &d.second;
-    if (!ev) {
-        if (plan.done.size() >= 8) {  // many streams over time: drop the entries already completed
-            std::vector<std::pair<hipStream_t, hipEvent_t>> keep;
-            for (auto &d : plan.done) {
-                if (hipEventQuery(d.second) == hipSuccess) (void)hipEventDestroy(d.second);
-                else keep.push_back(d);
-            }
-            (void)hipGetLastError();  // hipErrorNotReady from the queries
-            plan.done.swap(keep);
-        }
-        hipEvent_t e = nullptr;
-        FLM_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        plan.done.emplace_back(s, e);
-        ev = &plan.done.back().second;
-    }
-    FLM_HIP(ctx, hipEventRecord(*ev, s));
-    ctx->last_items = plan.n_items;
-    ctx->last_tile = flm::kWaveSlots * plan.subtiles;
-    ctx->last_atomics = plan.atomics;
-    ctx->last_variant = variant_id;
+    FLM_HIP(ctx, plan.done.record(s));
+    set_last_plan(ctx, plan.n_items, flm::kWaveSlots * plan.shape.subtiles, plan.shape.atomics, variant_id);
     return 0;
 }
 
-// Upload N host rows (pageable or pinned) into the context's row buffer at `pitch`.
 bool host_pinned(const void *p) {
     hipPointerAttribute_t a;
     const hipError_t e = hipPointerGetAttributes(&a, p);
@@ -1001,6 +654,8 @@ bool host_pinned(const void *p) {
 // arrays (SA_ServiceAgent.py:210).  No pageable row is ever handed to a HIP copy
 // (HostCopies below says why).
 using flm::rt::kStageBytes;  // flm_host_layout.h
+using flm::rt::Piece;
+using flm::rt::pieces;
 
 // The two kStageBytes pinned staging buffers of the context (upload_rows, HostCopies' large copies).
 int ensure_stage(flm_ctx *ctx) {
@@ -1063,12 +718,12 @@ int upload_rows(flm_ctx *ctx, const uint32_t *const *rows, int N, size_t L, uint
     int b = 0;
     bool used[2] = {false, false};
     if (slot_bytes > kStageBytes) {  // very long rows: each in kStageBytes pieces through the same ring
+        const std::vector<Piece> ps = pieces(row_bytes, 1);
         for (int i : pageable)
-            for (size_t off = 0; off < row_bytes; off += kStageBytes) {
-                const size_t n = std::min(kStageBytes, row_bytes - off);
+            for (const Piece &p : ps) {
                 if (used[b]) FLM_HIP(ctx, hipEventSynchronize(ctx->stage_done[b]));
-                ctx->copies.copy2d(ctx->stage[b], n, reinterpret_cast<const uint8_t *>(rows[i]) + off, n, n, 1);
-                FLM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t *>(dst + (size_t)i * pitch) + off, ctx->stage[b], n,
+                ctx->copies.copy2d(ctx->stage[b], p.w, reinterpret_cast<const uint8_t *>(rows[i]) + p.c, p.w, p.w, 1);
+                FLM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t *>(dst + (size_t)i * pitch) + p.c, ctx->stage[b], p.w,
                                             hipMemcpyHostToDevice, ctx->stream));
                 FLM_HIP(ctx, hipEventRecord(ctx->stage_done[b], ctx->stream));
                 used[b] = true;
@@ -1220,21 +875,6 @@ class HostCopies {
         return l.rows == 1 ? hipMemcpyAsync(dst, src, l.width, k, s_)
                            : hipMemcpy2DAsync(dst, d_pitch, src, s_pitch, l.width, l.rows, k, s_);
     }
-    // Pieces of at most kStageBytes of a rows x width copy: whole rows, or one row's columns.
-    struct Piece {
-        size_t r, c, w, nr;  // first row, first column, bytes per row, rows
-    };
-    static std::vector<Piece> pieces(size_t width, size_t rows) {
-        std::vector<Piece> v;
-        if (width > kStageBytes) {
-            for (size_t r = 0; r < rows; ++r)
-                for (size_t c = 0; c < width; c += kStageBytes) v.push_back({r, c, std::min(kStageBytes, width - c), 1});
-        } else {
-            const size_t per = kStageBytes / width;
-            for (size_t r = 0; r < rows; r += per) v.push_back({r, 0, width, std::min(per, rows - r)});
-        }
-        return v;
-    }
     // a large input: each piece copied into the next free staging buffer, then DMA'd from it
     int stream_in(const Decl &sp, const flm::rt::HostSpan &l) {
         if (int rc = ensure_stage(ctx_)) return rc;
@@ -1289,62 +929,15 @@ void declare_seeds(flm_ctx *ctx, HostCopies &hc, const uint8_t *seeds, const int
     hc.in(signs, (size_t)K, ctx->signs);
 }
 
-// Client masking / expansion plan: one job per output row, 16 sub-tiles per
-// workgroup (each wave its own 1024 slots, all of the row's seeds).
-// out[i] = (x[i] or base_bias) + sum of row i's seeds (+1 per negative seed).
-// seg NULL: row i has seed i alone.  signs: K host signs, or NULL for all +1 (expansion).
+// Client masking / expansion (flm::plan::plan_rows_jobs plans it): stages the items and the signs,
+// builds the seed table and launches.  signs: K host signs, or NULL for all +1 (expansion).
 // The items and the signs travel in one staging slot (StageSlot): nothing here waits on the host.
 int run_rows_jobs(flm_ctx *ctx, const uint32_t *d_x, uint64_t pitch, int N, const int64_t *seg, const int8_t *signs,
                   const uint8_t *d_seeds, int K, uint32_t base_bias, size_t L, uint64_t slot0, uint32_t *d_out,
                   hipStream_t s) {
-    const int subtiles = 16;
     std::vector<Item> items;
-    bool needs_zero = false, single_tile = true;
-    int atomics = 0;
-    for (int i = 0; i < N; ++i) {
-        Job j;
-        j.out_base = (uint64_t)i * pitch;
-        j.L = L;
-        const uint32_t k0 = seg ? (uint32_t)seg[i] : (uint32_t)i;
-        const uint32_t k1 = seg ? (uint32_t)seg[i + 1] : (uint32_t)i + 1;
-        uint32_t nneg = 0;
-        if (signs)
-            for (uint32_t k = k0; k < k1; ++k) nneg += signs[k] < 0;
-        const uint32_t bias = (d_x ? 0u : base_bias) + nneg;
-        if (k1 == k0) {
-            // no seeds: out = x (copy) or the constant bias, as a rows-only item
-            const uint64_t W = (uint64_t)flm::kWaveSlots * subtiles;
-            for (uint64_t t = 0; t < L; t += W) {
-                Item it;
-                std::memset(&it, 0, sizeof it);
-                it.flags = flm::kHasRows;
-                it.row_in = j.out_base + t;
-                it.nrows = d_x ? 1 : 0;
-                it.row_out = j.out_base + t;
-                it.row_valid = (uint32_t)std::min<uint64_t>(W, L - t);
-                it.row_bias = bias;
-                items.push_back(it);
-            }
-            continue;
-        }
-        if (d_x) {
-            j.rows_base = (uint64_t)i * pitch;
-            j.nrows = 1;
-        }
-        j.k0 = k0;
-        j.nseeds = k1 - k0;
-        j.mask_lo = 0;
-        j.mask_hi = L;
-        j.prg_slot0 = slot0;
-        j.mask_bias = bias;
-        plan_job(j, pitch, subtiles, 1, 1, false, items, needs_zero, atomics, single_tile);
-    }
-    Plan plan;
-    plan.subtiles = subtiles;
-    plan.needs_zero = needs_zero;
-    plan.atomics = atomics;
-    plan.single_tile = single_tile;
-    plan.n_items = (int)items.size();
+    const PlanShape shape = flm::plan::plan_rows_jobs(d_x != nullptr, pitch, N, seg, signs, K, base_bias, L, slot0, items);
+    const int n_items = (int)items.size();
     const size_t item_bytes = items.size() * sizeof(Item);
     int rc = 0;
     StageSlot *slot = stage_acquire(ctx, item_bytes + std::max(K, 1), &rc);
@@ -1359,25 +952,22 @@ int run_rows_jobs(flm_ctx *ctx, const uint32_t *d_x, uint64_t pitch, int N, cons
     const uint8_t *d = slot->dev.as<uint8_t>();
     SeedTable *table = nullptr;
     rc = run_seed_schedule(ctx, d_seeds, reinterpret_cast<const int8_t *>(d + item_bytes), K, s, &table);
-    if (!rc && needs_zero) {
+    if (!rc && shape.needs_zero) {
         const hipError_t e = hipMemsetAsync(d_out, 0, (size_t)N * pitch * sizeof(uint32_t), s);
         if (e != hipSuccess) rc = fail(ctx, FLM_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
-    const int variant_id = pick_variant(ctx, plan);
-    if (!rc && plan.n_items) {
-        hipError_t e = flm::launch_items(subtiles, variant_id, reinterpret_cast<const Item *>(d), plan.n_items, d_x,
+    const int variant_id = flm::plan::pick_variant(ctx->tune_variant, shape);
+    if (!rc && n_items) {
+        hipError_t e = flm::launch_items(shape.subtiles, variant_id, reinterpret_cast<const Item *>(d), n_items, d_x,
                                          pitch, table->recs.as<SeedRec>(), table->meta.as<uint32_t>(), d_out, s);
         if (e == hipSuccess) e = table_read(table, s);
         if (e != hipSuccess) rc = fail(ctx, FLM_EHIP, "items launch: %s", hipGetErrorString(e));
     }
-    if (table && (rc || !plan.n_items)) table_cover(table, s);  // no read recorded after the table's write
+    if (table && (rc || !n_items)) table_cover(table, s);  // no read recorded after the table's write
     // the slot is busy until the work enqueued so far has run, whether or not it all got enqueued
     FLM_HIP(ctx, stage_commit(slot, s));
     if (rc) return rc;
-    ctx->last_items = plan.n_items;
-    ctx->last_tile = flm::kWaveSlots * subtiles;
-    ctx->last_atomics = atomics;
-    ctx->last_variant = variant_id;
+    set_last_plan(ctx, n_items, flm::kWaveSlots * shape.subtiles, shape.atomics, variant_id);
     return 0;
 }
 
@@ -1568,23 +1158,21 @@ int flm_aggregate_unmask_dev(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pi
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
     int rc = 0;
-    if (const int B = small_round_width(ctx, N, K, L, mask_lo, mask_hi)) {
+    if (const int B = flm::plan::small_round_width(ctx->tune_small, N, K, L, mask_lo, mask_hi)) {
         // one submission; the device seed table is not built, so flm_aggregate_dev must not reuse it
         if ((rc = run_small_round(ctx, B, d_rows, row_pitch, N, d_seeds, d_signs, K, L, mask_lo, mask_hi, prg_slot0,
                                   d_out, s)))
             return rc;
-        ctx->last_items = (int)((L + flm::small_round_slots(B) - 1) / flm::small_round_slots(B));
-        ctx->last_tile = flm::small_round_slots(B);
-        ctx->last_atomics = 0;
-        ctx->last_variant = kSmallRoundVariant;
+        const int slots = flm::small_round_slots(B);
+        set_last_plan(ctx, (int)((L + slots - 1) / slots), slots, 0, kSmallRoundVariant);
         return 0;
     }
     Plan *plan = aggregate_plan(ctx, row_pitch, N, K, L, mask_lo, mask_hi, prg_slot0, s, &rc);
     if (!plan) return rc;
     // two submissions: seed schedule (+ the zero-fill an atomics plan needs), then the items
     SeedTable *table = nullptr;
-    if ((rc = run_seed_schedule(ctx, d_seeds, d_signs, K, s, &table, plan->needs_zero ? d_out : nullptr, L))) return rc;
-    if ((rc = run_plan(ctx, *plan, table, d_rows, row_pitch, d_out, L, s, plan->needs_zero))) table_cover(table, s);
+    if ((rc = run_seed_schedule(ctx, d_seeds, d_signs, K, s, &table, plan->shape.needs_zero ? d_out : nullptr, L))) return rc;
+    if ((rc = run_plan(ctx, *plan, table, d_rows, row_pitch, d_out, L, s, plan->shape.needs_zero))) table_cover(table, s);
     return rc;
 }
 
@@ -1652,10 +1240,7 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
             reinterpret_cast<const int8_t *>(slot->dev.as<uint8_t>() + seg_bytes), L, d_x ? 0u : 1u, d_out, s);
         FLM_HIP(ctx, stage_commit(slot, s));
         FLM_HIP(ctx, e);
-        ctx->last_items = (int)(((L + 255) / 256) * (uint64_t)N);
-        ctx->last_tile = 256;
-        ctx->last_atomics = 0;
-        ctx->last_variant = kSmallRoundVariant;
+        set_last_plan(ctx, (int)(((L + 255) / 256) * (uint64_t)N), 256, 0, kSmallRoundVariant);
         return 0;
     }
     // signs go to the device with the work items (the schedule folds them into xorc)
@@ -1712,10 +1297,7 @@ int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, ui
     FLM_HIP(ctx, stage_commit(slot, s));
     if (rc) return rc;
     const uint64_t units = (uint64_t)K * ((L + 1023) / 1024);
-    ctx->last_items = (int)std::min<uint64_t>(units, (uint64_t)groups);
-    ctx->last_tile = flm::kWaveSlots;
-    ctx->last_atomics = 0;
-    ctx->last_variant = kExpandVariant;
+    set_last_plan(ctx, (int)std::min<uint64_t>(units, (uint64_t)groups), flm::kWaveSlots, 0, kExpandVariant);
     return 0;
 }
 
@@ -1772,8 +1354,8 @@ int flm_plan_aggregate(int subtiles, int pairing, size_t row_pitch, int N, int K
         return fail(nullptr, FLM_EINVAL, "flm_plan_aggregate: bad arguments");
     if (int rc = check_range(nullptr, prg_slot0, mask_hi)) return rc;
     std::vector<Item> items;
-    Plan plan;
-    build_aggregate_items(subtiles, pairing, row_pitch, N, K, L, mask_lo, mask_hi, prg_slot0, items, plan);
+    const PlanShape plan = flm::plan::build_aggregate_items(subtiles, pairing, row_pitch, N, K, L, mask_lo, mask_hi,
+                                                            prg_slot0, items);
     *n_items = (int)items.size();
     if (plan_flags)
         *plan_flags = (plan.needs_zero ? 1 : 0) | (plan.atomics ? 2 : 0) | (plan.single_tile ? 4 : 0) |
@@ -1796,63 +1378,20 @@ int flm_host_layout(int n, const uint64_t *width, const uint64_t *rows, const in
 
 int flm_set_tuning(flm_ctx *ctx, const char *key, int value) {
     if (!ctx || !key) return fail(ctx, FLM_EINVAL, "NULL argument");
-    const std::string k(key);
-    if (k == "variant") {
-        if (value < -1 || value >= flm::kVarCount) return fail(ctx, FLM_EINVAL, "variant %d out of range", value);
-        ctx->tune_variant = value;
-    } else if (k == "pairing") {
-        if (value < 0 || value > 2) return fail(ctx, FLM_EINVAL, "pairing must be 0, 1 or 2");
-        ctx->tune_pairing = value;
-    } else if (k == "subtiles") {
-        if (value != 0 && value != 1 && value != 4 && value != 16)
-            return fail(ctx, FLM_EINVAL, "subtiles must be 0 (auto), 1, 4 or 16");
-        ctx->tune_subtiles = value;
-    } else if (k == "ec_waves") {
-        if (value != 1 && value != 4 && value != 8) return fail(ctx, FLM_EINVAL, "ec_waves must be 1, 4 or 8");
-        ctx->tune_ec_waves = value;
-    } else if (k == "small") {
-        if (value < 0 || value > 2) return fail(ctx, FLM_EINVAL, "small must be 0 (never), 1 (auto) or 2 (when legal)");
-        ctx->tune_small = value;
-    } else if (k == "min_items") {
-        if (value < 64 || value > (1 << 20)) return fail(ctx, FLM_EINVAL, "min_items must be in [64, 2^20]");
-        ctx->tune_min_items = value;
-    } else if (k == "ec_spread") {
-        if (value < 0 || value > 64) return fail(ctx, FLM_EINVAL, "ec_spread must be in [0, 64] KiB");
-        ctx->tune_ec_spread = value;
-    } else if (k == "ec_terms") {
-        if (value != 1 && value != 2 && value != 4) return fail(ctx, FLM_EINVAL, "ec_terms must be 1, 2 or 4");
-        ctx->tune_ec_terms = value;
-    } else if (k == "ec_coop") {
-        if (value < -1 || value > 2) return fail(ctx, FLM_EINVAL, "ec_coop must be -1, 0, 1 or 2");
-        ctx->tune_ec_coop = value;
-    } else if (k == "expand_waves") {
-        if (value < 1 || value > 256) return fail(ctx, FLM_EINVAL, "expand_waves must be in [1, 256]");
-        ctx->tune_expand_waves = value;
-    } else if (k == "ec_threads") {
-        if (value != 64 && value != 128 && value != 256)
-            return fail(ctx, FLM_EINVAL, "ec_threads must be 64, 128 or 256");
-        ctx->tune_ec_threads = value;
-    } else {
-        return fail(ctx, FLM_EINVAL, "unknown tuning key '%s'", key);
-    }
+    const TuneKey *t = tune_key(key);
+    if (!t) return fail(ctx, FLM_EINVAL, "unknown tuning key '%s'", key);
+    if (!t->accepts(value)) return fail(ctx, FLM_EINVAL, t->refusal, value);
+    ctx->*t->member = value;
     return 0;
 }
 
 int flm_get_tuning(const flm_ctx *ctx, const char *key, int *value) {
     flm_ctx *c = const_cast<flm_ctx *>(ctx);  // only its error string is written
     if (!ctx || !key || !value) return fail(c, FLM_EINVAL, "NULL argument");
-    const std::string k(key);
-    const std::pair<const char *, int> knobs[] = {
-        {"variant", ctx->tune_variant},       {"pairing", ctx->tune_pairing},     {"subtiles", ctx->tune_subtiles},
-        {"ec_waves", ctx->tune_ec_waves},     {"small", ctx->tune_small},         {"min_items", ctx->tune_min_items},
-        {"ec_spread", ctx->tune_ec_spread},   {"ec_terms", ctx->tune_ec_terms},   {"ec_coop", ctx->tune_ec_coop},
-        {"ec_threads", ctx->tune_ec_threads}, {"expand_waves", ctx->tune_expand_waves}};
-    for (const auto &kv : knobs)
-        if (k == kv.first) {
-            *value = kv.second;
-            return 0;
-        }
-    return fail(c, FLM_EINVAL, "unknown tuning key '%s'", key);
+    const TuneKey *t = tune_key(key);
+    if (!t) return fail(c, FLM_EINVAL, "unknown tuning key '%s'", key);
+    *value = ctx->*t->member;
+    return 0;
 }
 
 int flm_check_signs(flm_ctx *ctx, int *bad_count) {
@@ -1863,9 +1402,7 @@ int flm_check_signs(flm_ctx *ctx, int *bad_count) {
     if (!meta || !meta->p) return 0;
     FLM_ON_DEVICE(ctx);
     if (t && t->written_valid) FLM_HIP(ctx, hipEventSynchronize(t->written));
-    if (t)
-        for (const auto &r : t->readers)
-            if (r.first == t->w_stream) FLM_HIP(ctx, hipEventSynchronize(r.second));
+    if (const hipEvent_t read = t ? t->readers.event_of(t->w_stream) : nullptr) FLM_HIP(ctx, hipEventSynchronize(read));
     uint32_t parts = 0;
     FLM_HIP(ctx, hipMemcpy(&parts, meta->p, sizeof parts, hipMemcpyDeviceToHost));
     if (2 + 2 * (size_t)parts > meta->cap / sizeof(uint32_t))

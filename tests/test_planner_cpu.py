@@ -6,9 +6,16 @@ negative-sign bias exactly once per masked slot, use atomics wherever a slot
 has more than one writer (and then zero-fill), and start every mask tile on a
 ChaCha block boundary."""
 import ctypes
+import hashlib
+import json
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 ITEM = np.dtype([("row_in", "<u8"), ("row_out", "<u8"), ("mask_out", "<u8"), ("mask_ctr", "<u8"),
                  ("nrows", "<u4"), ("k0", "<u4"), ("nseeds", "<u4"), ("row_valid", "<u4"),
@@ -31,7 +38,7 @@ def plan(N, K, L, lo=0, hi=None, pitch=None, prg_slot0=0, subtiles=0, pairing=1)
     return buf[: n.value], fl.value, pitch
 
 
-@pytest.mark.parametrize("N,K,L,lo,hi,pairing", [
+COVER_SHAPES = [
     (1024, 1024, 1 << 20, 0, None, 1),          # c4, one GPU
     (1024, 1024, 1 << 18, 0, None, 1),          # c3: 256 tiles split into 8 same-tile parts
     (1024, 1000, 1 << 18, 0, None, 1),          # c3 with dropouts (K != N)
@@ -51,7 +58,15 @@ def plan(N, K, L, lo=0, hi=None, pitch=None, prg_slot0=0, subtiles=0, pairing=1)
     (33, 40, 4100, 1024, 3072, 2),              # window inside, ragged
     (7, 3, 70000, 69984, 70000, 2),             # last block only (one part)
     (5, 64, 70000, 4096, 69984, 2),             # fewer rows than parts
-])
+]
+# the shapes test_plan_modes plans, in the same form (tools/record_planner_items.py pins them too)
+MODE_SHAPES = [
+    (1024, 1024, 1 << 20, 0, None, 1), (1024, 1024, 1 << 18, 0, None, 1), (1024, 204, 1 << 20, 0, None, 1),
+    (1024, 8192, 1 << 20, 0, 1 << 17, 1), (128, 1024, 1 << 20, 7 << 17, 8 << 17, 2),
+]
+
+
+@pytest.mark.parametrize("N,K,L,lo,hi,pairing", COVER_SHAPES)
 def test_plan_covers_everything_once(N, K, L, lo, hi, pairing):
     hi = L if hi is None else hi
     items, flags, pitch = plan(N, K, L, lo, hi, pairing=pairing)
@@ -127,6 +142,43 @@ def test_plan_modes():
     assert heavy[0] and heavy.index(False) <= 3              # rows-only items spread between the heavy ones
     gaps = np.diff(np.flatnonzero(~np.array(heavy)))
     assert gaps.max() <= 3
+
+
+def _golden():
+    with open(os.path.join(ROOT, "tests", "golden", "planner_items.json")) as f:
+        return json.load(f)
+
+
+def test_golden_pins_the_shapes_of_the_other_tests():
+    have = {(g["N"], g["K"], g["L"], g["lo"], g["hi"], g["pairing"]) for g in _golden()
+            if g["subtiles"] == 0 and g["prg_slot0"] == 0}
+    for N, K, L, lo, hi, pairing in COVER_SHAPES + MODE_SHAPES:
+        assert (N, K, L, lo, L if hi is None else hi, pairing) in have
+
+
+@pytest.mark.parametrize("g", _golden(), ids=lambda g: "-".join(
+    str(g[k]) for k in ("subtiles", "pairing", "N", "K", "L", "lo", "hi", "prg_slot0")))
+def test_plan_items_are_the_recorded_ones(g):
+    """The items of each pinned shape, byte for byte and in order (tools/record_planner_items.py recorded
+    them before the planner moved into flm_planner.h).  The order is part of the contract: it decides
+    which workgroups share a CU, which is what the measured pairings are about; the coverage test above
+    does not see it."""
+    items, flags, _ = plan(g["N"], g["K"], g["L"], g["lo"], g["hi"], prg_slot0=g["prg_slot0"],
+                           subtiles=g["subtiles"], pairing=g["pairing"])
+    assert (len(items), flags) == (g["n_items"], g["plan_flags"])
+    assert hashlib.sha256(items.tobytes()).hexdigest() == g["sha256"]
+
+
+def test_planner_checker(tmp_path):
+    """tools/planner_check.cpp (flm_planner.h, flm_host_layout.h's pieces, flm_copy_pool.h: no HIP, no
+    library), built without a sanitizer"""
+    cxx = next((c for c in ("c++", "g++", "clang++", "hipcc") if shutil.which(c)), None)
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "planner_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "flamingo_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "planner_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
 
 
 def test_plan_range_rule():

@@ -127,6 +127,41 @@ def test_aggregate_dev_new_plan_on_another_stream(eng):
     assert np.array_equal(out_b.cpu().numpy().view(np.uint32), want)
 
 
+@pytest.mark.parametrize("window", [None, (1024, 2048)])   # one item per tile; dual-tile items, atomics, zero-fill
+def test_one_plan_and_the_table_ring_on_ten_streams(eng, window):
+    """One cached plan and the ring of 8 seed tables under ten streams, twice over: more streams than
+    the per-stream event set keeps before it prunes (8) and than there are tables, so the plan's
+    events are pruned and a stream has to wait for the least recently used table.  Every round's
+    output is the oracle's, bit for bit.  Nothing long is queued: the rounds take milliseconds."""
+    import torch
+    dev = torch.device("cuda", 0)
+    N, K, L = 3, 5, 2500                                   # three 1024-slot tiles, ragged tail
+    lo, hi = window or (0, L)
+    g = np.random.Generator(np.random.PCG64(31))
+    rows = g.integers(0, 2**32, (N, L), dtype=np.uint32)
+    seeds = g.integers(0, 256, (K, 32), dtype=np.uint8)
+    signs = np.array([1, -1, -1, 1, -1], np.int8)
+    want = O.aggregate_unmask(rows, np.zeros((0, 32), np.uint8), np.zeros(0, np.int8))
+    want[lo:hi] = O.aggregate_unmask(rows, seeds, signs)[lo:hi]
+    d_rows = torch.from_numpy(rows.view(np.int32)).to(dev)
+    d_seeds, d_signs = torch.from_numpy(seeds).to(dev), torch.from_numpy(signs).to(dev)
+    streams = [torch.cuda.Stream() for _ in range(10)]
+    outs = [torch.full((L,), 77, dtype=torch.int32, device=dev) for _ in range(2 * len(streams))]
+    torch.cuda.synchronize()
+    small = eng.get_tuning("small")
+    eng.set_tuning("small", 0)                             # the seed-table + items path, not the one-launch round
+    try:
+        for i, out in enumerate(outs):
+            eng.aggregate_unmask_dev(d_rows, d_seeds, d_signs, out, L=L, mask_lo=lo, mask_hi=hi,
+                                     stream=streams[i % len(streams)])
+        assert eng.last_plan()["variant"] < 100 and eng.last_plan()["atomics"] == (1 if window else 0)
+    finally:
+        eng.set_tuning("small", small)
+    torch.cuda.synchronize()
+    for out in outs:
+        assert np.array_equal(out.cpu().numpy().view(np.uint32), want)
+
+
 def test_reduce_scatter_null_stream_orders_with_torch_default_stream(eng):
     """stream=None on the collectives is torch's current stream (default: the null stream), as
     for every other *_dev call: the collective runs after the kernel that wrote the partial and
