@@ -230,7 +230,7 @@ def _sqrt(v: int):
 def map_to_curve(u: int):
     z_minus_10 = -10
     tv1_den = (100 * pow(u, 4, P) + z_minus_10 * pow(u, 2, P)) % P
-    tv1 = pow(tv1_den, -1, P) if tv1_den else 0
+    tv1 = pow(tv1_den, -1, P) if tv1_den else 0     # RFC 9380's inv0; the reference's invmod raises at 0
     x1 = ((-B * pow(A, -1, P)) * (1 + tv1)) % P
     if tv1 == 0:
         x1 = (B * pow(30, -1, P)) % P

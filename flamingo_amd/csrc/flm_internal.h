@@ -82,6 +82,10 @@ hipError_t launch_ec_finish(const uint8_t *d_base, const uint32_t *d_jac, int T,
 // v0 .. v0+n-1 (d_msgs NULL); d_out n x 64 wire bytes, d_flags n words (written)
 hipError_t launch_hash_to_curve(const uint8_t *d_msgs, const uint32_t *d_lens, uint32_t v0, int n, uint8_t *d_out,
                                 uint32_t *d_flags, hipStream_t stream);
+// the same kernel's tail (mod n, map_to_curve, Q_0 + Q_1) on d_uniform: n x 96 bytes in the place of
+// expand_message_xmd's output (h2c_from_uniform_kernel)
+hipError_t launch_h2c_from_uniform(const uint8_t *d_uniform, int n, uint8_t *d_out, uint32_t *d_flags,
+                                   hipStream_t stream);
 
 }  // namespace flm
 
@@ -140,3 +144,7 @@ void comm_release_clique(flm_ctx *const *ctxs, int n);
 // route, pitch and offset get n entries each, *total the bounce bytes.
 extern "C" int flm_host_layout(int n, const uint64_t *width, const uint64_t *rows, const int *may_in_place,
                                int *route, uint64_t *pitch, uint64_t *offset, uint64_t *total);
+// Hash to curve from the uniform bytes on, for the GPU tests: uniform is n x 96 bytes (big endian, what
+// expand_message_xmd(msg, DST, 96) gives), out n x 64 wire bytes, flags_out n words or NULL; host
+// pointers, with flm_hash_to_curve's conventions (infinity is a result: flags bit 2 and zero bytes).
+extern "C" int flm_h2c_from_uniform(flm_ctx *ctx, const uint8_t *uniform, int n, uint8_t *out, uint32_t *flags_out);

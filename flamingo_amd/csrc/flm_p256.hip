@@ -905,8 +905,11 @@ __global__ __launch_bounds__(kAesThreads) void aes_gcm_xor_kernel(const uint8_t 
 //   Q_k     = map_to_curve(u_k)                                                   (:233-275)
 //   H       = Q_0 + Q_1                                                           (:282)
 // One lane per message, Montgomery field of the scalar-multiplication kernels.  map_to_curve is the
-// reference's own simplified-SWU variant with Z = -10: tv1 = (100 u^4 - 10 u^2)^-1 (0 -> 0, the x1 =
-// b/30 branch), x1 = -b/a (1 + tv1), x2 = -10 u^2 x1, y = the first square root of g(x1) else of g(x2).
+// reference's own simplified-SWU variant with Z = -10: tv1 = (100 u^4 - 10 u^2)^-1, x1 = -b/a (1 + tv1),
+// x2 = -10 u^2 x1, y = the first square root of g(x1) else of g(x2).  Where the denominator is 0 (u = 0
+// and u = +-sqrt(1/10), which no message reaches) the reference's libnum.invmod raises and its x1 =
+// b/30 branch (:247-248) is dead; here the inverse is RFC 9380's inv0 (0 -> 0) and that branch is
+// taken -- this project's choice.
 // Square roots are a^((p+1)/4) (p = 3 mod 4): the root the host restatement (flamingo_amd/crypto.py)
 // takes first for libnum's sqrtmod -- the one convention that stays "parity unpinned" (DESIGN.md).
 // The sgn0 step (:271-272) flips y only when exactly one of u, y is zero.  The whole table of the
@@ -936,8 +939,11 @@ __device__ void sha_put_dst(Sha256 &s) {
     for (int i = 0; i < 45; ++i) sha_put(s, kDstPrime[i]);
 }
 
-// 384-bit big-endian words u[0..11] mod n: fold t = lo + hi (2^256 mod n) until t < 2^256 (at most
-// 7 folds for any 384-bit input: the high part shrinks by >= 31 bits a fold), then one subtraction
+// 384-bit big-endian words u[0..11] mod n: fold t = lo + hi (2^256 mod n) until t < 2^256, then one
+// subtraction.  2^256 mod n < 2^224, so hi goes from 128 bits to at most 96, 64, 32, 1 and 0: five
+// folds can meet a non-zero hi (random inputs need four or five, about half each) and the last two of
+// the seven iterations always see hi = 0 and add nothing.  tools/h2c_reduce_model.py replays these
+// limbs and carries in Python and proves the bound (fold_bound); the loop count is left as it was.
 __device__ Fe mod_n_384(const uint32_t *u) {
     uint32_t t[12];
 #pragma unroll
@@ -974,7 +980,7 @@ __device__ Fe mod_n_384(const uint32_t *u) {
 }
 
 // Montgomery-form inverse by binary GCD (ec_finish_kernel's: ~25k VALU instructions against Fermat's
-// ~73k): (a R)^-1 R^3 R^-1 = a^-1 R; 0 -> 0, as the reference's tv1 branch needs
+// ~73k): (a R)^-1 R^3 R^-1 = a^-1 R; 0 -> 0 (RFC 9380's inv0: h2c_map's x1 = b/30 branch)
 __device__ __forceinline__ Fe fe_inv_mont(const Fe &a) {
     if (fe_is_zero(a)) return a;
     return fe_mul(fe_inv_bingcd(a), fe_const(kR3));
@@ -1005,7 +1011,7 @@ __device__ void h2c_map(const Fe &u_plain, Fe &x, Fe &y, bool &bad) {
     const Fe u2 = fe_sqr(u);
     const Fe u4 = fe_sqr(u2);
     const Fe den = fe_sub(fe_mul(fe_const(k100m), u4), fe_mul(fe_const(k10m), u2));
-    const Fe tv1 = fe_inv_mont(den);                              // 0 -> 0 (the :247-248 branch)
+    const Fe tv1 = fe_inv_mont(den);                              // inv0: 0 -> 0, then x1 = b/30
     Fe x1 = fe_mul(fe_const(kC1m), fe_add(fe_const(kOne), tv1));
     if (fe_is_zero(tv1)) x1 = fe_const(kC2m);
     const Fe gx1 = fe_add(fe_mul(x1, fe_add(fe_sqr(x1), fe_const(kAm))), fe_const(kBm));
@@ -1018,6 +1024,50 @@ __device__ void h2c_map(const Fe &u_plain, Fe &x, Fe &y, bool &bad) {
     x = sq1 ? x1 : x2;
     y = sq1 ? y1 : y2;
     if (fe_is_zero(u_plain) != fe_is_zero(y)) y = fe_neg(y);    // sgn0(u) != sgn0(y), :271-272
+}
+
+// Everything after expand_message_xmd, for both kernels below: uni is the lane's 24 big-endian words
+// of uniform bytes (of message i; lane `half` of its pair takes words 12 half .. 12 half + 11).  Lane
+// 2m maps u_0 and lane 2m+1 maps u_1, then the odd lane hands its point to the even one (a lane
+// swap, no LDS), which adds, inverts and stores out row i and flags[i].  Lanes with !valid (i >= n)
+// compute on whatever uni holds and store nothing: both lanes of a pair stay to the swap.
+// Inlined into each kernel: as a shared out-of-line function it took hash_to_curve_kernel from 152 to
+// 200 VGPRs (3 -> 2 waves per SIMD); inlined, that kernel's code is what it was with the tail written
+// in place.
+__device__ __forceinline__ void h2c_tail(const uint32_t *uni, bool valid, int half, int i, uint8_t *__restrict__ out,
+                                         uint32_t *__restrict__ flags) {
+    Fe x, y;
+    bool bad;
+    h2c_map(mod_n_384(half ? uni + 12 : uni), x, y, bad);   // Q_half = map_to_curve(u_half)
+    Fe x1, y1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        x1.v[k] = (uint32_t)__shfl_xor((int)x.v[k], 1);
+        y1.v[k] = (uint32_t)__shfl_xor((int)y.v[k], 1);
+    }
+    const bool bad1 = __shfl_xor((int)bad, 1) != 0;
+    if (!valid || half) return;
+    Jac Q0, Q1;
+    Q0.X = x;
+    Q0.Y = y;
+    Q0.Z = fe_const(kOne);
+    Q1.X = x1;
+    Q1.Y = y1;
+    Q1.Z = fe_const(kOne);
+    const Jac R = jac_add(Q0, Q1);                                 // Q0 + Q1 (:282), P == +-Q handled
+    uint32_t fl = (bad || bad1) ? 8u : 0u;
+    Fe ax = {}, ay = {};
+    if (fe_is_zero(R.Z)) {
+        fl |= 4u;
+    } else {
+        const Fe zi = fe_inv_mont(R.Z);
+        const Fe zi2 = fe_sqr(zi);
+        ax = from_mont(fe_mul(R.X, zi2));
+        ay = from_mont(fe_mul(R.Y, fe_mul(zi2, zi)));
+    }
+    store_be(out + (size_t)i * 64, ax);
+    store_be(out + (size_t)i * 64 + 32, ay);
+    flags[i] = fl;
 }
 
 // msgs: n x kH2cMaxMsg bytes (message i in its first lens[i] bytes), or NULL for the decimal
@@ -1080,38 +1130,30 @@ __global__ __launch_bounds__(kEcThreads) void hash_to_curve_kernel(const uint8_t
 #pragma unroll
         for (int k = 0; k < 8; ++k) uni[(blk - 1) * 8 + k] = bi[k];
     }
-    Fe x, y;
-    bool bad;
-    h2c_map(mod_n_384(half ? uni + 12 : uni), x, y, bad);   // Q_half = map_to_curve(u_half)
-    Fe x1, y1;
+    h2c_tail(uni, valid, half, i, out, flags);
+}
+
+// The same tail on uniform bytes the caller chose (flm_h2c_from_uniform, for the tests: no message
+// reaches u = 0, the roots of 1/10, Q0 = +-Q1 or a late fold of mod_n_384).  uniform: n x 96 bytes,
+// what expand_message_xmd(msg, DST, 96) would give; out and flags as above.  Lanes with i >= n read
+// nothing and stay for the swap.
+__global__ __launch_bounds__(kEcThreads) void h2c_from_uniform_kernel(const uint8_t *__restrict__ uniform, int n,
+                                                                      uint8_t *__restrict__ out,
+                                                                      uint32_t *__restrict__ flags) {
+    const int t = blockIdx.x * kEcThreads + threadIdx.x;
+    const int i = t >> 1, half = t & 1;
+    const bool valid = i < n;
+    uint32_t uni[24];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        x1.v[k] = (uint32_t)__shfl_xor((int)x.v[k], 1);
-        y1.v[k] = (uint32_t)__shfl_xor((int)y.v[k], 1);
+    for (int k = 0; k < 24; ++k) uni[k] = 0;
+    if (valid) {
+        const uint8_t *row = uniform + (size_t)i * 96;
+#pragma unroll 1
+        for (int k = 0; k < 24; ++k)
+            uni[k] = (uint32_t)row[4 * k] << 24 | (uint32_t)row[4 * k + 1] << 16 | (uint32_t)row[4 * k + 2] << 8 |
+                     (uint32_t)row[4 * k + 3];
     }
-    const bool bad1 = __shfl_xor((int)bad, 1) != 0;
-    if (!valid || half) return;
-    Jac Q0, Q1;
-    Q0.X = x;
-    Q0.Y = y;
-    Q0.Z = fe_const(kOne);
-    Q1.X = x1;
-    Q1.Y = y1;
-    Q1.Z = fe_const(kOne);
-    const Jac R = jac_add(Q0, Q1);                                 // Q0 + Q1 (:282), P == +-Q handled
-    uint32_t fl = (bad || bad1) ? 8u : 0u;
-    Fe ax = {}, ay = {};
-    if (fe_is_zero(R.Z)) {
-        fl |= 4u;
-    } else {
-        const Fe zi = fe_inv_mont(R.Z);
-        const Fe zi2 = fe_sqr(zi);
-        ax = from_mont(fe_mul(R.X, zi2));
-        ay = from_mont(fe_mul(R.Y, fe_mul(zi2, zi)));
-    }
-    store_be(out + (size_t)i * 64, ax);
-    store_be(out + (size_t)i * 64 + 32, ay);
-    flags[i] = fl;
+    h2c_tail(uni, valid, half, i, out, flags);
 }
 
 }  // namespace
@@ -1221,6 +1263,15 @@ hipError_t launch_hash_to_curve(const uint8_t *d_msgs, const uint32_t *d_lens, u
     const size_t lanes = 2 * (size_t)n;  // two lanes per message
     hipLaunchKernelGGL(hash_to_curve_kernel, dim3((unsigned)((lanes + kEcThreads - 1) / kEcThreads)), dim3(kEcThreads),
                        0, stream, d_msgs, d_lens, v0, n, d_out, d_flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_h2c_from_uniform(const uint8_t *d_uniform, int n, uint8_t *d_out, uint32_t *d_flags,
+                                   hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const size_t lanes = 2 * (size_t)n;
+    hipLaunchKernelGGL(h2c_from_uniform_kernel, dim3((unsigned)((lanes + kEcThreads - 1) / kEcThreads)),
+                       dim3(kEcThreads), 0, stream, d_uniform, n, d_out, d_flags);
     return hipGetLastError();
 }
 

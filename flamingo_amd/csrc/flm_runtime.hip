@@ -1701,22 +1701,29 @@ int flm_ec_mul(flm_ctx *ctx, const uint8_t *points, const uint8_t *scalars, int 
     return 0;
 }
 
-static int h2c_run(flm_ctx *ctx, const uint8_t *msgs, const uint32_t *lens, uint32_t v0, int n, uint8_t *out,
-                   uint32_t *flags_out) {
+// one body for the three host forms: uniform (n x 96 bytes, flm_h2c_from_uniform), else msgs + lens, else decimals
+static int h2c_run(flm_ctx *ctx, const uint8_t *uniform, const uint8_t *msgs, const uint32_t *lens, uint32_t v0, int n,
+                   uint8_t *out, uint32_t *flags_out) {
     FLM_ON_DEVICE(ctx);
     hipStream_t s = ctx->stream;
     std::vector<uint32_t> fl(n);
     HostCopies hc(ctx, s);
-    if (msgs) {
+    if (uniform) {
+        hc.in(uniform, (size_t)n * 96, ctx->ec_in);
+    } else if (msgs) {
         hc.in(msgs, (size_t)n * 64, ctx->ec_in);
         hc.in(lens, (size_t)n * 4, ctx->ec_scal);
     }
     hc.out(fl.data(), (size_t)n * 4, ctx->ec_flags);
     hc.out(out, (size_t)n * 64, ctx->ec_out);
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_hash_to_curve(msgs ? ctx->ec_in.as<uint8_t>() : nullptr,
-                                           msgs ? ctx->ec_scal.as<uint32_t>() : nullptr, v0, n,
-                                           ctx->ec_out.as<uint8_t>(), ctx->ec_flags.as<uint32_t>(), s));
+    if (uniform)
+        FLM_HIP(ctx, flm::launch_h2c_from_uniform(ctx->ec_in.as<uint8_t>(), n, ctx->ec_out.as<uint8_t>(),
+                                                  ctx->ec_flags.as<uint32_t>(), s));
+    else
+        FLM_HIP(ctx, flm::launch_hash_to_curve(msgs ? ctx->ec_in.as<uint8_t>() : nullptr,
+                                               msgs ? ctx->ec_scal.as<uint32_t>() : nullptr, v0, n,
+                                               ctx->ec_out.as<uint8_t>(), ctx->ec_flags.as<uint32_t>(), s));
     if (int rc = hc.finish()) return rc;
     if (flags_out) std::copy(fl.begin(), fl.end(), flags_out);
     for (int i = 0; i < n; ++i)
@@ -1732,7 +1739,7 @@ int flm_hash_to_curve(flm_ctx *ctx, const uint8_t *msgs, const uint32_t *lens, i
     if (!msgs || !lens || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
     for (int i = 0; i < n; ++i)
         if (lens[i] > 64) return fail(ctx, FLM_EINVAL, "message %d is %u bytes (at most 64)", i, lens[i]);
-    return h2c_run(ctx, msgs, lens, 0, n, out, flags_out);
+    return h2c_run(ctx, nullptr, msgs, lens, 0, n, out, flags_out);
 }
 
 int flm_hash_to_curve_decimal(flm_ctx *ctx, uint32_t v0, int n, uint8_t *out, uint32_t *flags_out) {
@@ -1741,7 +1748,7 @@ int flm_hash_to_curve_decimal(flm_ctx *ctx, uint32_t v0, int n, uint8_t *out, ui
     if (n == 0) return 0;
     if (!out) return fail(ctx, FLM_EINVAL, "NULL argument");
     if ((uint64_t)v0 + (uint64_t)n > (1ull << 32)) return fail(ctx, FLM_EINVAL, "v0 + n exceeds 2^32");
-    return h2c_run(ctx, nullptr, nullptr, v0, n, out, flags_out);
+    return h2c_run(ctx, nullptr, nullptr, nullptr, v0, n, out, flags_out);
 }
 
 int flm_hash_to_curve_decimal_dev(flm_ctx *ctx, uint32_t v0, int n, uint8_t *d_out, uint32_t *d_flags, void *stream) {
@@ -1753,6 +1760,14 @@ int flm_hash_to_curve_decimal_dev(flm_ctx *ctx, uint32_t v0, int n, uint8_t *d_o
     FLM_ON_DEVICE(ctx);
     FLM_HIP(ctx, flm::launch_hash_to_curve(nullptr, nullptr, v0, n, d_out, d_flags, static_cast<hipStream_t>(stream)));
     return 0;
+}
+
+int flm_h2c_from_uniform(flm_ctx *ctx, const uint8_t *uniform, int n, uint8_t *out, uint32_t *flags_out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = ec_dims(ctx, 1, n)) return rc;
+    if (n == 0) return 0;
+    if (!uniform || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    return h2c_run(ctx, uniform, nullptr, nullptr, 0, n, out, flags_out);
 }
 
 void *flm_host_alloc(size_t bytes) {

@@ -126,9 +126,14 @@ def expand_message_xmd(msg: bytes, dst: bytes, len_in_bytes: int) -> bytes:
 
 
 def map_to_curve(u: int):
-    """ecchash.py:233-275 (Z = -10); a^((p+1)/4) as the first root of libnum.sqrtmod."""
+    """ecchash.py:233-275 (Z = -10); a^((p+1)/4) as the first root of libnum.sqrtmod.
+
+    Where den = 0 (u = 0 and u = +-sqrt(1/10) mod p) the reference's libnum.invmod raises, so its
+    x1 = b/30 branch (:247-248) is dead code and it has no answer; this oracle and the kernel take
+    RFC 9380's inv0 (0 -> 0) there and with it that branch.  A choice of this project,
+    recorded in tests/golden/h2c_map_golden.json; no hash output reaches those u."""
     den = (100 * pow(u, 4, P) - 10 * pow(u, 2, P)) % P
-    tv1 = pow(den, P - 2, P)                       # libnum.invmod; 0 -> 0 takes the :247-248 branch
+    tv1 = pow(den, P - 2, P)                       # inv0: 0 -> 0 (libnum.invmod for every other den)
     x1 = ((-B * pow(A, -1, P)) * (1 + tv1)) % P
     if tv1 == 0:
         x1 = B * pow(30, -1, P) % P
@@ -144,12 +149,18 @@ def map_to_curve(u: int):
     return (x, y)
 
 
+def h2c_from_uniform(ub: bytes) -> tuple | None:
+    """hash_str_to_curve from its 96 uniform bytes on: hash_to_field's u_k = OS2IP(ub[48k : 48k + 48])
+    mod n (:50-61, modulus = n) and Q_0 + Q_1 (:279-282).  Checker for flm_h2c_from_uniform."""
+    assert len(ub) == 96
+    u0, u1 = (int.from_bytes(ub[48 * i: 48 * i + 48], "big") % N for i in range(2))
+    return add(map_to_curve(u0), map_to_curve(u1))
+
+
 def hash_str_to_curve(msg) -> tuple | None:
     """ecchash.hash_str_to_curve(msg, 2, n, 1, 48, XMDExpander(DST, sha256, 128))."""
     m = msg.encode() if isinstance(msg, str) else bytes(msg)
-    ub = expand_message_xmd(m, DST, 96)
-    u0, u1 = (int.from_bytes(ub[48 * i: 48 * i + 48], "big") % N for i in range(2))
-    return add(map_to_curve(u0), map_to_curve(u1))
+    return h2c_from_uniform(expand_message_xmd(m, DST, 96))
 
 
 def h2c_table_digest(points) -> str:
