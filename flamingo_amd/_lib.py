@@ -58,6 +58,10 @@ SIGNATURES = {
     "flm_shamir_deal_dev": (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _vp]),
     "flm_aes_gcm_xor": (_int, [_vp, _u8p, _u8p, _int, _u8p, _u8p, _sz, _int]),
     "flm_aes_gcm_xor_dev": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _sz, _int, _vp]),
+    "flm_aes_gcm_seal": (_int, [_vp, _u8p, _u8p, _int, _u8p, _sz, _u8p, _u8p, _sz, _u8p, _int]),
+    "flm_aes_gcm_seal_dev": (_int, [_vp, _vp, _vp, _int, _vp, _sz, _vp, _vp, _sz, _vp, _int, _vp]),
+    "flm_aes_gcm_open": (_int, [_vp, _u8p, _u8p, _int, _u8p, _sz, _u8p, _u8p, _u8p, _sz, _u8p, _int]),
+    "flm_aes_gcm_open_dev": (_int, [_vp, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _int, _vp]),
     "flm_ecdsa_verify": (_int, [_vp, _u8p, _u8p, _u8p, _int, _u8p, _u32p]),
     "flm_ecdsa_verify_dev": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "flm_pair_units_dev": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _sz, _vp, _int, _int, _vp]),

@@ -65,6 +65,9 @@ def parse(argv):
     # ... in one GPU call per member (protocol.configure(gpu_verify=True)), not row by row on the host
     # (OpenSSL), which is the default: same verdicts, no faster at a member's 61 rows
     ap.add_argument("--gpu_verify", action="store_true")
+    # the sealed m_i shares keep their AES-GCM tag and the committee verifies it before it opens them
+    # (protocol.configure(authenticate_shares=True)); off by default
+    ap.add_argument("--authenticate_shares", action="store_true")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -114,7 +117,8 @@ def _run(args):
     param.configure(root=root, L=args.vector_len, committee=args.committee_size,
                     gpu_deal=False if args.host_deal else None,
                     check_signatures=True if args.check_signatures else None,
-                    gpu_verify=True if args.gpu_verify else None)
+                    gpu_verify=True if args.gpu_verify else None,
+                    authenticate_shares=True if args.authenticate_shares else None)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
     offline_its = offline_schedule(n, args.num_iterations, offline, args.dropout)
     print(f"Silent mode: {log.silent_mode}")

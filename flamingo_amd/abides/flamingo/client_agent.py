@@ -20,7 +20,11 @@ Committee members sign the offline set (ECDSA, :351-368) and answer DEC with
 sk_j * c0 for each dropout ciphertext plus their decrypted m_i shares
 (:370-431).  With protocol.configure(check_signatures=True) they first verify
 the server's signature and a quorum of the forwarded committee signatures
-(signaturesHold: the check the reference leaves as a comment, :387).
+(signaturesHold: the check the reference leaves as a comment, :387).  With
+protocol.configure(authenticate_shares=True) the m_i shares keep the AES-GCM
+tag the reference drops (:242), bound to (iteration, dealer, member), and a
+member whose shares do not all verify (openShares) sends TAG_CHECK_FAILED
+instead of its shares.
 """
 from __future__ import annotations
 
@@ -188,7 +192,12 @@ class SA_ClientAgent(Agent):
         enc_mi_shares = []
         for (_, y), cid in zip(shares, committee):
             nonce = bytes(self.random_state.randint(0, 256, size=16, dtype=np.uint8))
-            ct, _ = C.aes_gcm_encrypt(self.committee_keys[cid], y.to_bytes(self.key_length, "big"), nonce)
+            if param.authenticate_shares_on():     # the tag the reference drops (:242), behind the ciphertext
+                ct, tag = C.aes_gcm_seal(self.committee_keys[cid], y.to_bytes(self.key_length, "big"), nonce,
+                                         param.share_aad(self.current_iteration, self.id, cid))
+                ct += tag
+            else:
+                ct, _ = C.aes_gcm_encrypt(self.committee_keys[cid], y.to_bytes(self.key_length, "big"), nonce)
             enc_mi_shares.append((ct, nonce))
 
         # pairwise seeds: h_ijt -> H (group element) -> s_ij (:266-292), every client's in a few
@@ -258,7 +267,16 @@ class SA_ClientAgent(Agent):
         # decrypt this member's m_i shares (:402-420): one GPU launch for all of them, or one
         # OpenSSL context each on the host path
         sealed = list(zip(client_id_list, wire.deserialize_tuples_bytes(dec_target_mi)))
-        if sealed and param.deal_on_gpu():
+        if param.authenticate_shares_on():
+            dec_mi, bad = self.openShares(sealed)
+            if bad:
+                self.logger.info(f"client {self.id}: tag check failed in iteration {self.current_iteration} "
+                                 f"for the shares of {bad}")
+                self.sendMessage(self.serviceAgentID, Message({
+                    "msg": "TAG_CHECK_FAILED", "iteration": self.current_iteration, "sender": self.id,
+                    "bad": bad}), tag="tag_check_failed")
+                return
+        elif sealed and param.deal_on_gpu():
             if len({(len(ct), len(nonce)) for _, (ct, nonce) in sealed}) != 1:
                 raise RuntimeError("m_i share ciphertexts of one DEC differ in length")
             as_rows = lambda parts: np.frombuffer(b"".join(parts), np.uint8).reshape(len(sealed), -1)  # noqa: E731
@@ -274,6 +292,33 @@ class SA_ClientAgent(Agent):
             "shared_result_pairwise": wire.wire_to_ecp_json(dec_w),
             "shared_result_mi": wire.serialize_dim1_list(dec_mi),
             "committee_member_idx": self.committee_member_idx}), tag="comm_secret_sharing")
+
+    def openShares(self, sealed) -> tuple:
+        """protocol.configure(authenticate_shares=True): open this member's (dealer, (ciphertext ||
+        tag, nonce)) rows under the AAD the dealer sealed them with (protocol.share_aad) -- one
+        flm_aes_gcm_open launch, or crypto.aes_gcm_open per row on the host path.  Returns (the
+        shares in order, the dealers whose tag failed); a field of another length than 32 + 16
+        bytes, or a nonce of another than 16, is a failed tag.  One bad ciphertext silences this
+        member for the iteration (the server combines every client's m_i with one Lagrange set);
+        it says so and the server's threshold check decides."""
+        width = self.key_length + param.SHARE_TAG_LEN
+        good = [k for k, (_, (ct, nonce)) in enumerate(sealed) if len(ct) == width and len(nonce) == 16]
+        bad = [cid for cid, (ct, nonce) in sealed if len(ct) != width or len(nonce) != 16]
+        rows = [sealed[k] for k in good]
+        aads = [param.share_aad(self.current_iteration, cid, self.id) for cid, _ in rows]
+        if rows and param.deal_on_gpu():
+            as_rows = lambda parts: np.frombuffer(b"".join(parts), np.uint8).reshape(len(rows), -1)  # noqa: E731
+            field = as_rows(ct for _, (ct, _) in rows)
+            opened, ok = param.engine().aes_gcm_open_wire(as_rows(self.symmetric_keys[cid] for cid, _ in rows),
+                                                          as_rows(nonce for _, (_, nonce) in rows),
+                                                          field[:, :self.key_length], field[:, self.key_length:],
+                                                          aad=as_rows(aads))
+            plain = [row.tobytes() if v else None for row, v in zip(opened, ok)]
+        else:
+            plain = [C.aes_gcm_open(self.symmetric_keys[cid], ct[:self.key_length], ct[self.key_length:], nonce, aad)
+                     for (cid, (ct, nonce)), aad in zip(rows, aads)]
+        bad += [cid for (cid, _), p in zip(rows, plain) if p is None]
+        return [int.from_bytes(p, "big") for p in plain if p is not None], sorted(bad)
 
     def recordTime(self, startTime, categoryName):
         self.elapsed_time[categoryName] += pd.Timestamp("now") - startTime

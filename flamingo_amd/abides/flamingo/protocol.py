@@ -49,6 +49,9 @@ _mi_shares: dict = {}     # (root, iteration, id) -> [(ciphertext, nonce)] in co
 # The committee's check of the signatures the server forwards in DEC (the reference's
 # `# CHECK SIGNATURES`, SA_ClientAgent.py:387): off by default, so a run sends what it always sent.
 _check_signatures: bool = False        # configure(check_signatures=...)
+# The sealed m_i shares keep their AES-GCM tag (the reference drops it, SA_ClientAgent.py:242, and
+# opens without verify, :423-425): off by default, so a run sends what it always sent.
+_authenticate_shares: bool = False     # configure(authenticate_shares=...)
 # A member's 61 rows take as long in one GPU call as in the host loop (one wave's 2.6 ms chain against
 # 61 x 43 us of OpenSSL), so the members verify on the host unless told otherwise.
 _gpu_verify: bool = False              # configure(gpu_verify=True): one MaskEngine.ecdsa_verify call per DEC
@@ -58,9 +61,13 @@ _signature_quorum = 2 / 3               # configure(signature_quorum=...): the s
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
-              signature_quorum: float | None = None, gpu_verify: bool | None = None):
+              signature_quorum: float | None = None, gpu_verify: bool | None = None,
+              authenticate_shares: bool | None = None):
     """Reset the protocol parameters (between simulations / in tests)."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
+    global _authenticate_shares
+    if authenticate_shares is not None:
+        _authenticate_shares = bool(authenticate_shares)
     if gpu_deal is not None:
         _gpu_deal = bool(gpu_deal)
     if check_signatures is not None:
@@ -380,7 +387,26 @@ def deal_on_gpu() -> bool:
     """True when the clients' m_i shares go through mi_shares (configure(gpu_deal=True), the
     default).  An engine object that brings no dealing calls (a CPU test double, as for
     vector_store) leaves the agents on the host path, which sends the same bytes."""
-    return _gpu_deal and hasattr(engine(), "shamir_deal_wire") and hasattr(engine(), "aes_gcm_xor_wire")
+    calls = ("shamir_deal_wire", "aes_gcm_xor_wire") + (("aes_gcm_seal_wire", "aes_gcm_open_wire")
+                                                       if _authenticate_shares else ())
+    return _gpu_deal and all(hasattr(engine(), c) for c in calls)
+
+
+# ------------------------------------------------ authenticated sealing of the m_i shares
+SHARE_TAG_LEN = 16
+
+
+def authenticate_shares_on() -> bool:
+    """True when the m_i shares travel with their AES-GCM tag and the committee verifies it
+    (configure(authenticate_shares=True); off by default)."""
+    return _authenticate_shares
+
+
+def share_aad(iteration: int, dealer: int, member: int) -> bytes:
+    """What a sealed share is bound to besides its key: iteration (8 bytes) || dealer id (4) ||
+    committee member id (4), big endian.  The pair key is a static ECDH key, so without the
+    iteration last iteration's ciphertext of the same dealer would still verify."""
+    return int(iteration).to_bytes(8, "big") + int(dealer).to_bytes(4, "big") + int(member).to_bytes(4, "big")
 
 
 # ------------------------------------------------ the committee's signature check
@@ -477,7 +503,9 @@ def mi_shares(agent, iteration: int) -> list:
     (SA_ClientAgent.py:218-244): the Shamir shares of m_i at x = 1..C, each AES-128-GCM encrypted
     (tag dropped) under the key shared with that member (client_agent._aes_keys).  The first
     client to ask in an iteration deals every registered, online client's shares in ONE
-    flm_shamir_deal launch and seals them in ONE flm_aes_gcm_xor launch.
+    flm_shamir_deal launch and seals them in ONE flm_aes_gcm_xor launch -- or, with
+    configure(authenticate_shares=True), ONE flm_aes_gcm_seal launch, the 16-byte tag appended to
+    each ciphertext; no draw is added, so the draw order below holds either way.
 
     Every client's random state sees the draws of the host path in the same order, so the VECTOR
     messages stay byte-identical: a client draws its own m_i, coefficients and nonces through
@@ -509,10 +537,17 @@ def mi_shares(agent, iteration: int) -> list:
                 c.committee_keys = c._aes_keys(members)
         keys = np.frombuffer(b"".join(c.committee_keys[m] for c in batch for m in members), np.uint8).reshape(M * C, 16)
         nonces = np.frombuffer(b"".join(n for d in draws for n in d[2]), np.uint8).reshape(M * C, 16)
-        ct = engine().aes_gcm_xor_wire(keys, nonces, np.ascontiguousarray(shares.transpose(1, 0, 2)).reshape(M * C, 32))
+        plain = np.ascontiguousarray(shares.transpose(1, 0, 2)).reshape(M * C, 32)
+        if _authenticate_shares:       # ciphertext || tag per share, bound to (iteration, dealer, member)
+            aad = np.frombuffer(b"".join(share_aad(iteration, c.id, m) for c in batch for m in members),
+                                np.uint8).reshape(M * C, 16)
+            ct = np.concatenate(engine().aes_gcm_seal_wire(keys, nonces, plain, aad=aad), axis=1)
+        else:
+            ct = engine().aes_gcm_xor_wire(keys, nonces, plain)
+        w = ct.shape[1]
         for i, (c, d) in enumerate(zip(batch, draws)):
             b = ct[i * C:(i + 1) * C].tobytes()
-            _mi_shares[(root_seed, iteration, c.id)] = [(b[32 * k: 32 * k + 32], d[2][k]) for k in range(C)]
+            _mi_shares[(root_seed, iteration, c.id)] = [(b[w * k: w * k + w], d[2][k]) for k in range(C)]
         for cache in (_mi_shares, _mi_draws):
             for k in [k for k in cache if k[1] < iteration - 1]:
                 del cache[k]

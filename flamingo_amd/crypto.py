@@ -62,6 +62,8 @@ def _lib():
         "EVP_EncryptUpdate": (ip, [vp, ctypes.c_char_p, ctypes.POINTER(ip), ctypes.c_char_p, ip]),
         "EVP_DecryptInit_ex": (ip, [vp, vp, vp, ctypes.c_char_p, ctypes.c_char_p]),
         "EVP_DecryptUpdate": (ip, [vp, ctypes.c_char_p, ctypes.POINTER(ip), ctypes.c_char_p, ip]),
+        "EVP_EncryptFinal_ex": (ip, [vp, ctypes.c_char_p, ctypes.POINTER(ip)]),
+        "EVP_DecryptFinal_ex": (ip, [vp, ctypes.c_char_p, ctypes.POINTER(ip)]),
         "ECDSA_do_sign": (vp, [ctypes.c_char_p, ip, vp]), "ECDSA_do_verify": (ip, [ctypes.c_char_p, ip, vp, vp]),
         "ECDSA_SIG_get0": (None, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]), "ECDSA_SIG_free": (None, [vp]),
         "ECDSA_SIG_new": (vp, []), "ECDSA_SIG_set0": (ip, [vp, vp, vp]),
@@ -287,6 +289,63 @@ def aes_gcm_decrypt(key16: bytes, ct: bytes, nonce: bytes) -> bytes:
         n = ctypes.c_int(0)
         assert c.EVP_DecryptUpdate(ctx, out, ctypes.byref(n), ct, len(ct)) == 1
         return out.raw[: n.value]
+    finally:
+        c.EVP_CIPHER_CTX_free(ctx)
+
+
+EVP_CTRL_GCM_GET_TAG = 0x10
+EVP_CTRL_GCM_SET_TAG = 0x11
+
+
+def aes_gcm_seal(key16: bytes, data: bytes, nonce: bytes, aad: bytes = b""):
+    """c = AES.new(key, AES.MODE_GCM, nonce=nonce); c.update(aad); c.encrypt_and_digest(data):
+    (ciphertext, 16-byte tag).  The ciphertext is aes_gcm_encrypt's; the tag is what that drops."""
+    c = _lib()
+    ctx = c.EVP_CIPHER_CTX_new()
+    try:
+        assert c.EVP_EncryptInit_ex(ctx, c.EVP_aes_128_gcm(), None, None, None) == 1
+        assert c.EVP_CIPHER_CTX_ctrl(ctx, EVP_CTRL_GCM_SET_IVLEN, len(nonce), None) == 1
+        assert c.EVP_EncryptInit_ex(ctx, None, None, key16, nonce) == 1
+        n = ctypes.c_int(0)
+        if aad:
+            assert c.EVP_EncryptUpdate(ctx, None, ctypes.byref(n), aad, len(aad)) == 1
+        out = ctypes.create_string_buffer(len(data) + 16)
+        got = 0
+        if data:
+            assert c.EVP_EncryptUpdate(ctx, out, ctypes.byref(n), data, len(data)) == 1
+            got = n.value
+        fin = ctypes.create_string_buffer(16)
+        assert c.EVP_EncryptFinal_ex(ctx, fin, ctypes.byref(n)) == 1 and n.value == 0
+        tag = ctypes.create_string_buffer(16)
+        assert c.EVP_CIPHER_CTX_ctrl(ctx, EVP_CTRL_GCM_GET_TAG, 16, tag) == 1
+        return out.raw[:got], tag.raw
+    finally:
+        c.EVP_CIPHER_CTX_free(ctx)
+
+
+def aes_gcm_open(key16: bytes, ct: bytes, tag: bytes, nonce: bytes, aad: bytes = b""):
+    """decrypt_and_verify: the plaintext, or None where the 16-byte tag does not verify."""
+    if len(tag) != 16:
+        return None
+    c = _lib()
+    ctx = c.EVP_CIPHER_CTX_new()
+    try:
+        assert c.EVP_DecryptInit_ex(ctx, c.EVP_aes_128_gcm(), None, None, None) == 1
+        assert c.EVP_CIPHER_CTX_ctrl(ctx, EVP_CTRL_GCM_SET_IVLEN, len(nonce), None) == 1
+        assert c.EVP_DecryptInit_ex(ctx, None, None, key16, nonce) == 1
+        n = ctypes.c_int(0)
+        if aad:
+            assert c.EVP_DecryptUpdate(ctx, None, ctypes.byref(n), aad, len(aad)) == 1
+        out = ctypes.create_string_buffer(len(ct) + 16)
+        got = 0
+        if ct:
+            assert c.EVP_DecryptUpdate(ctx, out, ctypes.byref(n), ct, len(ct)) == 1
+            got = n.value
+        assert c.EVP_CIPHER_CTX_ctrl(ctx, EVP_CTRL_GCM_SET_TAG, 16, ctypes.create_string_buffer(bytes(tag), 16)) == 1
+        fin = ctypes.create_string_buffer(16)
+        if c.EVP_DecryptFinal_ex(ctx, fin, ctypes.byref(n)) != 1:
+            return None
+        return out.raw[:got]
     finally:
         c.EVP_CIPHER_CTX_free(ctx)
 

@@ -1,5 +1,6 @@
 // flm_aes128.h -- AES-128 and GCM's field multiplication as block functions, one message per lane
-// (gfx950); aes_gcm_xor_kernel in flm_p256.hip stages the S-box in LDS and drives them.
+// (gfx950); aes_gcm_xor_kernel and aes_gcm_auth_kernel in flm_p256.hip stage the S-box in LDS and
+// drive them.
 // Included by flm_p256.hip only; everything is in the anonymous namespace.
 // State columns are big-endian words (row 0 in the top byte).
 #pragma once
@@ -94,6 +95,55 @@ __device__ __forceinline__ void gcm_mul(uint32_t (&x)[4], const uint32_t (&h)[4]
 // (flm_aes_gcm_xor_dev), and a 12-byte nonce row promises no word alignment
 __device__ __forceinline__ uint32_t load_be32(const uint8_t *p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
+
+// the 44 round-key words of the 16-byte key at `key` (aes_gcm_xor_kernel keeps its own, older copy of
+// these lines, so that its machine code stays what §6 of DESIGN.md measured)
+__device__ __forceinline__ void aes128_expand_key(const uint8_t *sb, const uint8_t *key, uint32_t (&rk)[44]) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) rk[w] = load_be32(key + 4 * w);
+#pragma unroll
+    for (int w = 4; w < 44; ++w) {
+        uint32_t t = rk[w - 1];
+        if (w % 4 == 0) {
+            constexpr uint32_t rcon[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1b, 0x36};
+            t = aes_sub_word(sb, rotl32(t, 8)) ^ (rcon[w / 4 - 1] << 24);
+        }
+        rk[w] = rk[w - 4] ^ t;
+    }
+}
+
+// the first cnt (1..16) bytes at p as a block of big-endian words, zero behind them (GHASH's padding)
+__device__ __forceinline__ void load_block_be(const uint8_t *p, uint32_t cnt, uint32_t (&w)[4]) {
+    w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k)
+        if (k < cnt) w[k >> 2] |= (uint32_t)p[k] << (24u - 8u * (k & 3u));
+}
+
+// the first cnt (1..16) bytes of a block of big-endian words to p
+__device__ __forceinline__ void store_block_be(uint8_t *p, uint32_t cnt, const uint32_t (&w)[4]) {
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k)
+        if (k < cnt) p[k] = (uint8_t)(w[k >> 2] >> (24u - 8u * (k & 3u)));
+}
+
+// word w of a block whose first cnt bytes are ones and the rest zero
+__device__ __forceinline__ uint32_t head_mask(uint32_t cnt, uint32_t w) {
+    const uint32_t nb = cnt > 4u * w ? (cnt - 4u * w < 4u ? cnt - 4u * w : 4u) : 0u;
+    return nb ? 0xffffffffu << (32u - 8u * nb) : 0u;
+}
+
+// y = GHASH_h continued over len bytes at p, the last block zero padded (SP 800-38D, 6.4)
+__device__ __forceinline__ void ghash_absorb(uint32_t (&y)[4], const uint32_t (&h)[4], const uint8_t *p, uint32_t len) {
+#pragma unroll 1
+    for (uint32_t o = 0; o < len; o += 16u) {
+        uint32_t b[4];
+        load_block_be(p + o, len - o < 16u ? len - o : 16u, b);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) y[w] ^= b[w];
+        gcm_mul(y, h);
+    }
 }
 
 }  // namespace

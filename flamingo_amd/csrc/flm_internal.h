@@ -73,6 +73,15 @@ hipError_t launch_shamir_deal(const uint8_t *d_coeffs, int T, int M, const uint3
 // d_out = d_in ^ AES-128-GCM keystream of (key i, nonce i), n messages of len bytes (aes_gcm_xor_kernel)
 hipError_t launch_aes_gcm_xor(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_in,
                               uint8_t *d_out, uint32_t len, int n, hipStream_t stream);
+// AES-128-GCM with its tag, n messages of len bytes under aad_len bytes of AAD each (aes_gcm_auth_kernel):
+// seal writes d_out and d_tags (n x 16); open checks d_tags, writes d_ok (n) and the plaintext, or zero
+// bytes where the tag is wrong.  d_aad is unread when aad_len is 0, d_in and d_out when len is 0.
+hipError_t launch_aes_gcm_seal(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_aad,
+                               uint32_t aad_len, const uint8_t *d_in, uint8_t *d_out, uint32_t len, uint8_t *d_tags,
+                               int n, hipStream_t stream);
+hipError_t launch_aes_gcm_open(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_aad,
+                               uint32_t aad_len, const uint8_t *d_in, const uint8_t *d_tags, uint8_t *d_out,
+                               uint32_t len, uint8_t *d_ok, int n, hipStream_t stream);
 // d_ok[i] = ECDSA verdict of (pubkey i, digest i, signature i); d_flags n words or NULL (ecdsa_verify_kernel)
 hipError_t launch_ecdsa_verify(const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs, int n,
                                uint8_t *d_ok, uint32_t *d_flags, hipStream_t stream);

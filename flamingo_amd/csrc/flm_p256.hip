@@ -896,6 +896,99 @@ __global__ __launch_bounds__(kAesThreads) void aes_gcm_xor_kernel(const uint8_t 
     }
 }
 
+// ------------------------------------------------------------- AES-128-GCM with its tag
+// The whole of NIST SP 800-38D for AES-128, one lane per message like aes_gcm_xor_kernel:
+//     H, J0 and C as above;  S = GHASH_H(A || 0* || C || 0* || [8 aad_len]_64 || [8 len]_64);
+//     T = S ^ E_k(J0)        (J0 itself: the keystream starts at inc32(J0))
+// Seal writes C and T.  Open recomputes T over the ciphertext it was given, compares all 16 bytes
+// (OR of XORs, no early exit), writes ok[i] and then the plaintext -- or zero bytes where the tag
+// is wrong, never unauthenticated plaintext.  in == out is allowed: seal reads a block before it
+// writes it, open has hashed every block before it writes the first.
+// One copy of the cipher's code per kernel: pass 0 encrypts the zero block, one pass J0 (the tag's
+// mask; last for seal, which hashes C as it produces it, second for open, which needs the verdict
+// before it writes), the others a keystream block each.  The lane holds the 44 round keys, H, J0
+// and the GHASH accumulator; gcm_mul's loops stay rolled.
+// keys: [n][16]; nonces: [n][nonce_len]; aad: [n][aad_len] (unread when aad_len is 0); in, out:
+// [n][len] (unread when len is 0); tags: [n][16], written by seal and read by open; ok: [n], open only
+template <bool kOpen>
+__global__ __launch_bounds__(kAesThreads) void aes_gcm_auth_kernel(const uint8_t *__restrict__ keys,
+                                                                   const uint8_t *__restrict__ nonces, int nonce_len,
+                                                                   const uint8_t *__restrict__ aad, uint32_t aad_len,
+                                                                   const uint8_t *in, uint8_t *out, uint32_t len,
+                                                                   const uint8_t *tags_in, uint8_t *tags_out,
+                                                                   uint8_t *ok_out, int n) {
+    __shared__ uint8_t sb[256];
+    sb[threadIdx.x] = kAesSbox[threadIdx.x];
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * kAesThreads + threadIdx.x;
+    if (i >= (size_t)n) return;
+    uint32_t rk[44];
+    aes128_expand_key(sb, keys + i * 16, rk);
+    const uint8_t *nc = nonces + i * (size_t)nonce_len;
+    uint32_t j0[4] = {load_be32(nc), load_be32(nc + 4), load_be32(nc + 8), 1u};
+    const uint8_t *src = in + i * (size_t)len;
+    uint8_t *dst = out + i * (size_t)len;
+    const uint32_t blocks = (len + 15u) / 16u;
+    uint32_t h[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0};
+    uint32_t open_mask = 0;  // all ones once open has found the tag right
+#pragma unroll 1
+    for (uint32_t t = 0; t <= blocks + 1u; ++t) {
+        const bool tag_pass = kOpen ? t == 1u : t == blocks + 1u;
+        const uint32_t m = kOpen ? t - 1u : t;  // the keystream block of a pass that is neither
+        uint32_t s[4] = {0, 0, 0, 0};
+        if (t > 0) {
+            s[0] = j0[0], s[1] = j0[1], s[2] = j0[2];
+            s[3] = j0[3] + (tag_pass ? 0u : m);  // inc32: the low word wraps, nothing carries out of it
+        }
+        aes128_encrypt(sb, rk, s);
+        if (t == 0) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) h[w] = s[w];
+            if (nonce_len == 16) {
+                j0[3] = load_be32(nc + 12);
+                gcm_mul(j0, h);
+                j0[3] ^= 128u;  // 0^64 || [128]_64
+                gcm_mul(j0, h);
+            }
+            ghash_absorb(y, h, aad + i * (size_t)aad_len, aad_len);
+            if (kOpen) ghash_absorb(y, h, src, len);
+            continue;
+        }
+        if (tag_pass) {
+            y[1] ^= aad_len << 3;  // [8 aad_len]_64 || [8 len]_64: both far below 2^32
+            y[3] ^= len << 3;
+            gcm_mul(y, h);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) s[w] ^= y[w];
+            if (kOpen) {
+                uint32_t diff = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) diff |= s[w] ^ load_be32(tags_in + i * 16 + 4 * w);
+                open_mask = diff ? 0u : 0xffffffffu;
+                ok_out[i] = (uint8_t)(open_mask & 1u);
+            } else {
+                store_block_be(tags_out + i * 16, 16u, s);
+            }
+            continue;
+        }
+        const uint32_t o = 16u * (m - 1u), cnt = len - o < 16u ? len - o : 16u;
+        uint32_t b[4];
+        load_block_be(src + o, cnt, b);
+        if (kOpen) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) b[w] = (b[w] ^ s[w]) & open_mask;
+        } else {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                b[w] = (b[w] ^ s[w]) & head_mask(cnt, w);  // the keystream behind the message is no ciphertext
+                y[w] ^= b[w];
+            }
+            gcm_mul(y, h);
+        }
+        store_block_be(dst + o, cnt, b);
+    }
+}
+
 // ------------------------------------------------------------- hash to curve
 // The client's pairwise seed group element (SA_ClientAgent.py:275-286): h_ijt, a decimal string
 // below 2^16, goes through util/crypto/ecchash.hash_str_to_curve(msg, count=2, modulus=n, degree=1,
@@ -1236,6 +1329,26 @@ hipError_t launch_aes_gcm_xor(const uint8_t *d_keys, const uint8_t *d_nonces, in
     if (n <= 0 || len == 0) return hipSuccess;
     hipLaunchKernelGGL(aes_gcm_xor_kernel, dim3((unsigned)(((size_t)n + kAesThreads - 1) / kAesThreads)),
                        dim3(kAesThreads), 0, stream, d_keys, d_nonces, nonce_len, d_in, d_out, len, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_aes_gcm_seal(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_aad,
+                               uint32_t aad_len, const uint8_t *d_in, uint8_t *d_out, uint32_t len, uint8_t *d_tags,
+                               int n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aes_gcm_auth_kernel<false>, dim3((unsigned)(((size_t)n + kAesThreads - 1) / kAesThreads)),
+                       dim3(kAesThreads), 0, stream, d_keys, d_nonces, nonce_len, d_aad, aad_len, d_in, d_out, len,
+                       (const uint8_t *)nullptr, d_tags, (uint8_t *)nullptr, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_aes_gcm_open(const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len, const uint8_t *d_aad,
+                               uint32_t aad_len, const uint8_t *d_in, const uint8_t *d_tags, uint8_t *d_out,
+                               uint32_t len, uint8_t *d_ok, int n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aes_gcm_auth_kernel<true>, dim3((unsigned)(((size_t)n + kAesThreads - 1) / kAesThreads)),
+                       dim3(kAesThreads), 0, stream, d_keys, d_nonces, nonce_len, d_aad, aad_len, d_in, d_out, len, d_tags,
+                       (uint8_t *)nullptr, d_ok, n);
     return hipGetLastError();
 }
 

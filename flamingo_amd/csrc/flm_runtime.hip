@@ -1012,7 +1012,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.5 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor)"; }
+const char *flm_version(void) { return "flamingo_hip 0.5 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor) + aes_gcm_seal, aes_gcm_open"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1635,6 +1635,93 @@ int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, in
     FLM_HIP(ctx, flm::launch_aes_gcm_xor(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len,
                                          hi->as<const uint8_t>(), ho->as<uint8_t>(), (uint32_t)len, n, s));
     return hc.finish();
+}
+
+int flm_aes_gcm_seal_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
+                         const uint8_t *d_aad, size_t aad_len, const uint8_t *d_in, uint8_t *d_out, size_t len,
+                         uint8_t *d_tags_out, int n, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n))
+        return fail(ctx, FLM_EINVAL, "aes gcm seal (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", nonce_len, aad_len, len, n, why);
+    if (n == 0) return 0;
+    if (const char *why = flm::rt::aes_gcm_auth_null_error(d_keys, d_nonces, d_aad, aad_len, d_in, d_out, len, d_tags_out, nullptr, false))
+        return fail(ctx, FLM_EINVAL, "aes gcm seal: %s", why);
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_aes_gcm_seal(d_keys, d_nonces, nonce_len, d_aad, (uint32_t)aad_len, d_in, d_out,
+                                          (uint32_t)len, d_tags_out, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_aes_gcm_open_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
+                         const uint8_t *d_aad, size_t aad_len, const uint8_t *d_in, const uint8_t *d_tags,
+                         uint8_t *d_out, size_t len, uint8_t *d_ok_out, int n, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n))
+        return fail(ctx, FLM_EINVAL, "aes gcm open (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", nonce_len, aad_len, len, n, why);
+    if (n == 0) return 0;
+    if (const char *why = flm::rt::aes_gcm_auth_null_error(d_keys, d_nonces, d_aad, aad_len, d_in, d_out, len, d_tags, d_ok_out, true))
+        return fail(ctx, FLM_EINVAL, "aes gcm open: %s", why);
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_aes_gcm_open(d_keys, d_nonces, nonce_len, d_aad, (uint32_t)aad_len, d_in, d_tags, d_out,
+                                          (uint32_t)len, d_ok_out, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+namespace {
+// the host-pointer seal (ok_out NULL: tags written) and open (tags read, ok_out written): one body
+int aes_gcm_auth_host(flm_ctx *ctx, const char *what, const uint8_t *keys, const uint8_t *nonces, int nonce_len,
+                      const uint8_t *aad, size_t aad_len, const uint8_t *in, uint8_t *out, size_t len, uint8_t *tags,
+                      uint8_t *ok_out, bool open, int n) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n))
+        return fail(ctx, FLM_EINVAL, "%s (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", what, nonce_len, aad_len, len, n, why);
+    if (n == 0) return 0;
+    if (const char *why = flm::rt::aes_gcm_auth_null_error(keys, nonces, aad, aad_len, in, out, len, tags, ok_out, open))
+        return fail(ctx, FLM_EINVAL, "%s: %s", what, why);
+    FLM_ON_DEVICE(ctx);
+    hipStream_t s = ctx->stream;
+    const flm::rt::AesGcmAuthBytes nb = flm::rt::aes_gcm_auth_bytes(nonce_len, aad_len, len, n);
+    HostCopies hc(ctx, s);
+    hc.in(keys, nb.keys, ctx->ec_scal);
+    hc.in(nonces, nb.nonces, ctx->ec_base);
+    if (aad_len) hc.in(aad, nb.aad, ctx->ec_in);
+    const HostCopies::Span *hi = nullptr, *ho = nullptr;
+    if (len) {
+        hi = hc.in(in, nb.data, ctx->bytes_in, HostCopies::kMayRunInPlace);
+        ho = hc.out(out, nb.data, ctx->bytes_out, HostCopies::kMayRunInPlace);
+    }
+    if (open) {
+        hc.in(tags, nb.tags, ctx->ec_dig);
+        hc.out(ok_out, nb.ok, ctx->ec_out);
+    } else {
+        hc.out(tags, nb.tags, ctx->ec_dig);
+    }
+    if (int rc = hc.begin()) return rc;
+    const uint8_t *d_aad = aad_len ? ctx->ec_in.as<uint8_t>() : nullptr;
+    const uint8_t *d_in = len ? hi->as<const uint8_t>() : nullptr;
+    uint8_t *d_out = len ? ho->as<uint8_t>() : nullptr;
+    if (open)
+        FLM_HIP(ctx, flm::launch_aes_gcm_open(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len, d_aad,
+                                              (uint32_t)aad_len, d_in, ctx->ec_dig.as<uint8_t>(), d_out, (uint32_t)len,
+                                              ctx->ec_out.as<uint8_t>(), n, s));
+    else
+        FLM_HIP(ctx, flm::launch_aes_gcm_seal(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len, d_aad,
+                                              (uint32_t)aad_len, d_in, d_out, (uint32_t)len, ctx->ec_dig.as<uint8_t>(), n, s));
+    return hc.finish();
+}
+}  // namespace
+
+int flm_aes_gcm_seal(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *aad,
+                     size_t aad_len, const uint8_t *in, uint8_t *out, size_t len, uint8_t *tags_out, int n) {
+    return aes_gcm_auth_host(ctx, "aes gcm seal", keys, nonces, nonce_len, aad, aad_len, in, out, len, tags_out, nullptr,
+                             false, n);
+}
+
+int flm_aes_gcm_open(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *aad,
+                     size_t aad_len, const uint8_t *in, const uint8_t *tags, uint8_t *out, size_t len,
+                     uint8_t *ok_out, int n) {
+    return aes_gcm_auth_host(ctx, "aes gcm open", keys, nonces, nonce_len, aad, aad_len, in, out, len,
+                             const_cast<uint8_t *>(tags), ok_out, true, n);
 }
 
 int flm_ecdsa_verify_dev(flm_ctx *ctx, const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs,

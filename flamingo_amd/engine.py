@@ -614,6 +614,96 @@ class MaskEngine:
         self._check(rc, "flm_aes_gcm_xor_dev")
         return out
 
+    @staticmethod
+    def _gcm_rows(keys, nonces, aad, data):
+        """The host arrays of aes_gcm_seal_wire / aes_gcm_open_wire: (keys, nonces, aad or None, data)."""
+        k = np.ascontiguousarray(keys, np.uint8)
+        nc = np.ascontiguousarray(nonces, np.uint8)
+        d = np.ascontiguousarray(data, np.uint8)
+        if k.ndim != 2 or k.shape[1] != 16 or nc.ndim != 2 or d.ndim != 2:
+            raise RuntimeError("keys must be (n, 16), nonces (n, nonce_len), data (n, len)")
+        n = k.shape[0]
+        if nc.shape[0] != n or d.shape[0] != n:
+            raise RuntimeError(f"{n} keys for {nc.shape[0]} nonces and {d.shape[0]} messages")
+        a = None
+        if aad is not None:
+            a = np.ascontiguousarray(aad, np.uint8)
+            if a.ndim != 2 or a.shape[0] != n:
+                raise RuntimeError(f"aad must be ({n}, aad_len)")
+            if a.shape[1] == 0:
+                a = None
+        return k, nc, a, d
+
+    def aes_gcm_seal_wire(self, keys, nonces, data, aad=None):
+        """AES-128-GCM with its tag for n messages (flm_aes_gcm_seal): what pycryptodome's
+        update(aad) + encrypt_and_digest(data) returns.  keys (n, 16), nonces (n, 12 or 16), data
+        (n, len) with 0 <= len <= 256, aad (n, aad_len <= 64) or None -> (ct (n, len), tags (n, 16))."""
+        k, nc, a, d = self._gcm_rows(keys, nonces, aad, data)
+        n = k.shape[0]
+        out = np.zeros_like(d)
+        tags = np.zeros((n, 16), np.uint8)
+        rc = self.lib.flm_aes_gcm_seal(self.ctx, p_u8(k), p_u8(nc), nc.shape[1], p_u8(a) if a is not None else None,
+                                       a.shape[1] if a is not None else 0, p_u8(d), p_u8(out), d.shape[1], p_u8(tags), n)
+        self._check(rc, "flm_aes_gcm_seal")
+        return out, tags
+
+    def aes_gcm_open_wire(self, keys, nonces, data, tags, aad=None):
+        """The verifying inverse (flm_aes_gcm_open): -> (plain (n, len), ok (n,) bool).  A row whose tag
+        does not verify has ok False and len zero bytes, never unauthenticated plaintext."""
+        k, nc, a, d = self._gcm_rows(keys, nonces, aad, data)
+        n = k.shape[0]
+        t = np.ascontiguousarray(tags, np.uint8)
+        if t.shape != (n, 16):
+            raise RuntimeError(f"tags must be ({n}, 16)")
+        out = np.zeros_like(d)
+        ok = np.zeros(n, np.uint8)
+        rc = self.lib.flm_aes_gcm_open(self.ctx, p_u8(k), p_u8(nc), nc.shape[1], p_u8(a) if a is not None else None,
+                                       a.shape[1] if a is not None else 0, p_u8(d), p_u8(t), p_u8(out), d.shape[1],
+                                       p_u8(ok), n)
+        self._check(rc, "flm_aes_gcm_open")
+        return out, ok.astype(bool)
+
+    def _gcm_dev_args(self, keys, nonces, aad, data, out, tags):
+        _need(keys.dim() == 2 and nonces.dim() == 2 and data.dim() == 2,
+              "keys must be (n, 16), nonces (n, nonce_len), data (n, len)")
+        n, ln = data.shape
+        _need(keys.shape[0] == n and nonces.shape[0] == n, f"{keys.shape[0]} keys and {nonces.shape[0]} nonces "
+              f"for {n} messages")
+        _dev_bytes(keys, "keys", 16, n)
+        _dev_bytes(nonces, "nonces", nonces.shape[1], n)
+        _dev_bytes(data, "data", ln, n)
+        _dev_bytes(out, "out", ln, n)
+        _dev_bytes(tags, "tags", 16, n)
+        al = 0
+        if aad is not None and aad.dim() == 2 and aad.shape[1] > 0:
+            al = aad.shape[1]
+            _dev_bytes(aad, "aad", al, n)
+        else:
+            aad = None
+        return n, ln, aad, al
+
+    def aes_gcm_seal_dev(self, keys, nonces, data, tags_out, out=None, aad=None, stream=None):
+        """Device form of aes_gcm_seal_wire: uint8 CUDA tensors, tags_out (n, 16); out (n, len) may be
+        `data` itself (the default: in place); enqueued on `stream`, nothing staged or awaited."""
+        out = data if out is None else out
+        n, ln, aad, al = self._gcm_dev_args(keys, nonces, aad, data, out, tags_out)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        rc = self.lib.flm_aes_gcm_seal_dev(self.ctx, vp(keys), vp(nonces), nonces.shape[1], vp(aad), al, vp(data),
+                                           vp(out), ln, vp(tags_out), n, self._stream_handle(stream))
+        self._check(rc, "flm_aes_gcm_seal_dev")
+        return out, tags_out
+
+    def aes_gcm_open_dev(self, keys, nonces, data, tags, ok_out, out=None, aad=None, stream=None):
+        """Device form of aes_gcm_open_wire: ok_out (n,) uint8; out may be `data` itself (the default)."""
+        out = data if out is None else out
+        n, ln, aad, al = self._gcm_dev_args(keys, nonces, aad, data, out, tags)
+        _dev_bytes(ok_out, "ok_out", 1, n)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        rc = self.lib.flm_aes_gcm_open_dev(self.ctx, vp(keys), vp(nonces), nonces.shape[1], vp(aad), al, vp(data),
+                                           vp(tags), vp(out), ln, vp(ok_out), n, self._stream_handle(stream))
+        self._check(rc, "flm_aes_gcm_open_dev")
+        return out, ok_out
+
     def ecdsa_verify_wire(self, pk_w, digests_w, sigs_w):
         """flm_ecdsa_verify on wire arrays: public keys (n, 64) x||y, digests (n, 32), signatures (n, 64)
         r||s, uint8 big endian -> (ok (n,) bool, flags (n,) uint32).  The verdict of FIPS 186-4 /

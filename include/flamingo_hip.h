@@ -290,6 +290,31 @@ int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, in
                     uint8_t *out, size_t len, int n);
 int flm_aes_gcm_xor_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
                         const uint8_t *d_in, uint8_t *d_out, size_t len, int n, void *stream);
+/* AES-128-GCM in full (NIST SP 800-38D), n messages per call: ciphertext and 16-byte tag, what
+ *   c = AES.new(key, AES.MODE_GCM, nonce=nonce); c.update(aad); ct, tag = c.encrypt_and_digest(data)
+ * returns, and decrypt_and_verify on the way back.  The ciphertext is flm_aes_gcm_xor's;
+ *   tag = GHASH_H(aad || 0* || ct || 0* || [8 aad_len]_64 || [8 len]_64) ^ E_k(J0).
+ * keys: n*16 bytes; nonces: n*nonce_len, nonce_len 12 or 16; aad: n*aad_len, 0 <= aad_len <= 64,
+ * NULL iff aad_len is 0; in, out: n*len, 0 <= len <= 256 (len 0: a tag over the AAD alone; in and
+ * out are then not read and may be NULL); tags: n*16; all dense; in == out is allowed.
+ * flm_aes_gcm_open recomputes each tag over the ciphertext it is given and compares all 16
+ * bytes: ok_out[i] (n bytes) is 1 and out[i] the plaintext where they agree, else ok_out[i] is 0
+ * and out[i] is len zero bytes -- never unauthenticated plaintext.  A wrong tag is a result, not
+ * an error: the call returns 0.  FLM_EINVAL (nothing written) for another nonce_len, len or
+ * aad_len, n < 0 or above 2^26, or a NULL array; n = 0 succeeds and launches nothing.
+ * _dev: device pointers, enqueued on `stream` (NULL: the null stream); nothing is staged or
+ * synchronised, and the call returns without waiting for earlier work on the stream. */
+int flm_aes_gcm_seal(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *aad,
+                     size_t aad_len, const uint8_t *in, uint8_t *out, size_t len, uint8_t *tags_out, int n);
+int flm_aes_gcm_seal_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
+                         const uint8_t *d_aad, size_t aad_len, const uint8_t *d_in, uint8_t *d_out, size_t len,
+                         uint8_t *d_tags_out, int n, void *stream);
+int flm_aes_gcm_open(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *aad,
+                     size_t aad_len, const uint8_t *in, const uint8_t *tags, uint8_t *out, size_t len,
+                     uint8_t *ok_out, int n);
+int flm_aes_gcm_open_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
+                         const uint8_t *d_aad, size_t aad_len, const uint8_t *d_in, const uint8_t *d_tags,
+                         uint8_t *d_out, size_t len, uint8_t *d_ok_out, int n, void *stream);
 /* Batched ECDSA verification on P-256, the check the reference leaves as the comment
  * `# CHECK SIGNATURES` at SA_ClientAgent.py:387: before a committee member releases its
  * decryption shares it must verify the server's signature over the offline set and the

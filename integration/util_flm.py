@@ -34,6 +34,8 @@ for _name, _res, _args in (
         ("flm_shamir_combine", _int, [_vp, _u8p, _u8p, _int, _int, _u8p]),
         ("flm_shamir_deal", _int, [_vp, _u8p, _int, _int, _u32p, _int, _u8p]),
         ("flm_aes_gcm_xor", _int, [_vp, _u8p, _u8p, _int, _u8p, _u8p, _sz, _int]),
+        ("flm_aes_gcm_seal", _int, [_vp, _u8p, _u8p, _int, _u8p, _sz, _u8p, _u8p, _sz, _u8p, _int]),
+        ("flm_aes_gcm_open", _int, [_vp, _u8p, _u8p, _int, _u8p, _sz, _u8p, _u8p, _u8p, _sz, _u8p, _int]),
         ("flm_ecdsa_verify", _int, [_vp, _u8p, _u8p, _u8p, _int, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
         ("flm_ec_combine", _int, [_vp, _u8p, _u8p, _u8p, _int, _int, _int, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
         ("flm_group_init", _int, [ctypes.POINTER(_vp), _int, ctypes.POINTER(_int)]),
@@ -169,6 +171,48 @@ def aes_gcm_xor(keys, nonces, datas):
     _check(_lib.flm_aes_gcm_xor(_context(), k.ctypes.data_as(_u8p), nc.ctypes.data_as(_u8p), nl,
                                 d.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), ln, n))
     return [out[ln * i:ln * i + ln].tobytes() for i in range(n)]
+
+
+def _gcm_batch(keys, nonces, aads, datas):
+    n = len(datas)
+    k, nc, d = (np.frombuffer(b"".join(bytes(v) for v in part), np.uint8) for part in (keys, nonces, datas))
+    ln, nl = len(datas[0]), len(nonces[0])
+    al = len(aads[0]) if aads else 0
+    a = np.frombuffer(b"".join(bytes(v) for v in aads), np.uint8) if al else None
+    if k.size != 16 * n or nc.size != nl * n or d.size != ln * n or (al and (len(aads) != n or a.size != al * n)):
+        raise RuntimeError("keys must be 16 bytes each; nonces, messages, and AADs, of one length")
+    return n, k, nc, nl, a, al, d, ln
+
+
+def aes_gcm_seal(keys, nonces, datas, aads=None):
+    """[(ct, tag)] with c = AES.new(key, AES.MODE_GCM, nonce=nonce); c.update(aad); ct, tag =
+    c.encrypt_and_digest(data), for a batch of equally long messages (at most 256 bytes), nonces (12
+    or 16 bytes) and AADs (at most 64 bytes, or None): the sealing of SA_ClientAgent.py:227-244 with
+    the tag the reference discards at :242."""
+    if len(datas) == 0:
+        return []
+    n, k, nc, nl, a, al, d, ln = _gcm_batch(keys, nonces, aads, datas)
+    out, tags = np.empty(max(1, ln * n), np.uint8), np.empty(16 * n, np.uint8)
+    _check(_lib.flm_aes_gcm_seal(_context(), k.ctypes.data_as(_u8p), nc.ctypes.data_as(_u8p), nl,
+                                 a.ctypes.data_as(_u8p) if al else None, al, d.ctypes.data_as(_u8p),
+                                 out.ctypes.data_as(_u8p), ln, tags.ctypes.data_as(_u8p), n))
+    return [(out[ln * i:ln * i + ln].tobytes(), tags[16 * i:16 * i + 16].tobytes()) for i in range(n)]
+
+
+def aes_gcm_open(keys, nonces, cts, tags, aads=None):
+    """[c.decrypt_and_verify(ct, tag), or None where it raises ValueError("MAC check failed")] for a
+    batch: the opening of SA_ClientAgent.py:402-425 with the check it leaves out."""
+    if len(cts) == 0:
+        return []
+    n, k, nc, nl, a, al, d, ln = _gcm_batch(keys, nonces, aads, cts)
+    t = np.frombuffer(b"".join(bytes(v) for v in tags), np.uint8)
+    if t.size != 16 * n:
+        raise RuntimeError("tags must be 16 bytes each")
+    out, ok = np.empty(max(1, ln * n), np.uint8), np.zeros(n, np.uint8)
+    _check(_lib.flm_aes_gcm_open(_context(), k.ctypes.data_as(_u8p), nc.ctypes.data_as(_u8p), nl,
+                                 a.ctypes.data_as(_u8p) if al else None, al, d.ctypes.data_as(_u8p),
+                                 t.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p), ln, ok.ctypes.data_as(_u8p), n))
+    return [out[ln * i:ln * i + ln].tobytes() if ok[i] else None for i in range(n)]
 
 
 def ecdsa_verify(public_keys, messages, signatures):
