@@ -64,6 +64,8 @@ SIGNATURES = {
     "flm_aes_gcm_open_dev": (_int, [_vp, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _int, _vp]),
     "flm_ecdsa_verify": (_int, [_vp, _u8p, _u8p, _u8p, _int, _u8p, _u32p]),
     "flm_ecdsa_verify_dev": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "flm_feldman_verify": (_int, [_vp, _u8p, _int, _int, _u32p, _u32p, _int, _u8p, _int, _u8p, _u8p, _u32p]),
+    "flm_feldman_verify_dev": (_int, [_vp, _vp, _int, _int, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp]),
     "flm_pair_units_dev": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _sz, _vp, _int, _int, _vp]),
     "flm_flag_set_dev": (_int, [_vp, _vp, _vp]),
     "flm_cu_count": (_int, [_vp, _vp]),

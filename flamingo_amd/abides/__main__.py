@@ -1,5 +1,5 @@
 """Entry point with the reference's two-stage flag parsing (abides.py:17-29):
-``python -m flamingo_amd.abides -c flamingo [config flags]``."""
+``python -m flamingo_amd.abides -c flamingo [config flags]`` or ``-c dkg [config flags]``."""
 import argparse
 import sys
 
@@ -16,10 +16,15 @@ def main(argv=None):
     ap.add_argument("-c", "--config", required=True)
     ap.add_argument("--config-help", action="store_true")
     args, _ = ap.parse_known_args(argv)
-    if args.config != "flamingo":
-        raise SystemExit(f"config {args.config!r} is not part of this repository (only 'flamingo')")
-    from .config_flamingo import run
+    if args.config not in ("flamingo", "dkg"):
+        raise SystemExit(f"config {args.config!r} is not part of this repository (only 'flamingo' and 'dkg')")
     from .flamingo import protocol
+    if args.config == "dkg":
+        from .config_dkg import run
+        run(argv)
+        protocol.shutdown()
+        return
+    from .config_flamingo import run
     res = run(argv)
     # explicit teardown (the server's store, its device group and RCCL clique, the engine) instead of
     # leaving them to finalizers at interpreter exit

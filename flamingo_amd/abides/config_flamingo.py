@@ -68,6 +68,11 @@ def parse(argv):
     # the sealed m_i shares keep their AES-GCM tag and the committee verifies it before it opens them
     # (protocol.configure(authenticate_shares=True)); off by default
     ap.add_argument("--authenticate_shares", action="store_true")
+    # the committee generates the system key itself before the first iteration, by the DKG of
+    # abides/dkg among its sorted members (protocol.configure(dkg=True)): the server never holds the key
+    # and sends no COMMITTEE_SHARED_SK; off by default.  --host_dkg: that DKG's dealing and checks on the host
+    ap.add_argument("--dkg", action="store_true")
+    ap.add_argument("--host_dkg", action="store_true")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -82,6 +87,26 @@ def offline_schedule(n: int, iterations: int, always=(), dropout: float = 0.0) -
             for i in np.random.Generator(np.random.PCG64(t)).choice(n, k, replace=False):
                 out.setdefault(int(i), set()).add(t)
     return out
+
+
+def committee_dkg(num_clients: int, seed: int, latency: str = "cubic", gpu_dkg: bool = True) -> None:
+    """The committee's key generation before the first iteration (protocol.configure(dkg=True)): a
+    joint-Feldman DKG (abides/dkg) among the sorted committee, member index cnt + 1 as initialize
+    assigns it, with as many coefficients as the default set-up's shamir_share(system_sk,
+    max(1, committee_threshold), ...) call, so reconstruction and its Lagrange sets are untouched.
+    The group key becomes the protocol's system_pk and each member's key share its committee_shared_sk."""
+    from . import config_dkg
+    from .dkg import keygen
+    members = sorted(param.committee(num_clients))
+    threshold = max(1, int(param.fraction * len(members)))
+    keygen.configure(gpu_dkg=gpu_dkg)
+    res = config_dkg.simulate(len(members), seed, latency=latency, poly_degree=threshold - 1)
+    done = res["members"]
+    if sorted(done) != list(range(1, len(members) + 1)):
+        raise RuntimeError(f"{len(done)} of {len(members)} committee members finished the key generation")
+    _, key = config_dkg.agreed(done)
+    param.set_dkg_result(key, {cid: done[cnt + 1]["sk_share"] for cnt, cid in enumerate(members)})
+    keygen.configure()
 
 
 # Young-generation threshold for the run: the simulation allocates ~1.7 M container objects per
@@ -118,7 +143,10 @@ def _run(args):
                     gpu_deal=False if args.host_deal else None,
                     check_signatures=True if args.check_signatures else None,
                     gpu_verify=True if args.gpu_verify else None,
-                    authenticate_shares=True if args.authenticate_shares else None)
+                    authenticate_shares=True if args.authenticate_shares else None,
+                    dkg=True if args.dkg else None)
+    if param.dkg_on():
+        committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
     offline_its = offline_schedule(n, args.num_iterations, offline, args.dropout)
     print(f"Silent mode: {log.silent_mode}")

@@ -100,6 +100,10 @@ class SA_ClientAgent(Agent):
         self.committee_keys = {}     # member -> AES key (a_i A_c).x mod 2^128 (:234-236)
         self.symmetric_keys = {}     # (committee members) client -> AES key (:86-91)
         param.register_client(self)
+        if param.dkg_on() and param.dkg_share(id) is not None:
+            # the committee generated the key itself: what COMMITTEE_SHARED_SK would carry
+            self.committee_member_idx, share = param.dkg_share(id)
+            self.committee_shared_sk = (self.committee_member_idx, share)
         if id in self.user_committee:
             ids = list(range(num_clients))
             self.symmetric_keys = self._aes_keys(ids)

@@ -57,15 +57,23 @@ _authenticate_shares: bool = False     # configure(authenticate_shares=...)
 _gpu_verify: bool = False              # configure(gpu_verify=True): one MaskEngine.ecdsa_verify call per DEC
 _signature_quorum = 2 / 3               # configure(signature_quorum=...): the share of the committee whose
                                         # signatures over the same labels must verify
+# The committee generates the system key itself (config_flamingo's --dkg: a joint-Feldman DKG among the
+# members, abides/dkg) instead of receiving Shamir shares of a key the server knows (the reference's
+# set-up, SA_ServiceAgent.py:261-279): off by default, so a run sends what it always sent.
+_dkg: bool = False                      # configure(dkg=...)
+_dkg_result = None                      # (group key, {committee member id: (member index, key share)})
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
-              authenticate_shares: bool | None = None):
+              authenticate_shares: bool | None = None, dkg: bool | None = None):
     """Reset the protocol parameters (between simulations / in tests)."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares
+    global _authenticate_shares, _dkg, _dkg_result
+    if dkg is not None:
+        _dkg = bool(dkg)
+    _dkg_result = None
     if authenticate_shares is not None:
         _authenticate_shares = bool(authenticate_shares)
     if gpu_deal is not None:
@@ -215,13 +223,37 @@ def find_neighbors(root, current_iteration, num_clients, id, neighborhood_size) 
 
 
 def pki(num_clients: int):
-    """Key material for this simulation (pki_files/ stand-in, see pki.py)."""
+    """Key material for this simulation (pki_files/ stand-in, see pki.py).  With configure(dkg=True)
+    the system key is the committee's (set_dkg_result must have run): its public half is the DKG's
+    group key and nobody holds the private half."""
     key = (root_seed, num_clients)
     if key not in _pkis:
         from .pki import PKI
         _pkis.clear()
-        _pkis[key] = PKI(root_seed, num_clients, engine())
+        if _dkg and _dkg_result is None:
+            raise RuntimeError("configure(dkg=True): the committee's key generation has not run (set_dkg_result)")
+        _pkis[key] = PKI(root_seed, num_clients, engine(), system_pk=_dkg_result[0] if _dkg else None)
     return _pkis[key]
+
+
+def dkg_on() -> bool:
+    """True when the committee's key comes from its own key generation (configure(dkg=True))."""
+    return _dkg
+
+
+def set_dkg_result(group_key, shares: dict) -> None:
+    """The outcome of the committee's key generation: the group key and, per committee member id,
+    (member index, key share) -- what COMMITTEE_SHARED_SK carries in the default set-up."""
+    global _dkg_result
+    if group_key is None:
+        raise RuntimeError("the key generation ended with the group key at infinity")
+    _dkg_result = (group_key, dict(shares))
+    _pkis.clear()
+
+
+def dkg_share(member_id: int):
+    """(member index, key share) of a committee member from the key generation, None for others."""
+    return _dkg_result[1].get(member_id) if _dkg_result is not None else None
 
 
 def hash_to_curve(h_ijt: str):

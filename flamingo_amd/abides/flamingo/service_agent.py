@@ -159,11 +159,13 @@ class SA_ServiceAgent(Agent):
         t0 = pd.Timestamp("now")
         self.user_committee = param.committee(self.num_clients)
         self.committee_threshold = int(param.fraction * len(self.user_committee))
-        # Shamir shares of the system decryption key for the committee (:261-279)
+        # Shamir shares of the system decryption key for the committee (:261-279); with
+        # configure(dkg=True) the members hold shares of a key they generated themselves, and the
+        # server has none to send
         pki = param.pki(self.num_clients)
-        shares = shamir_share(pki.system_sk, max(1, self.committee_threshold), len(self.user_committee),
-                              self.prime, rng=None)
-        for cnt, cid in enumerate(sorted(self.user_committee)):
+        shares = [] if param.dkg_on() else shamir_share(pki.system_sk, max(1, self.committee_threshold),
+                                                        len(self.user_committee), self.prime, rng=None)
+        for cnt, cid in enumerate(sorted(self.user_committee) if shares else ()):
             self.sendMessage(cid, Message({"msg": "COMMITTEE_SHARED_SK", "sender": self.id,
                                            "committee_member_idx": cnt + 1, "sk_share": shares[cnt]}),
                              tag="comm_dec_server")

@@ -192,6 +192,34 @@ def points_from_wire(buf, flags=None) -> list:
     return out
 
 
+def feldman_point(x: int, commitments):
+    """F(x) = sum_k x^k C_k by Horner's rule in the exponent, top term first: acc = x acc + C_k.
+    commitments: affine (x, y) pairs, None = infinity (a zero coefficient).  ValueError if one is
+    not a point of the curve."""
+    acc = None
+    for c in reversed(list(commitments)):
+        if c is not None and not (0 <= c[0] < P and 0 <= c[1] < P):
+            raise ValueError("coordinate outside [0, p)")    # OpenSSL would reduce it
+        if acc is not None:
+            acc = mul(x, acc) if x % N else None
+        acc = add(acc, c)
+    return acc
+
+
+def feldman_verify(share: int, x: int, commitments) -> bool:
+    """The Feldman share check of the committee's key generation (agent/dkg/SA_ClientAgent.py:219-228,
+    verify_commitment): share * G == sum_k x^k C_k.  The host twin of MaskEngine.feldman_verify, with
+    the same verdict: a share outside [0, n), a negative x and a commitment off the curve are refused;
+    infinity is a valid commitment."""
+    if not 0 <= int(share) < N or int(x) < 0:
+        return False
+    try:
+        rhs = feldman_point(int(x), commitments)
+    except (ValueError, OverflowError):
+        return False
+    return (mul(int(share)) if share else None) == rhs
+
+
 def keygen(seed: bytes):
     """Deterministic P-256 key pair from a seed (stand-in for pki_files/setup_pki.py)."""
     d = int.from_bytes(hashlib.sha512(b"flm-key" + seed).digest(), "big") % (N - 1) + 1

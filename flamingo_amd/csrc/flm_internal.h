@@ -85,6 +85,12 @@ hipError_t launch_aes_gcm_open(const uint8_t *d_keys, const uint8_t *d_nonces, i
 // d_ok[i] = ECDSA verdict of (pubkey i, digest i, signature i); d_flags n words or NULL (ecdsa_verify_kernel)
 hipError_t launch_ecdsa_verify(const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs, int n,
                                uint8_t *d_ok, uint32_t *d_flags, hipStream_t stream);
+// d_ok[i] = whether shares[i] G equals dealer row i's committed polynomial at xs[i] (feldman_verify_kernel);
+// d_commitments T x M x 64 term-major, d_dealer n indices < M or NULL (row i: dealer i % M), x_bits 1..32;
+// d_points (n x 64, that polynomial's point) and d_flags (n words) may be NULL
+hipError_t launch_feldman_verify(const uint8_t *d_commitments, int T, int M, const uint32_t *d_dealer,
+                                 const uint32_t *d_xs, int x_bits, const uint8_t *d_shares, int n, uint8_t *d_ok,
+                                 uint8_t *d_points, uint32_t *d_flags, hipStream_t stream);
 hipError_t launch_ec_finish(const uint8_t *d_base, const uint32_t *d_jac, int T, int D, int negate,
                             uint8_t *d_points_out, uint8_t *d_digests_out, uint32_t *d_flags, hipStream_t stream);
 // hash_str_to_curve of n messages (d_msgs: n x 64 bytes + d_lens), or of the decimal strings of

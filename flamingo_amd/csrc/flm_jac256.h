@@ -19,11 +19,15 @@ using Jac = JacT<Fe>;
 
 // -------------------------------------------------------------- points (a = -3)
 __device__ __forceinline__ Jac jac_inf() {
+    // X, Y, Z are assigned in this order here, in jac_dbl and in the additions: where their early returns
+    // meet, the compiler then merges the last stores of every path by value.  With Z before Y on one path
+    // it merged them by address instead and kept two 7-word arrays in scratch (ecdsa_verify_kernel 832 ->
+    // 784 bytes a lane, feldman_verify_kernel 60 -> 0).
     Jac r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.X.v[i] = r.Y.v[i] = r.Z.v[i] = 0;
     r.X = fe_const(kOne);
     r.Y = fe_const(kOne);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.Z.v[i] = 0;
     return r;
 }
 
@@ -39,9 +43,10 @@ __device__ __forceinline__ JacT<typename F::E> jac_dbl(const JacT<typename F::E>
     JacT<E> R;
     R.X = f.sub(f.sqr(alpha), beta8);
     const E yz = f.add(P.Y, P.Z);
-    R.Z = f.sub(f.sub(f.sqr(yz), gamma), delta);
+    const E z3 = f.sub(f.sub(f.sqr(yz), gamma), delta);
     const E g1 = f.sqr(gamma), g2 = f.add(g1, g1), g4 = f.add(g2, g2), g8 = f.add(g4, g4);  // 8 gamma^2
     R.Y = f.sub(f.mul(alpha, f.sub(beta4, R.X)), g8);
+    R.Z = z3;  // after Y: jac_inf says why
     return R;
 }
 __device__ __forceinline__ Jac jac_dbl(const Jac &P) { return jac_dbl(P, FeField{}); }

@@ -12,10 +12,11 @@
 // VALU integer work: no MFMA.  A small batch is one latency chain, bound by the
 // quarter-rate v_mad_u64_u32 on its critical path.
 //
-// This file holds the kernels, the cooperative formulas with their field policies, the ECDSA recoding,
-// the hash-to-curve map and the launchers.  The device libraries under them are headers that only this
-// translation unit includes: flm_fe256.h (the fields mod p and mod n, inversion, wire format),
-// flm_jac256.h (points, wNAF, odd multiples), flm_sha256.h, flm_aes128.h and flm_fe_row.h (16-lane rows).
+// This file holds the kernels, the cooperative formulas with their field policies, the ECDSA recoding
+// with the fixed-base ladder it shares with the Feldman share check, the hash-to-curve map and the
+// launchers.  The device libraries under them are headers that only this translation unit includes:
+// flm_fe256.h (the fields mod p and mod n, inversion, wire format), flm_jac256.h (points, wNAF, odd
+// multiples), flm_sha256.h, flm_aes128.h and flm_fe_row.h (16-lane rows).
 
 #include <hip/hip_runtime.h>
 
@@ -747,6 +748,27 @@ __device__ __forceinline__ void regular_next(Regular &r, int &t, bool &negative)
     negative = (d < 0) != r.neg;
 }
 
+// The fixed-base half of a regular ladder, shared by ecdsa_verify_kernel (u1 G, beside u2 Q on the same
+// doublings) and feldman_verify_kernel (s G alone): acc +- (2t+1) G as a mixed addition from kGOdd ...
+__device__ __forceinline__ Jac fixed_base_add(const Jac &acc, int t, bool negative) {
+    Fe gx, gy;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        gx.v[k] = kGOdd[t][k];
+        gy.v[k] = kGOdd[t][8 + k];
+    }
+    if (negative) gy = fe_neg(gy);
+    return jac_add_affine(acc, gx, gy);
+}
+// ... and one window's step after its four doublings: the scalar's next digit, added.  The top digit
+// (+1, weight 2^256) is fixed_base_add(acc, 0, k.neg) before the first window.
+__device__ __forceinline__ Jac fixed_base_step(const Jac &acc, Regular &k) {
+    int t;
+    bool negative;
+    regular_next(k, t, negative);
+    return fixed_base_add(acc, t, negative);
+}
+
 // pubkeys n x 64 wire bytes, digests n x 32, sigs n x 64 (r || s), all big endian.
 // ok[i] = 1 accept / 0 reject; flags[i] (may be NULL): bit 0 r or s outside [1, n-1], bit 1 Q not a
 // valid point, bit 2 u1 G + u2 Q at infinity.
@@ -785,31 +807,14 @@ __global__ __launch_bounds__(kEcThreads) void ecdsa_verify_kernel(const uint8_t 
         // top digits (+1 each, weight 2^256): acc = +-G +- Q
         Jac acc = Q;
         if (k2.neg) acc.Y = fe_neg(acc.Y);
-        {
-            Fe gx, gy;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                gx.v[k] = kGOdd[0][k];
-                gy.v[k] = kGOdd[0][8 + k];
-            }
-            if (k1.neg) gy = fe_neg(gy);
-            acc = jac_add_affine(acc, gx, gy);
-        }
+        acc = fixed_base_add(acc, 0, k1.neg);
 #pragma unroll 1
         for (int wnd = 0; wnd < 64; ++wnd) {
 #pragma unroll 1
             for (int k = 0; k < 4; ++k) acc = jac_dbl(acc);  // doubling infinity keeps Z = 0
+            acc = fixed_base_step(acc, k1);
             int t;
             bool negative;
-            regular_next(k1, t, negative);
-            Fe gx, gy;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                gx.v[k] = kGOdd[t][k];
-                gy.v[k] = kGOdd[t][8 + k];
-            }
-            if (negative) gy = fe_neg(gy);
-            acc = jac_add_affine(acc, gx, gy);
             regular_next(k2, t, negative);
             Jac A = tab[t];
             if (negative) A.Y = fe_neg(A.Y);
@@ -828,6 +833,111 @@ __global__ __launch_bounds__(kEcThreads) void ecdsa_verify_kernel(const uint8_t 
 #pragma unroll
             for (int k = 0; k < 8; ++k) r2.v[k] = rn[k];
             if (!accept && c == 0 && fe_lt_p(r2)) accept = fe_eq(fe_mul(to_mont(r2), z2), acc.X);
+        }
+    }
+    ok_out[g] = accept ? 1 : 0;
+    if (flags) flags[g] = fl;
+}
+
+// ------------------------------------------------------------- Feldman share checks (the DKG)
+// The check a committee member runs on every share a dealer sends it in the joint-Feldman key
+// generation (agent/dkg/SA_ClientAgent.py:219-228, verify_commitment):
+//     s G == F_d(x) = sum_{k<T} x^k C_{d,k}
+// with C_{d,k} = c_{d,k} G the dealer's commitments to its polynomial's coefficients.  The reference
+// evaluates the right-hand side as T full scalar multiplications by the unreduced integer x ** k; here
+// it is Horner's rule in the exponent, one lane per (dealer, x, share) row:
+//     acc = C_{d,T-1};   acc = x acc + C_{d,k}   for k = T-2 .. 0
+// where x acc is left-to-right double-and-add over exactly x_bits bits (a launch parameter, so every
+// lane runs the same number of steps): (T-1) (x_bits doublings + at most x_bits + 1 additions), 21 x
+// (6 + 7) point operations at the protocol's T = 22, x <= 60, against 22 x ~300 for the reference's form.
+// The per-bit addition is taken by branch: the lanes of a wave hold different x, so a mixed wave runs
+// the addition masked at the cost computing and selecting would have every time, and a wave whose
+// lanes all have the bit clear (the upper bits of small x under a wide x_bits, x = 0) skips it.
+// The left-hand side is the fixed-base half of the ECDSA ladder (fixed_base_step) and runs after the
+// right-hand side, whose temporaries are dead by then: the lane carries F (24 words) through it.
+// Commitments: [T][M][64] wire bytes, term-major; 64 zero bytes are the point at infinity, a valid
+// term (a zero coefficient).  A commitment with a coordinate >= p or off the curve sets flag bit 1,
+// counts as infinity in F (as ec_mul_kernel's inputs do) and fails the row.  An x >= 2^x_bits sets bit 3
+// and fails the row; F is then evaluated at its low x_bits bits.  The verdict compares projectively
+// (no inversion); points_out, when given, costs one inversion for the affine F.
+__device__ __forceinline__ bool load_commitment(const uint8_t *p, Jac &out) {
+    const uint4 *w = reinterpret_cast<const uint4 *>(p);
+    uint32_t any = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) any |= w[k].x | w[k].y | w[k].z | w[k].w;
+    const bool ok = load_point(p, out);
+    if (any == 0 || !ok) out = jac_inf();
+    return any == 0 || ok;
+}
+
+__global__ __launch_bounds__(kEcThreads) void feldman_verify_kernel(const uint8_t *__restrict__ commitments, int T,
+                                                                    int M, const uint32_t *__restrict__ dealer,
+                                                                    const uint32_t *__restrict__ xs, int x_bits,
+                                                                    const uint8_t *__restrict__ shares, int n,
+                                                                    uint8_t *__restrict__ ok_out,
+                                                                    uint8_t *__restrict__ points_out,
+                                                                    uint32_t *__restrict__ flags) {
+    __builtin_amdgcn_s_setprio(3);  // one wave's issue chain sets the time, as the other EC kernels
+    const size_t g = (size_t)blockIdx.x * kEcThreads + threadIdx.x;
+    if (g >= (size_t)n) return;
+    const uint32_t d = dealer ? dealer[g] : (uint32_t)(g % (size_t)M);
+    const uint32_t x = xs[g];
+    uint32_t fl = 0;
+    if (x_bits < 32 && (x >> x_bits) != 0) fl |= 8u;
+    const uint8_t *col = commitments + (size_t)d * 64;  // term k at col + k M 64
+
+    // right-hand side: Horner from the top term
+    Jac acc;
+    if (!load_commitment(col + (size_t)(T - 1) * M * 64, acc)) fl |= 2u;
+#pragma unroll 1
+    for (int k = T - 2; k >= 0; --k) {
+        Jac R = jac_inf();
+#pragma unroll 1
+        for (int b = x_bits - 1; b >= 0; --b) {
+            R = jac_dbl(R);  // doubling infinity keeps Z = 0
+            if ((x >> b) & 1u) R = jac_add(R, acc);
+        }
+        Jac C;
+        if (!load_commitment(col + (size_t)k * M * 64, C)) fl |= 2u;
+        acc = jac_add(R, C);
+    }
+    const bool f_inf = fe_is_zero(acc.Z);
+    if (f_inf) fl |= 4u;
+    if (points_out) {
+        Fe px = {}, py = {};
+        if (!f_inf) {
+            // (Z R)^-1 R^3 R^-1 = Z^-1 R, the Montgomery form of Z^-1 (ec_finish_kernel)
+            const Fe zi = fe_mul(fe_inv_bingcd(acc.Z), fe_const(kR3));
+            const Fe zi2 = fe_sqr(zi);
+            px = from_mont(fe_mul(acc.X, zi2));
+            py = from_mont(fe_mul(acc.Y, fe_mul(zi2, zi)));
+        }
+        store_be(points_out + g * 64, px);
+        store_be(points_out + g * 64 + 32, py);
+    }
+
+    // left-hand side: s G by the regular ladder's fixed-base half
+    const Fe s = load_be(shares + g * 32);
+    if (!sc_lt_n(s)) fl |= 1u;
+    bool accept = false;
+    if (fl == 0 || fl == 4u) {
+        Regular ks = regular_recode(s);
+        Jac L = fixed_base_add(jac_inf(), 0, ks.neg);  // the top digit: +-G
+#pragma unroll 1
+        for (int wnd = 0; wnd < 64; ++wnd) {
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) L = jac_dbl(L);
+            L = fixed_base_step(L, ks);
+        }
+        // L == F without leaving Jacobian form: X1 Z2^2 == X2 Z1^2 and Y1 Z2^3 == Y2 Z1^3; infinity
+        // equals only infinity
+        const bool l_inf = fe_is_zero(L.Z);
+        if (l_inf || f_inf) {
+            accept = l_inf && f_inf;
+        } else {
+            const Fe z1 = fe_sqr(L.Z), z2 = fe_sqr(acc.Z);
+            accept = fe_eq(fe_mul(L.X, z2), fe_mul(acc.X, z1)) &&
+                     fe_eq(fe_mul(L.Y, fe_mul(z2, acc.Z)), fe_mul(acc.Y, fe_mul(z1, L.Z)));
         }
     }
     ok_out[g] = accept ? 1 : 0;
@@ -1357,6 +1467,16 @@ hipError_t launch_ecdsa_verify(const uint8_t *d_pubkeys, const uint8_t *d_digest
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(ecdsa_verify_kernel, dim3((unsigned)(((size_t)n + kEcThreads - 1) / kEcThreads)),
                        dim3(kEcThreads), 0, stream, d_pubkeys, d_digests, d_sigs, n, d_ok, d_flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_feldman_verify(const uint8_t *d_commitments, int T, int M, const uint32_t *d_dealer,
+                                 const uint32_t *d_xs, int x_bits, const uint8_t *d_shares, int n, uint8_t *d_ok,
+                                 uint8_t *d_points, uint32_t *d_flags, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(feldman_verify_kernel, dim3((unsigned)(((size_t)n + kEcThreads - 1) / kEcThreads)),
+                       dim3(kEcThreads), 0, stream, d_commitments, T, M, d_dealer, d_xs, x_bits, d_shares, n, d_ok,
+                       d_points, d_flags);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@
 #include "flm_copy_pool.h"
 #include "flm_deal_args.h"
 #include "flm_ecdsa_args.h"
+#include "flm_feldman_args.h"
 #include "flm_internal.h"
 #include "flm_planner.h"
 
@@ -1012,7 +1013,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.5 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor) + aes_gcm_seal, aes_gcm_open"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1757,6 +1758,51 @@ int flm_ecdsa_verify(flm_ctx *ctx, const uint8_t *pubkeys, const uint8_t *digest
     FLM_HIP(ctx, flm::launch_ecdsa_verify(ctx->ec_in.as<uint8_t>(), ctx->ec_base.as<uint8_t>(),
                                           ctx->ec_scal.as<uint8_t>(), n, ctx->ec_out.as<uint8_t>(),
                                           flags_out ? ctx->ec_flags.as<uint32_t>() : nullptr, s));
+    return hc.finish();
+}
+
+int flm_feldman_verify_dev(flm_ctx *ctx, const uint8_t *d_commitments, int T, int M, const uint32_t *d_dealer,
+                           const uint32_t *d_xs, int x_bits, const uint8_t *d_shares, int n, uint8_t *d_ok_out,
+                           uint8_t *d_points_out, uint32_t *d_flags, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::feldman_verify_dims_error(T, M, x_bits, n))
+        return fail(ctx, FLM_EINVAL, "feldman verify (T=%d, M=%d, x_bits=%d, n=%d): %s", T, M, x_bits, n, why);
+    if (n == 0) return 0;
+    if (!d_commitments || !d_xs || !d_shares || !d_ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (!flm::rt::feldman_verify_aligned((uintptr_t)d_commitments, (uintptr_t)d_shares, (uintptr_t)d_points_out))
+        return fail(ctx, FLM_EINVAL, "commitments, shares and points_out must be 16-byte aligned");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_feldman_verify(d_commitments, T, M, d_dealer, d_xs, x_bits, d_shares, n, d_ok_out,
+                                            d_points_out, d_flags, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_feldman_verify(flm_ctx *ctx, const uint8_t *commitments, int T, int M, const uint32_t *dealer,
+                       const uint32_t *xs, int x_bits, const uint8_t *shares, int n, uint8_t *ok_out,
+                       uint8_t *points_out, uint32_t *flags_out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (const char *why = flm::rt::feldman_verify_dims_error(T, M, x_bits, n))
+        return fail(ctx, FLM_EINVAL, "feldman verify (T=%d, M=%d, x_bits=%d, n=%d): %s", T, M, x_bits, n, why);
+    if (n == 0) return 0;
+    if (!commitments || !xs || !shares || !ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    const int bad = flm::rt::feldman_bad_dealer(dealer, n, M);
+    if (bad >= 0) return fail(ctx, FLM_EINVAL, "dealer[%d] = %u, but there are %d dealers", bad, dealer[bad], M);
+    FLM_ON_DEVICE(ctx);
+    hipStream_t s = ctx->stream;
+    const flm::rt::FeldmanVerifyBytes nb = flm::rt::feldman_verify_bytes(T, M, n);
+    HostCopies hc(ctx, s);
+    hc.in(commitments, nb.commitments, ctx->ec_in);
+    if (dealer) hc.in(dealer, nb.dealer, ctx->ec_dig);
+    hc.in(xs, nb.xs, ctx->ec_scal);
+    hc.in(shares, nb.shares, ctx->ec_base);
+    hc.out(ok_out, nb.ok, ctx->bytes_out);
+    if (points_out) hc.out(points_out, nb.points, ctx->ec_out);
+    if (flags_out) hc.out(flags_out, nb.flags, ctx->ec_flags);
+    if (int rc = hc.begin()) return rc;
+    FLM_HIP(ctx, flm::launch_feldman_verify(ctx->ec_in.as<uint8_t>(), T, M, dealer ? ctx->ec_dig.as<uint32_t>() : nullptr,
+                                            ctx->ec_scal.as<uint32_t>(), x_bits, ctx->ec_base.as<uint8_t>(), n,
+                                            ctx->bytes_out.as<uint8_t>(), points_out ? ctx->ec_out.as<uint8_t>() : nullptr,
+                                            flags_out ? ctx->ec_flags.as<uint32_t>() : nullptr, s));
     return hc.finish();
 }
 

@@ -761,6 +761,81 @@ class MaskEngine:
         self._check(rc, "flm_ecdsa_verify_dev")
         return ok_out
 
+    def feldman_verify_wire(self, commitments_w, dealer, xs, shares_w, x_bits=None, points=False):
+        """flm_feldman_verify on wire arrays: commitments (T, M, 64) term-major wire points (64 zero bytes:
+        infinity, a valid term), dealer (n,) indices < M or None (row i: dealer i % M), xs (n,) uint32,
+        shares (n, 32) big endian -> (ok (n,) bool, flags (n,) uint32, points (n, 64) or None).
+        ok[i]: shares[i] G == sum_k xs[i]^k C[k][dealer[i]] (agent/dkg/SA_ClientAgent.py:219-228).
+        x_bits None: the bit length of max(xs), at least 1.  flags bit 0: share >= n, bit 1: a
+        commitment off the curve, bit 2: the right-hand side at infinity, bit 3: x >= 2^x_bits.  A
+        failed check is a result, not an error."""
+        cw = np.ascontiguousarray(commitments_w, np.uint8)
+        sw = np.ascontiguousarray(shares_w, np.uint8)
+        xv = np.ascontiguousarray(xs, np.uint32).reshape(-1)
+        if cw.ndim != 3 or cw.shape[2] != 64 or sw.ndim != 2 or sw.shape[1] != 32:
+            raise RuntimeError("commitments must be (T, M, 64), shares (n, 32)")
+        T, M, n = cw.shape[0], cw.shape[1], sw.shape[0]
+        if xv.shape[0] != n:
+            raise RuntimeError(f"{n} shares for {xv.shape[0]} evaluation points")
+        dv = None
+        if dealer is not None:
+            dv = np.ascontiguousarray(dealer, np.uint32).reshape(-1)
+            if dv.shape[0] != n:
+                raise RuntimeError(f"{n} shares for {dv.shape[0]} dealer indices")
+        if x_bits is None:
+            x_bits = max(1, int(xv.max()).bit_length()) if n else 1
+        ok = np.zeros(n, np.uint8)
+        fl = np.zeros(n, np.uint32)
+        pts = np.zeros((n, 64), np.uint8) if points else None
+        rc = self.lib.flm_feldman_verify(self.ctx, p_u8(cw), T, M, p_u32(dv) if dv is not None else None, p_u32(xv),
+                                         int(x_bits), p_u8(sw), n, p_u8(ok), p_u8(pts) if points else None, p_u32(fl))
+        self._check(rc, "flm_feldman_verify")
+        return ok.astype(bool), fl, pts
+
+    def feldman_verify(self, commitments, dealer, xs, shares, x_bits=None, points=False):
+        """Feldman share checks for n (dealer, x, share) rows in one launch: what crypto.feldman_verify
+        answers row by row.  commitments[k][d]: term k of dealer d, an affine (x, y) integer pair or
+        None (infinity); dealer: n indices or None (row i: dealer i % M); shares: integers (one outside
+        [0, 2^256) is refused like any share >= n).  -> the verdicts, a list of bool; with points=True
+        (verdicts, [F_d(x) as (x, y) or None])."""
+        from .crypto import points_from_wire, points_to_wire
+        T = len(commitments)
+        M = len(commitments[0]) if T else 0
+        cw = (np.stack([points_to_wire(row) for row in commitments]) if T and M else np.zeros((T, M, 64), np.uint8))
+        n = len(shares)
+        sw = np.full((n, 32), 0xFF, np.uint8)   # 2^256 - 1 >= n: refused
+        for i, s in enumerate(shares):
+            if 0 <= int(s) < (1 << 256):
+                sw[i] = np.frombuffer(int(s).to_bytes(32, "big"), np.uint8)
+        ok, fl, pts = self.feldman_verify_wire(cw, dealer, [int(v) for v in xs], sw, x_bits, points)
+        verdicts = [bool(v) for v in ok]
+        return (verdicts, points_from_wire(pts, fl)) if points else verdicts
+
+    def feldman_verify_dev(self, commitments, dealer, xs, shares, x_bits, ok_out, points_out=None, flags=None,
+                           stream=None):
+        """Device form: commitments (T, M, 64) uint8, dealer (n,) int32 or None, xs (n,) int32 (read as
+        uint32), shares (n, 32) uint8 CUDA tensors -> ok_out (n,) uint8 and, unless None, points_out
+        (n, 64) uint8 and flags (n,) int32; enqueued on `stream` (nothing staged or awaited).  A dealer
+        index >= M is not checked here."""
+        _need(commitments.dim() == 3 and shares.dim() == 2, "commitments must be (T, M, 64), shares (n, 32)")
+        T, M, n = commitments.shape[0], commitments.shape[1], shares.shape[0]
+        _dev_bytes(commitments, "commitments", 64, T * M)
+        _dev_bytes(shares, "shares", 32, n)
+        _dev_bytes(xs, "xs", 1, n, 4)
+        _dev_bytes(ok_out, "ok_out", 1, n)
+        if dealer is not None:
+            _dev_bytes(dealer, "dealer", 1, n, 4)
+        if points_out is not None:
+            _dev_bytes(points_out, "points_out", 64, n)
+        if flags is not None:
+            _dev_bytes(flags, "flags", 1, n, 4)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        rc = self.lib.flm_feldman_verify_dev(self.ctx, vp(commitments), T, M, vp(dealer), vp(xs), int(x_bits),
+                                             vp(shares), n, vp(ok_out), vp(points_out), vp(flags),
+                                             self._stream_handle(stream))
+        self._check(rc, "flm_feldman_verify_dev")
+        return ok_out
+
     def ec_combine_dev(self, c1, shares, lambdas, seeds_out, flags, points_out=None, negate: bool = True,
                        stream=None):
         """Device form: c1 (D,64), shares (T,D,64), lambdas (T,32) uint8 CUDA tensors;

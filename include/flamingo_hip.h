@@ -335,6 +335,40 @@ int flm_ecdsa_verify(flm_ctx *ctx, const uint8_t *pubkeys, const uint8_t *digest
                      uint8_t *ok_out, uint32_t *flags_out);
 int flm_ecdsa_verify_dev(flm_ctx *ctx, const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs,
                          int n, uint8_t *d_ok_out, uint32_t *d_flags, void *stream);
+/* Batched Feldman share checks, the hot path of the committee's distributed key generation:
+ * agent/dkg/SA_ClientAgent.py:219-228 (verify_commitment), which each member runs on every share
+ * it receives (:150-170) and on every share broadcast after a complaint (:195-214).  Row i holds a
+ * dealer d, an evaluation point x and a share s, and the check is
+ *   s G == F_d(x) = sum_{k<T} x^k C_{d,k}
+ * -- the reference's T scalar multiplications by the unreduced integer x ** k, here Horner's rule
+ * in the exponent: T - 1 multiplications by the x_bits-bit x plus one fixed-base multiplication.
+ * commitments: T*M*64 bytes, term-major (term k of dealer d at (k*M + d)*64), wire points: what
+ * flm_ec_mul returns for G tiled against a flm_shamir_deal `coeffs` array.  64 zero bytes are the
+ * point at infinity and a VALID commitment (a zero coefficient; the reference's EccPoint(0, 0)).
+ * dealer: n indices < M, or NULL: row i then belongs to dealer i % M, so that with
+ * xs[i] = x_{i / M} the rows are flm_shamir_deal's point-major shares_out as it stands.
+ * xs: n values, 0 allowed (the secret against C_0); x_bits in 1..32, the number of bits of x the
+ * evaluation walks, the same for every row; shares: n*32 bytes, big endian.
+ * ok_out[i] (n bytes) = 1 iff the share is < n (the group order), every commitment of the row's
+ * dealer is infinity or a point of the curve, x < 2^x_bits and s G = F_d(x); else 0.
+ * flags_out (n words, may be NULL): bit 0 share >= n, bit 1 a commitment with a coordinate >= p
+ * or off the curve (it counts as infinity in F), bit 2 F_d(x) at infinity, bit 3 x >= 2^x_bits
+ * (F is then evaluated at x mod 2^x_bits).  points_out (n*64, may be NULL): the affine wire form
+ * of F_d(x), a member's public verification key material; infinity as 64 zero bytes.  The verdict
+ * never depends on points_out.  A failed check is a result, not an error: the call returns 0.
+ * FLM_EINVAL, with nothing written, for T < 1, M < 1, x_bits outside 1..32, n < 0, n or T*M
+ * above 2^26, a NULL commitments, xs, shares or ok_out, or (host form only) a dealer index >= M;
+ * n = 0 succeeds and launches nothing.
+ * _dev: device pointers (commitments, shares and points_out 16-byte aligned), enqueued on
+ * `stream` (NULL: the null stream); nothing is staged or synchronised, and the call returns
+ * without waiting for earlier work on the stream.  A dealer index >= M is NOT checked there: the
+ * kernel would read outside `commitments`. */
+int flm_feldman_verify(flm_ctx *ctx, const uint8_t *commitments, int T, int M, const uint32_t *dealer,
+                       const uint32_t *xs, int x_bits, const uint8_t *shares, int n, uint8_t *ok_out,
+                       uint8_t *points_out, uint32_t *flags_out);
+int flm_feldman_verify_dev(flm_ctx *ctx, const uint8_t *d_commitments, int T, int M, const uint32_t *d_dealer,
+                           const uint32_t *d_xs, int x_bits, const uint8_t *d_shares, int n, uint8_t *d_ok_out,
+                           uint8_t *d_points_out, uint32_t *d_flags, void *stream);
 /* Batched scalar multiplication out[i] = scalars[i] * points[i]: the ECDH
  * (SA_ClientAgent.py:256-263), ElGamal (:434-447) and decryption-share
  * (:397-400) products, n independent elements per call. */

@@ -37,6 +37,7 @@ for _name, _res, _args in (
         ("flm_aes_gcm_seal", _int, [_vp, _u8p, _u8p, _int, _u8p, _sz, _u8p, _u8p, _sz, _u8p, _int]),
         ("flm_aes_gcm_open", _int, [_vp, _u8p, _u8p, _int, _u8p, _sz, _u8p, _u8p, _u8p, _sz, _u8p, _int]),
         ("flm_ecdsa_verify", _int, [_vp, _u8p, _u8p, _u8p, _int, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+        ("flm_feldman_verify", _int, [_vp, _u8p, _int, _int, _u32p, _u32p, _int, _u8p, _int, _u8p, _u8p, _u32p]),
         ("flm_ec_combine", _int, [_vp, _u8p, _u8p, _u8p, _int, _int, _int, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
         ("flm_group_init", _int, [ctypes.POINTER(_vp), _int, ctypes.POINTER(_int)]),
         ("flm_group_last_error", ctypes.c_char_p, [_vp]),
@@ -236,6 +237,34 @@ def ecdsa_verify(public_keys, messages, signatures):
     ok = np.zeros(n, np.uint8)
     _check(_lib.flm_ecdsa_verify(_context(), pk.ctypes.data_as(_u8p), dg.ctypes.data_as(_u8p),
                                  sg.ctypes.data_as(_u8p), n, ok.ctypes.data_as(_u8p), None))
+    return [bool(v) for v in ok]
+
+
+def feldman_verify(shares, ids, commitments_by_dealer):
+    """[verify_commitment(s_ij, commitments of dealer i) as member j sees it] for a batch
+    (agent/dkg/SA_ClientAgent.py:219-228): shares[r] * G == sum_k ids[r]**k * commitments_by_dealer[r][k],
+    one row per (share, checking member's id, that dealer's commitment list) -- a member's n rows of
+    SHARE_AND_COMMIT (:93-96, every id its own) or the broadcast shares of FORWARD_SHARE (:141-146).
+    shares: integers (the y of the (x, y) tuples); commitments: EccPoint-like objects (.x, .y), with
+    EccPoint(0, 0) the point at infinity.  A failed check is a False in the list, not an exception."""
+    n = len(shares)
+    if n == 0:
+        return []
+    if len(ids) != n or len(commitments_by_dealer) != n:
+        raise RuntimeError("one id and one commitment list per share")
+    T = len(commitments_by_dealer[0])
+    if any(len(c) != T for c in commitments_by_dealer):
+        raise RuntimeError("every commitment list must have the same length")
+    com = _be([v for k in range(T) for c in commitments_by_dealer for v in (int(c[k].x), int(c[k].y))])  # term-major
+    sh = np.full((n, 32), 0xFF, np.uint8)          # a share outside [0, 2^256): refused like any share >= n
+    for i, s in enumerate(shares):
+        if 0 <= int(s) < (1 << 256):
+            sh[i] = np.frombuffer(int(s).to_bytes(32, "big"), np.uint8)
+    xs = np.array([int(v) for v in ids], np.uint32)
+    ok = np.zeros(n, np.uint8)
+    _check(_lib.flm_feldman_verify(_context(), com.ctypes.data_as(_u8p), T, n, None, xs.ctypes.data_as(_u32p),
+                                   max(1, int(xs.max()).bit_length()), sh.ctypes.data_as(_u8p), n,
+                                   ok.ctypes.data_as(_u8p), None, None))
     return [bool(v) for v in ok]
 
 
