@@ -14,16 +14,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <tuple>
 #include <vector>
 
 #include "../../include/flamingo_hip.h"
+#include "flm_call_args.h"
 #include "flm_copy_pool.h"
-#include "flm_deal_args.h"
-#include "flm_ecdsa_args.h"
-#include "flm_feldman_args.h"
 #include "flm_internal.h"
 #include "flm_planner.h"
 
@@ -796,10 +795,25 @@ class HostCopies {
     }
     const Span *in(const void *h, size_t n, DevBuf &buf, Place p = kDevice) { return in(h, n, n, 1, buf, n, p); }
     const Span *out(void *h, size_t n, DevBuf &buf, Place p = kDevice) { return out(h, n, n, 1, buf, n, p); }
+    // A batch crypto call: every array of its list (flm_call_args.h) that is present, with the host
+    // pointer at the same position; after begin(), dev<T>(i) is where the kernel finds array i (NULL: absent).
+    void declare(const flm::rt::ArgList &l, std::initializer_list<const void *> host) {
+        assert((int)host.size() == l.n);
+        twice_ = flm::rt::names_slot_twice(l);
+        for (int i = 0; i < l.n; ++i) {
+            const flm::rt::Arg &a = l.a[i];
+            arg_[i] = !a.present ? nullptr
+                                 : add(const_cast<void *>(host.begin()[i]), a.bytes, a.bytes, 1, ctx_->*kSlot[a.slot], a.bytes,
+                                       a.is_out, a.in_place ? kMayRunInPlace : kDevice);
+        }
+    }
+    template <class T>
+    T *dev(int i) const { return arg_[i] ? arg_[i]->as<T>() : nullptr; }
     // Lays the call out, grows the bounce buffer and the DevBufs, copies the inputs into pinned memory
     // and enqueues their DMAs (large ones stream through the staging ring at once).
     int begin() {
         if (n_ > kMaxSpans) return fail(ctx_, FLM_EINVAL, "host copies: more than %d arrays declared", kMaxSpans);
+        if (twice_) return fail(ctx_, FLM_EINVAL, "host copies: two arrays of the call share a scratch buffer");
         const size_t total = flm::rt::host_layout(lay_, n_);
         if (total > ctx_->bounce_cap) {
             if (ctx_->bounce) (void)hipHostFree(ctx_->bounce);  // waits for the device: nothing reads it after
@@ -853,7 +867,11 @@ class HostCopies {
     void hand_over() { open_ = false; }
 
   private:
-    static constexpr int kMaxSpans = 8;
+    static constexpr int kMaxSpans = flm::rt::kMaxArgs;
+    // flm::rt::Slot -> the context's buffer of that name
+    static constexpr DevBuf flm_ctx::*kSlot[flm::rt::kSlots] = {
+        &flm_ctx::ec_in,  &flm_ctx::ec_base,  &flm_ctx::ec_scal,  &flm_ctx::ec_out,
+        &flm_ctx::ec_dig, &flm_ctx::ec_flags, &flm_ctx::bytes_in, &flm_ctx::bytes_out};
     struct Decl : Span {  // a declaration behind its handle; its width, rows and route are lay_[i], as host_layout takes them
         void *host;
         size_t h_pitch, d_pitch;
@@ -920,7 +938,9 @@ class HostCopies {
     hipStream_t s_;
     Decl spans_[kMaxSpans + 1];
     flm::rt::HostSpan lay_[kMaxSpans + 1];  // spans_[i]'s width, rows and may-run-in-place; its route after begin()
+    const Span *arg_[kMaxSpans] = {};  // declare()'s arrays by their place in the list
     int n_ = 0;
+    bool twice_ = false;  // declare()'s list names a scratch buffer twice: begin() refuses the call
     bool open_ = false;  // begin() has queued work or handed out in-place memory, finish() has not waited yet
 };
 
@@ -1426,8 +1446,32 @@ int flm_last_plan(const flm_ctx *ctx, int *items, int *tile_slots, int *atomics,
 // ------------------------------------------------------------------ P-256
 static int ec_dims(flm_ctx *ctx, int T, int D) {
     if (T < 0 || D < 0) return fail(ctx, FLM_EINVAL, "negative batch size (T=%d, D=%d)", T, D);
-    if ((size_t)T * (size_t)D > (size_t)1 << 26) return fail(ctx, FLM_EINVAL, "batch too large (T*D=%zu)", (size_t)T * D);
+    if ((size_t)T * (size_t)D > flm::rt::kMaxRows) return fail(ctx, FLM_EINVAL, "batch too large (T*D=%zu)", (size_t)T * D);
     return 0;
+}
+
+// The other calls' size rules (flm_call_args.h) as refusals: the _dev form's first check, and the host
+// form's before it reads an array or returns for an empty batch.
+static int shamir_deal_dims(flm_ctx *ctx, int T, int M, int C) {
+    const char *why = flm::rt::shamir_deal_dims_error(T, M, C);
+    return why ? fail(ctx, FLM_EINVAL, "shamir deal (T=%d, M=%d, C=%d): %s", T, M, C, why) : 0;
+}
+static int aes_gcm_xor_dims(flm_ctx *ctx, int nonce_len, size_t len, int n) {
+    const char *why = flm::rt::aes_gcm_dims_error(nonce_len, len, n);
+    return why ? fail(ctx, FLM_EINVAL, "aes gcm xor (nonce_len=%d, len=%zu, n=%d): %s", nonce_len, len, n, why) : 0;
+}
+static int aes_gcm_auth_dims(flm_ctx *ctx, const char *what, int nonce_len, size_t aad_len, size_t len, int n) {
+    const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n);
+    return why ? fail(ctx, FLM_EINVAL, "%s (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", what, nonce_len, aad_len, len, n, why)
+               : 0;
+}
+static int ecdsa_verify_dims(flm_ctx *ctx, int n) {
+    const char *why = flm::rt::ecdsa_verify_dims_error(n);
+    return why ? fail(ctx, FLM_EINVAL, "ecdsa verify (n=%d): %s", n, why) : 0;
+}
+static int feldman_verify_dims(flm_ctx *ctx, int T, int M, int x_bits, int n) {
+    const char *why = flm::rt::feldman_verify_dims_error(T, M, x_bits, n);
+    return why ? fail(ctx, FLM_EINVAL, "feldman verify (T=%d, M=%d, x_bits=%d, n=%d): %s", T, M, x_bits, n, why) : 0;
 }
 
 // Cooperative scalar multiplication when the whole batch fits one pass of the device -- the
@@ -1478,19 +1522,13 @@ int flm_ec_combine(flm_ctx *ctx, const uint8_t *c1, const uint8_t *shares, const
     hipStream_t s = ctx->stream;
     std::vector<uint32_t> fl(D);
     HostCopies hc(ctx, s);
-    hc.in(shares, (size_t)T * D * 64, ctx->ec_in);
-    hc.in(lambdas, (size_t)T * 32, ctx->ec_scal);
-    if (c1) hc.in(c1, (size_t)D * 64, ctx->ec_base);
-    hc.out(fl.data(), (size_t)D * 4, ctx->ec_flags);
+    hc.declare(flm::rt::ec_combine_args(T, D, c1, points_out, seeds_out), {shares, lambdas, c1, fl.data(), points_out, seeds_out});
     // the kernel writes points and digests whether or not the caller takes them back
-    if (points_out) hc.out(points_out, (size_t)D * 64, ctx->ec_out);
-    else FLM_HIP(ctx, ctx->ec_out.reserve((size_t)D * 64));
-    if (seeds_out) hc.out(seeds_out, (size_t)D * 32, ctx->ec_dig);
-    else FLM_HIP(ctx, ctx->ec_dig.reserve((size_t)D * 32));
+    if (!points_out) FLM_HIP(ctx, ctx->ec_out.reserve((size_t)D * 64));
+    if (!seeds_out) FLM_HIP(ctx, ctx->ec_dig.reserve((size_t)D * 32));
     if (int rc = hc.begin()) return rc;
-    if (int rc = flm_ec_combine_dev(ctx, c1 ? ctx->ec_base.as<uint8_t>() : nullptr, ctx->ec_in.as<uint8_t>(),
-                                    ctx->ec_scal.as<uint8_t>(), T, D, negate, ctx->ec_out.as<uint8_t>(),
-                                    ctx->ec_dig.as<uint8_t>(), ctx->ec_flags.as<uint32_t>(), s))
+    if (int rc = flm_ec_combine_dev(ctx, hc.dev<uint8_t>(2), hc.dev<uint8_t>(0), hc.dev<uint8_t>(1), T, D, negate,
+                                    ctx->ec_out.as<uint8_t>(), ctx->ec_dig.as<uint8_t>(), hc.dev<uint32_t>(3), s))
         return rc;
     if (int rc = hc.finish()) return rc;
     if (flags_out) std::copy(fl.begin(), fl.end(), flags_out);
@@ -1555,22 +1593,18 @@ int flm_shamir_combine(flm_ctx *ctx, const uint8_t *shares, const uint8_t *lambd
     if (M == 0) return 0;
     if (!seeds_out || (T > 0 && (!shares || !lambdas))) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
-    hipStream_t s = ctx->stream;
-    HostCopies hc(ctx, s);
-    hc.in(shares, (size_t)T * M * 32, ctx->ec_in);
-    hc.in(lambdas, (size_t)T * 32, ctx->ec_scal);
-    hc.out(seeds_out, (size_t)M * 32, ctx->ec_dig);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::shamir_combine_args(T, M), {shares, lambdas, seeds_out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_shamir_combine(ctx->ec_in.as<uint8_t>(), ctx->ec_scal.as<uint8_t>(), T, M,
-                                            ctx->ec_dig.as<uint8_t>(), s));
+    // launched here, not through flm_shamir_combine_dev: through it this call measured over its bound
+    FLM_HIP(ctx, flm::launch_shamir_combine(hc.dev<uint8_t>(0), hc.dev<uint8_t>(1), T, M, hc.dev<uint8_t>(2), ctx->stream));
     return hc.finish();
 }
 
 int flm_shamir_deal_dev(flm_ctx *ctx, const uint8_t *d_coeffs, int T, int M, const uint32_t *d_xs, int C,
                         uint8_t *d_shares_out, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::shamir_deal_dims_error(T, M, C))
-        return fail(ctx, FLM_EINVAL, "shamir deal (T=%d, M=%d, C=%d): %s", T, M, C, why);
+    if (int rc = shamir_deal_dims(ctx, T, M, C)) return rc;
     if (M == 0) return 0;
     if (!d_coeffs || !d_xs || !d_shares_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (((uintptr_t)d_coeffs | (uintptr_t)d_shares_out) & 15)
@@ -1583,31 +1617,25 @@ int flm_shamir_deal_dev(flm_ctx *ctx, const uint8_t *d_coeffs, int T, int M, con
 int flm_shamir_deal(flm_ctx *ctx, const uint8_t *coeffs, int T, int M, const uint32_t *xs, int C,
                     uint8_t *shares_out) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::shamir_deal_dims_error(T, M, C))
-        return fail(ctx, FLM_EINVAL, "shamir deal (T=%d, M=%d, C=%d): %s", T, M, C, why);
+    if (int rc = shamir_deal_dims(ctx, T, M, C)) return rc;
     if (!xs) return fail(ctx, FLM_EINVAL, "NULL argument");
     const int zero = flm::rt::shamir_deal_zero_x(xs, C);
     if (zero >= 0) return fail(ctx, FLM_EINVAL, "xs[%d] is 0: a share at x = 0 would be the secret itself", zero);
     if (M == 0) return 0;
     if (!coeffs || !shares_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
-    hipStream_t s = ctx->stream;
-    const flm::rt::ShamirDealBytes nb = flm::rt::shamir_deal_bytes(T, M, C);
-    HostCopies hc(ctx, s);
-    hc.in(coeffs, nb.coeffs, ctx->ec_in);
-    hc.in(xs, nb.xs, ctx->ec_scal);
-    hc.out(shares_out, nb.shares, ctx->ec_out);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::shamir_deal_args(T, M, C), {coeffs, xs, shares_out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_shamir_deal(ctx->ec_in.as<uint8_t>(), T, M, ctx->ec_scal.as<uint32_t>(), C,
-                                         ctx->ec_out.as<uint8_t>(), s));
+    if (int rc = flm_shamir_deal_dev(ctx, hc.dev<uint8_t>(0), T, M, hc.dev<uint32_t>(1), C, hc.dev<uint8_t>(2), ctx->stream))
+        return rc;
     return hc.finish();
 }
 
 int flm_aes_gcm_xor_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_nonces, int nonce_len,
                         const uint8_t *d_in, uint8_t *d_out, size_t len, int n, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::aes_gcm_dims_error(nonce_len, len, n))
-        return fail(ctx, FLM_EINVAL, "aes gcm xor (nonce_len=%d, len=%zu, n=%d): %s", nonce_len, len, n, why);
+    if (int rc = aes_gcm_xor_dims(ctx, nonce_len, len, n)) return rc;
     if (n == 0) return 0;
     if (!d_keys || !d_nonces || !d_in || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
@@ -1619,22 +1647,17 @@ int flm_aes_gcm_xor_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_no
 int flm_aes_gcm_xor(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, int nonce_len, const uint8_t *in,
                     uint8_t *out, size_t len, int n) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::aes_gcm_dims_error(nonce_len, len, n))
-        return fail(ctx, FLM_EINVAL, "aes gcm xor (nonce_len=%d, len=%zu, n=%d): %s", nonce_len, len, n, why);
+    if (int rc = aes_gcm_xor_dims(ctx, nonce_len, len, n)) return rc;
     if (n == 0) return 0;
     if (!keys || !nonces || !in || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
-    hipStream_t s = ctx->stream;
-    const flm::rt::AesGcmBytes nb = flm::rt::aes_gcm_bytes(nonce_len, len, n);
-    HostCopies hc(ctx, s);
-    hc.in(keys, nb.keys, ctx->ec_scal);
-    hc.in(nonces, nb.nonces, ctx->ec_base);
-    // read and written in place in the bounce buffer when it fits (flm_chacha20_xor); in == out is fine
-    const HostCopies::Span *hi = hc.in(in, nb.data, ctx->bytes_in, HostCopies::kMayRunInPlace);
-    const HostCopies::Span *ho = hc.out(out, nb.data, ctx->bytes_out, HostCopies::kMayRunInPlace);
+    HostCopies hc(ctx, ctx->stream);
+    // in and out are read and written in place in the bounce buffer when they fit (flm_chacha20_xor)
+    hc.declare(flm::rt::aes_gcm_xor_args(nonce_len, len, n), {keys, nonces, in, out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_aes_gcm_xor(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len,
-                                         hi->as<const uint8_t>(), ho->as<uint8_t>(), (uint32_t)len, n, s));
+    if (int rc = flm_aes_gcm_xor_dev(ctx, hc.dev<uint8_t>(0), hc.dev<uint8_t>(1), nonce_len, hc.dev<uint8_t>(2),
+                                     hc.dev<uint8_t>(3), len, n, ctx->stream))
+        return rc;
     return hc.finish();
 }
 
@@ -1642,8 +1665,7 @@ int flm_aes_gcm_seal_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_n
                          const uint8_t *d_aad, size_t aad_len, const uint8_t *d_in, uint8_t *d_out, size_t len,
                          uint8_t *d_tags_out, int n, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n))
-        return fail(ctx, FLM_EINVAL, "aes gcm seal (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", nonce_len, aad_len, len, n, why);
+    if (int rc = aes_gcm_auth_dims(ctx, "aes gcm seal", nonce_len, aad_len, len, n)) return rc;
     if (n == 0) return 0;
     if (const char *why = flm::rt::aes_gcm_auth_null_error(d_keys, d_nonces, d_aad, aad_len, d_in, d_out, len, d_tags_out, nullptr, false))
         return fail(ctx, FLM_EINVAL, "aes gcm seal: %s", why);
@@ -1657,8 +1679,7 @@ int flm_aes_gcm_open_dev(flm_ctx *ctx, const uint8_t *d_keys, const uint8_t *d_n
                          const uint8_t *d_aad, size_t aad_len, const uint8_t *d_in, const uint8_t *d_tags,
                          uint8_t *d_out, size_t len, uint8_t *d_ok_out, int n, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n))
-        return fail(ctx, FLM_EINVAL, "aes gcm open (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", nonce_len, aad_len, len, n, why);
+    if (int rc = aes_gcm_auth_dims(ctx, "aes gcm open", nonce_len, aad_len, len, n)) return rc;
     if (n == 0) return 0;
     if (const char *why = flm::rt::aes_gcm_auth_null_error(d_keys, d_nonces, d_aad, aad_len, d_in, d_out, len, d_tags, d_ok_out, true))
         return fail(ctx, FLM_EINVAL, "aes gcm open: %s", why);
@@ -1674,40 +1695,22 @@ int aes_gcm_auth_host(flm_ctx *ctx, const char *what, const uint8_t *keys, const
                       const uint8_t *aad, size_t aad_len, const uint8_t *in, uint8_t *out, size_t len, uint8_t *tags,
                       uint8_t *ok_out, bool open, int n) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::aes_gcm_auth_dims_error(nonce_len, aad_len, len, n))
-        return fail(ctx, FLM_EINVAL, "%s (nonce_len=%d, aad_len=%zu, len=%zu, n=%d): %s", what, nonce_len, aad_len, len, n, why);
+    if (int rc = aes_gcm_auth_dims(ctx, what, nonce_len, aad_len, len, n)) return rc;
     if (n == 0) return 0;
     if (const char *why = flm::rt::aes_gcm_auth_null_error(keys, nonces, aad, aad_len, in, out, len, tags, ok_out, open))
         return fail(ctx, FLM_EINVAL, "%s: %s", what, why);
     FLM_ON_DEVICE(ctx);
     hipStream_t s = ctx->stream;
-    const flm::rt::AesGcmAuthBytes nb = flm::rt::aes_gcm_auth_bytes(nonce_len, aad_len, len, n);
     HostCopies hc(ctx, s);
-    hc.in(keys, nb.keys, ctx->ec_scal);
-    hc.in(nonces, nb.nonces, ctx->ec_base);
-    if (aad_len) hc.in(aad, nb.aad, ctx->ec_in);
-    const HostCopies::Span *hi = nullptr, *ho = nullptr;
-    if (len) {
-        hi = hc.in(in, nb.data, ctx->bytes_in, HostCopies::kMayRunInPlace);
-        ho = hc.out(out, nb.data, ctx->bytes_out, HostCopies::kMayRunInPlace);
-    }
-    if (open) {
-        hc.in(tags, nb.tags, ctx->ec_dig);
-        hc.out(ok_out, nb.ok, ctx->ec_out);
-    } else {
-        hc.out(tags, nb.tags, ctx->ec_dig);
-    }
+    hc.declare(flm::rt::aes_gcm_auth_args(nonce_len, aad_len, len, n, open), {keys, nonces, aad, in, out, tags, ok_out});
     if (int rc = hc.begin()) return rc;
-    const uint8_t *d_aad = aad_len ? ctx->ec_in.as<uint8_t>() : nullptr;
-    const uint8_t *d_in = len ? hi->as<const uint8_t>() : nullptr;
-    uint8_t *d_out = len ? ho->as<uint8_t>() : nullptr;
-    if (open)
-        FLM_HIP(ctx, flm::launch_aes_gcm_open(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len, d_aad,
-                                              (uint32_t)aad_len, d_in, ctx->ec_dig.as<uint8_t>(), d_out, (uint32_t)len,
-                                              ctx->ec_out.as<uint8_t>(), n, s));
-    else
-        FLM_HIP(ctx, flm::launch_aes_gcm_seal(ctx->ec_scal.as<uint8_t>(), ctx->ec_base.as<uint8_t>(), nonce_len, d_aad,
-                                              (uint32_t)aad_len, d_in, d_out, (uint32_t)len, ctx->ec_dig.as<uint8_t>(), n, s));
+    const uint8_t *d_keys = hc.dev<uint8_t>(0), *d_nonces = hc.dev<uint8_t>(1), *d_aad = hc.dev<uint8_t>(2);
+    const uint8_t *d_in = hc.dev<uint8_t>(3);
+    uint8_t *d_out = hc.dev<uint8_t>(4), *d_tags = hc.dev<uint8_t>(5);
+    if (int rc = open ? flm_aes_gcm_open_dev(ctx, d_keys, d_nonces, nonce_len, d_aad, aad_len, d_in, d_tags, d_out, len,
+                                             hc.dev<uint8_t>(6), n, s)
+                      : flm_aes_gcm_seal_dev(ctx, d_keys, d_nonces, nonce_len, d_aad, aad_len, d_in, d_out, len, d_tags, n, s))
+        return rc;
     return hc.finish();
 }
 }  // namespace
@@ -1728,7 +1731,7 @@ int flm_aes_gcm_open(flm_ctx *ctx, const uint8_t *keys, const uint8_t *nonces, i
 int flm_ecdsa_verify_dev(flm_ctx *ctx, const uint8_t *d_pubkeys, const uint8_t *d_digests, const uint8_t *d_sigs,
                          int n, uint8_t *d_ok_out, uint32_t *d_flags, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::ecdsa_verify_dims_error(n)) return fail(ctx, FLM_EINVAL, "ecdsa verify (n=%d): %s", n, why);
+    if (int rc = ecdsa_verify_dims(ctx, n)) return rc;
     if (n == 0) return 0;
     if (!d_pubkeys || !d_digests || !d_sigs || !d_ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (!flm::rt::ecdsa_verify_aligned((uintptr_t)d_pubkeys, (uintptr_t)d_digests, (uintptr_t)d_sigs))
@@ -1742,22 +1745,16 @@ int flm_ecdsa_verify_dev(flm_ctx *ctx, const uint8_t *d_pubkeys, const uint8_t *
 int flm_ecdsa_verify(flm_ctx *ctx, const uint8_t *pubkeys, const uint8_t *digests, const uint8_t *sigs, int n,
                      uint8_t *ok_out, uint32_t *flags_out) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::ecdsa_verify_dims_error(n)) return fail(ctx, FLM_EINVAL, "ecdsa verify (n=%d): %s", n, why);
+    if (int rc = ecdsa_verify_dims(ctx, n)) return rc;
     if (n == 0) return 0;
     if (!pubkeys || !digests || !sigs || !ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
-    hipStream_t s = ctx->stream;
-    const flm::rt::EcdsaVerifyBytes nb = flm::rt::ecdsa_verify_bytes(n);
-    HostCopies hc(ctx, s);
-    hc.in(pubkeys, nb.pubkeys, ctx->ec_in);
-    hc.in(digests, nb.digests, ctx->ec_base);
-    hc.in(sigs, nb.sigs, ctx->ec_scal);
-    hc.out(ok_out, nb.ok, ctx->ec_out);
-    if (flags_out) hc.out(flags_out, nb.flags, ctx->ec_flags);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::ecdsa_verify_args(n, flags_out), {pubkeys, digests, sigs, ok_out, flags_out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_ecdsa_verify(ctx->ec_in.as<uint8_t>(), ctx->ec_base.as<uint8_t>(),
-                                          ctx->ec_scal.as<uint8_t>(), n, ctx->ec_out.as<uint8_t>(),
-                                          flags_out ? ctx->ec_flags.as<uint32_t>() : nullptr, s));
+    if (int rc = flm_ecdsa_verify_dev(ctx, hc.dev<uint8_t>(0), hc.dev<uint8_t>(1), hc.dev<uint8_t>(2), n, hc.dev<uint8_t>(3),
+                                      hc.dev<uint32_t>(4), ctx->stream))
+        return rc;
     return hc.finish();
 }
 
@@ -1765,8 +1762,7 @@ int flm_feldman_verify_dev(flm_ctx *ctx, const uint8_t *d_commitments, int T, in
                            const uint32_t *d_xs, int x_bits, const uint8_t *d_shares, int n, uint8_t *d_ok_out,
                            uint8_t *d_points_out, uint32_t *d_flags, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::feldman_verify_dims_error(T, M, x_bits, n))
-        return fail(ctx, FLM_EINVAL, "feldman verify (T=%d, M=%d, x_bits=%d, n=%d): %s", T, M, x_bits, n, why);
+    if (int rc = feldman_verify_dims(ctx, T, M, x_bits, n)) return rc;
     if (n == 0) return 0;
     if (!d_commitments || !d_xs || !d_shares || !d_ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (!flm::rt::feldman_verify_aligned((uintptr_t)d_commitments, (uintptr_t)d_shares, (uintptr_t)d_points_out))
@@ -1781,28 +1777,20 @@ int flm_feldman_verify(flm_ctx *ctx, const uint8_t *commitments, int T, int M, c
                        const uint32_t *xs, int x_bits, const uint8_t *shares, int n, uint8_t *ok_out,
                        uint8_t *points_out, uint32_t *flags_out) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (const char *why = flm::rt::feldman_verify_dims_error(T, M, x_bits, n))
-        return fail(ctx, FLM_EINVAL, "feldman verify (T=%d, M=%d, x_bits=%d, n=%d): %s", T, M, x_bits, n, why);
+    if (int rc = feldman_verify_dims(ctx, T, M, x_bits, n)) return rc;
     if (n == 0) return 0;
     if (!commitments || !xs || !shares || !ok_out) return fail(ctx, FLM_EINVAL, "NULL argument");
     const int bad = flm::rt::feldman_bad_dealer(dealer, n, M);
     if (bad >= 0) return fail(ctx, FLM_EINVAL, "dealer[%d] = %u, but there are %d dealers", bad, dealer[bad], M);
     FLM_ON_DEVICE(ctx);
-    hipStream_t s = ctx->stream;
-    const flm::rt::FeldmanVerifyBytes nb = flm::rt::feldman_verify_bytes(T, M, n);
-    HostCopies hc(ctx, s);
-    hc.in(commitments, nb.commitments, ctx->ec_in);
-    if (dealer) hc.in(dealer, nb.dealer, ctx->ec_dig);
-    hc.in(xs, nb.xs, ctx->ec_scal);
-    hc.in(shares, nb.shares, ctx->ec_base);
-    hc.out(ok_out, nb.ok, ctx->bytes_out);
-    if (points_out) hc.out(points_out, nb.points, ctx->ec_out);
-    if (flags_out) hc.out(flags_out, nb.flags, ctx->ec_flags);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::feldman_verify_args(T, M, n, dealer, points_out, flags_out),
+               {commitments, dealer, xs, shares, ok_out, points_out, flags_out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_feldman_verify(ctx->ec_in.as<uint8_t>(), T, M, dealer ? ctx->ec_dig.as<uint32_t>() : nullptr,
-                                            ctx->ec_scal.as<uint32_t>(), x_bits, ctx->ec_base.as<uint8_t>(), n,
-                                            ctx->bytes_out.as<uint8_t>(), points_out ? ctx->ec_out.as<uint8_t>() : nullptr,
-                                            flags_out ? ctx->ec_flags.as<uint32_t>() : nullptr, s));
+    if (int rc = flm_feldman_verify_dev(ctx, hc.dev<uint8_t>(0), T, M, hc.dev<uint32_t>(1), hc.dev<uint32_t>(2), x_bits,
+                                        hc.dev<uint8_t>(3), n, hc.dev<uint8_t>(4), hc.dev<uint8_t>(5), hc.dev<uint32_t>(6),
+                                        ctx->stream))
+        return rc;
     return hc.finish();
 }
 
@@ -1816,17 +1804,13 @@ int flm_ec_mul(flm_ctx *ctx, const uint8_t *points, const uint8_t *scalars, int 
     hipStream_t s = ctx->stream;
     std::vector<uint32_t> fl(n);
     HostCopies hc(ctx, s);
-    hc.in(points, (size_t)n * 64, ctx->ec_in);
-    hc.in(scalars, (size_t)n * 32, ctx->ec_scal);
-    hc.out(fl.data(), (size_t)n * 4, ctx->ec_flags);
-    hc.out(out, (size_t)n * 64, ctx->ec_out);
+    hc.declare(flm::rt::ec_mul_args(n), {points, scalars, fl.data(), out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, hipMemsetAsync(ctx->ec_flags.p, 0, (size_t)n * 4, s));
-    FLM_HIP(ctx, flm::launch_ec_mul(ctx->ec_in.as<uint8_t>(), ctx->ec_scal.as<uint8_t>(), 1, 1, n,
-                                    ctx->ec_jac.as<uint32_t>(), ctx->ec_flags.as<uint32_t>(), s,
+    uint32_t *d_flags = hc.dev<uint32_t>(2);
+    FLM_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)n * 4, s));
+    FLM_HIP(ctx, flm::launch_ec_mul(hc.dev<uint8_t>(0), hc.dev<uint8_t>(1), 1, 1, n, ctx->ec_jac.as<uint32_t>(), d_flags, s,
                                     ctx->tune_ec_threads, ctx->tune_ec_waves, ec_coop(ctx, (size_t)n)));
-    FLM_HIP(ctx, flm::launch_ec_finish(nullptr, ctx->ec_jac.as<uint32_t>(), 1, n, 0, ctx->ec_out.as<uint8_t>(),
-                                       nullptr, ctx->ec_flags.as<uint32_t>(), s));
+    FLM_HIP(ctx, flm::launch_ec_finish(nullptr, ctx->ec_jac.as<uint32_t>(), 1, n, 0, hc.dev<uint8_t>(3), nullptr, d_flags, s));
     if (int rc = hc.finish()) return rc;
     if (flags_out) std::copy(fl.begin(), fl.end(), flags_out);
     for (int i = 0; i < n; ++i)
@@ -1841,22 +1825,13 @@ static int h2c_run(flm_ctx *ctx, const uint8_t *uniform, const uint8_t *msgs, co
     hipStream_t s = ctx->stream;
     std::vector<uint32_t> fl(n);
     HostCopies hc(ctx, s);
-    if (uniform) {
-        hc.in(uniform, (size_t)n * 96, ctx->ec_in);
-    } else if (msgs) {
-        hc.in(msgs, (size_t)n * 64, ctx->ec_in);
-        hc.in(lens, (size_t)n * 4, ctx->ec_scal);
-    }
-    hc.out(fl.data(), (size_t)n * 4, ctx->ec_flags);
-    hc.out(out, (size_t)n * 64, ctx->ec_out);
+    hc.declare(flm::rt::h2c_args(n, uniform, msgs), {uniform ? uniform : msgs, lens, fl.data(), out});
     if (int rc = hc.begin()) return rc;
     if (uniform)
-        FLM_HIP(ctx, flm::launch_h2c_from_uniform(ctx->ec_in.as<uint8_t>(), n, ctx->ec_out.as<uint8_t>(),
-                                                  ctx->ec_flags.as<uint32_t>(), s));
+        FLM_HIP(ctx, flm::launch_h2c_from_uniform(hc.dev<uint8_t>(0), n, hc.dev<uint8_t>(3), hc.dev<uint32_t>(2), s));
     else
-        FLM_HIP(ctx, flm::launch_hash_to_curve(msgs ? ctx->ec_in.as<uint8_t>() : nullptr,
-                                               msgs ? ctx->ec_scal.as<uint32_t>() : nullptr, v0, n,
-                                               ctx->ec_out.as<uint8_t>(), ctx->ec_flags.as<uint32_t>(), s));
+        FLM_HIP(ctx, flm::launch_hash_to_curve(hc.dev<uint8_t>(0), hc.dev<uint32_t>(1), v0, n, hc.dev<uint8_t>(3),
+                                               hc.dev<uint32_t>(2), s));
     if (int rc = hc.finish()) return rc;
     if (flags_out) std::copy(fl.begin(), fl.end(), flags_out);
     for (int i = 0; i < n; ++i)

@@ -69,6 +69,11 @@ def _dev_bytes(t, name: str, cols: int, rows: int, dtype_bytes: int = 1):
           f"{name} must hold >= {rows} x {cols} elements, got {tuple(t.shape)}")
 
 
+def _vp(t) -> ctypes.c_void_p:
+    """A CUDA tensor's address for a *_dev call; None: a NULL pointer."""
+    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+
 def _dev_rows(rows, L: int) -> int:
     """Row pitch (elements) of an (N, >= L) 32-bit CUDA tensor whose rows may be a strided view."""
     _need(rows.is_cuda and rows.dim() == 2 and rows.element_size() == 4, "rows must be a 2-D 32-bit CUDA tensor")
@@ -582,14 +587,8 @@ class MaskEngine:
         """AES.new(key, AES.MODE_GCM, nonce=nonce).encrypt(data) with the tag dropped, for n messages
         (flm_aes_gcm_xor; SA_ClientAgent.py:227-244, and the decryption of :402-420 -- the same XOR).
         keys (n, 16), nonces (n, 12 or 16), data (n, len) uint8 with 1 <= len <= 256 -> (n, len)."""
-        k = np.ascontiguousarray(keys, np.uint8)
-        nc = np.ascontiguousarray(nonces, np.uint8)
-        d = np.ascontiguousarray(data, np.uint8)
-        if k.ndim != 2 or k.shape[1] != 16 or nc.ndim != 2 or d.ndim != 2:
-            raise RuntimeError("keys must be (n, 16), nonces (n, nonce_len), data (n, len)")
+        k, nc, _, d = self._gcm_rows(keys, nonces, None, data)
         n = k.shape[0]
-        if nc.shape[0] != n or d.shape[0] != n:
-            raise RuntimeError(f"{n} keys for {nc.shape[0]} nonces and {d.shape[0]} messages")
         out = np.zeros_like(d)
         rc = self.lib.flm_aes_gcm_xor(self.ctx, p_u8(k), p_u8(nc), nc.shape[1], p_u8(d), p_u8(out), d.shape[1], n)
         self._check(rc, "flm_aes_gcm_xor")
@@ -608,8 +607,7 @@ class MaskEngine:
         _dev_bytes(out, "out", ln, n)
         _need(keys.shape[0] == n and nonces.shape[0] == n, f"{keys.shape[0]} keys and {nonces.shape[0]} nonces "
               f"for {n} messages")
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        rc = self.lib.flm_aes_gcm_xor_dev(self.ctx, vp(keys), vp(nonces), nonces.shape[1], vp(data), vp(out), ln, n,
+        rc = self.lib.flm_aes_gcm_xor_dev(self.ctx, _vp(keys), _vp(nonces), nonces.shape[1], _vp(data), _vp(out), ln, n,
                                           self._stream_handle(stream))
         self._check(rc, "flm_aes_gcm_xor_dev")
         return out
@@ -687,9 +685,8 @@ class MaskEngine:
         `data` itself (the default: in place); enqueued on `stream`, nothing staged or awaited."""
         out = data if out is None else out
         n, ln, aad, al = self._gcm_dev_args(keys, nonces, aad, data, out, tags_out)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
-        rc = self.lib.flm_aes_gcm_seal_dev(self.ctx, vp(keys), vp(nonces), nonces.shape[1], vp(aad), al, vp(data),
-                                           vp(out), ln, vp(tags_out), n, self._stream_handle(stream))
+        rc = self.lib.flm_aes_gcm_seal_dev(self.ctx, _vp(keys), _vp(nonces), nonces.shape[1], _vp(aad), al, _vp(data),
+                                           _vp(out), ln, _vp(tags_out), n, self._stream_handle(stream))
         self._check(rc, "flm_aes_gcm_seal_dev")
         return out, tags_out
 
@@ -698,9 +695,8 @@ class MaskEngine:
         out = data if out is None else out
         n, ln, aad, al = self._gcm_dev_args(keys, nonces, aad, data, out, tags)
         _dev_bytes(ok_out, "ok_out", 1, n)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
-        rc = self.lib.flm_aes_gcm_open_dev(self.ctx, vp(keys), vp(nonces), nonces.shape[1], vp(aad), al, vp(data),
-                                           vp(tags), vp(out), ln, vp(ok_out), n, self._stream_handle(stream))
+        rc = self.lib.flm_aes_gcm_open_dev(self.ctx, _vp(keys), _vp(nonces), nonces.shape[1], _vp(aad), al, _vp(data),
+                                           _vp(tags), _vp(out), ln, _vp(ok_out), n, self._stream_handle(stream))
         self._check(rc, "flm_aes_gcm_open_dev")
         return out, ok_out
 
@@ -755,8 +751,7 @@ class MaskEngine:
         _dev_bytes(ok_out, "ok_out", 1, n)
         if flags is not None:
             _dev_bytes(flags, "flags", 1, n, 4)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
-        rc = self.lib.flm_ecdsa_verify_dev(self.ctx, vp(pubkeys), vp(digests), vp(sigs), n, vp(ok_out), vp(flags),
+        rc = self.lib.flm_ecdsa_verify_dev(self.ctx, _vp(pubkeys), _vp(digests), _vp(sigs), n, _vp(ok_out), _vp(flags),
                                            self._stream_handle(stream))
         self._check(rc, "flm_ecdsa_verify_dev")
         return ok_out
@@ -829,9 +824,8 @@ class MaskEngine:
             _dev_bytes(points_out, "points_out", 64, n)
         if flags is not None:
             _dev_bytes(flags, "flags", 1, n, 4)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
-        rc = self.lib.flm_feldman_verify_dev(self.ctx, vp(commitments), T, M, vp(dealer), vp(xs), int(x_bits),
-                                             vp(shares), n, vp(ok_out), vp(points_out), vp(flags),
+        rc = self.lib.flm_feldman_verify_dev(self.ctx, _vp(commitments), T, M, _vp(dealer), _vp(xs), int(x_bits),
+                                             _vp(shares), n, _vp(ok_out), _vp(points_out), _vp(flags),
                                              self._stream_handle(stream))
         self._check(rc, "flm_feldman_verify_dev")
         return ok_out
@@ -851,9 +845,8 @@ class MaskEngine:
         if points_out is not None:
             _dev_bytes(points_out, "points_out", 64, D)
         _dev_bytes(flags, "flags", 1, D, 4)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
-        rc = self.lib.flm_ec_combine_dev(self.ctx, vp(c1), vp(shares), vp(lambdas), T, D, 1 if negate else 0,
-                                         vp(points_out), vp(seeds_out), vp(flags), self._stream_handle(stream))
+        rc = self.lib.flm_ec_combine_dev(self.ctx, _vp(c1), _vp(shares), _vp(lambdas), T, D, 1 if negate else 0,
+                                         _vp(points_out), _vp(seeds_out), _vp(flags), self._stream_handle(stream))
         self._check(rc, "flm_ec_combine_dev")
         return seeds_out
 
@@ -871,8 +864,7 @@ class MaskEngine:
         for name, t in (("p0", p0), ("p1", p1)):
             if t is not None:
                 _dev_bytes(t, name, 1, L, 4)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
-        rc = self.lib.flm_pair_units_dev(self.ctx, vp(seeds), vp(signs), K, vp(p0), vp(p1), vp(dst), L, vp(ws),
+        rc = self.lib.flm_pair_units_dev(self.ctx, _vp(seeds), _vp(signs), K, _vp(p0), _vp(p1), _vp(dst), L, _vp(ws),
                                          1 if final else 0, int(groups), self._stream_handle(stream))
         self._check(rc, "flm_pair_units_dev")
         return dst

@@ -131,12 +131,12 @@ def test_bingcd_schedule_inverts_mod_the_group_order():
 
 # ------------------------------------------------------------------ the argument rules
 def test_argument_rules_checker(tmp_path):
-    """tools/ecdsa_args_check.cpp (flm_ecdsa_args.h + the bounce-buffer layout), built without a sanitizer"""
+    """tools/args_check.cpp (flm_call_args.h + the bounce-buffer layout), built without a sanitizer"""
     cxx = next((c for c in ("c++", "g++", "clang++", "hipcc") if shutil.which(c)), None)
     assert cxx, "no C++ compiler"
-    exe = str(tmp_path / "ecdsa_args_check")
+    exe = str(tmp_path / "args_check")
     subprocess.run([cxx, "-std=c++17", "-O1", "-I", os.path.join(ROOT, "flamingo_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "ecdsa_args_check.cpp"), "-o", exe], check=True)
+                    os.path.join(ROOT, "tools", "args_check.cpp"), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
 

@@ -143,12 +143,12 @@ def test_generator_replays_the_fixture():
 
 # ------------------------------------------------------------------ the argument rules and the ABI
 def test_argument_rules_checker(tmp_path):
-    """tools/feldman_args_check.cpp (flm_feldman_args.h + the bounce-buffer layout), built without a sanitizer"""
+    """tools/args_check.cpp (flm_call_args.h + the bounce-buffer layout), built without a sanitizer"""
     cxx = next((c for c in ("c++", "g++", "clang++", "hipcc") if shutil.which(c)), None)
     assert cxx, "no C++ compiler"
-    exe = str(tmp_path / "feldman_args_check")
+    exe = str(tmp_path / "args_check")
     subprocess.run([cxx, "-std=c++17", "-O1", "-I", os.path.join(ROOT, "flamingo_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "feldman_args_check.cpp"), "-o", exe], check=True)
+                    os.path.join(ROOT, "tools", "args_check.cpp"), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
 

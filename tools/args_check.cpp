@@ -1,0 +1,247 @@
+// args_check.cpp -- the host side of the batch crypto calls (flm_shamir_combine / _deal, flm_aes_gcm_xor /
+// _seal / _open, flm_ecdsa_verify, flm_feldman_verify, flm_ec_combine, flm_ec_mul, hash to curve) without
+// a GPU, for the host sanitizers:
+//   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -I flamingo_amd/csrc tools/args_check.cpp -o build/args_check && build/args_check
+// It runs the argument rules (flm_call_args.h) over accepted and refused calls, and for the accepted
+// ones takes the call's list of arrays -- the very list the host-pointer entry point declares to
+// HostCopies -- through the bounce-buffer layout (flm_host_layout.h): every input copied into a heap
+// buffer of the size the layout returned, a byte-wise stand-in for the kernel that reads every input
+// byte and writes every output byte, every output copied out and compared.  A span placed past the
+// buffer or overlapping another is then a sanitizer report or a failed check; so is a list that names
+// one scratch buffer twice, for any combination of its optional arrays.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "flm_call_args.h"
+#include "flm_host_layout.h"
+
+using namespace flm::rt;
+
+static int failures = 0;
+#define CHECK(cond)                                                        \
+    do {                                                                   \
+        if (!(cond)) {                                                     \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
+            ++failures;                                                    \
+        }                                                                  \
+    } while (0)
+
+// n bytes at p all equal v
+static bool all_bytes(const uint8_t *p, size_t n, uint8_t v) { return !n || (p[0] == v && !std::memcmp(p, p + 1, n - 1)); }
+
+// One call's list through a heap "bounce buffer", as HostCopies::declare, begin() and finish() move it.
+// Array i holds the byte i + 1 on the way in and 0x80 + i on the way out, so a span that overlaps
+// another loses bytes that the stand-in or the caller then misses.
+static void through_bounce(const ArgList &l) {
+    CHECK(l.n <= kMaxArgs && !names_slot_twice(l));
+    std::vector<HostSpan> spans;
+    std::vector<Arg> args;
+    for (int i = 0; i < l.n; ++i)
+        if (l.a[i].present) spans.push_back({l.a[i].bytes, 1, l.a[i].in_place}), args.push_back(l.a[i]);
+    const size_t total = host_layout(spans.data(), (int)spans.size());
+    std::vector<uint8_t> bounce(total);
+    std::vector<std::vector<uint8_t>> host(spans.size());
+    size_t end = 0;
+    for (size_t i = 0; i < spans.size(); ++i) {
+        const HostSpan &s = spans[i];
+        CHECK(s.route == (args[i].in_place ? kRouteInPlace : kRouteBounce));  // every shape here is below the staging size
+        CHECK(s.offset >= end && s.offset % 256 == 0);
+        CHECK(s.offset + s.rows * s.pitch <= total);
+        end = s.offset + s.rows * s.pitch;
+        host[i].assign(s.width, (uint8_t)(i + 1));
+        if (!args[i].is_out && s.width) std::memcpy(bounce.data() + s.offset, host[i].data(), s.width);  // inputs in
+    }
+    for (size_t i = 0; i < spans.size(); ++i)  // the kernel's stand-in: every input byte read ...
+        if (!args[i].is_out) CHECK(all_bytes(bounce.data() + spans[i].offset, spans[i].width, (uint8_t)(i + 1)));
+    for (size_t i = 0; i < spans.size(); ++i)  // ... and every output byte written
+        if (args[i].is_out && spans[i].width) std::memset(bounce.data() + spans[i].offset, (int)(0x80 + i), spans[i].width);
+    for (size_t i = 0; i < spans.size(); ++i) {  // outputs out
+        if (!args[i].is_out || !spans[i].width) continue;
+        std::memcpy(host[i].data(), bounce.data() + spans[i].offset, spans[i].width);
+        CHECK(all_bytes(host[i].data(), spans[i].width, (uint8_t)(0x80 + i)));
+    }
+}
+
+static bool bytes_are(const ArgList &l, std::initializer_list<size_t> want) {
+    if ((size_t)l.n != want.size()) return false;
+    for (int i = 0; i < l.n; ++i)
+        if (l.a[i].bytes != want.begin()[i]) return false;
+    return true;
+}
+
+static void check_lists() {
+    CHECK(kMaxRows == (size_t(1) << 26));
+    const ArgList twice = {{arg_in(4, ec_in), arg_out(4, ec_out), arg_out(4, ec_in)}, 3};
+    const ArgList absent = {{arg_in(4, ec_in), arg_out(4, ec_out), arg_out(4, ec_in, false)}, 3};
+    CHECK(names_slot_twice(twice) && !names_slot_twice(absent));
+    // every call, every combination of its optional arrays: no scratch buffer twice, and they pass the layout
+    for (int opt = 0; opt < 8; ++opt) {
+        through_bounce(ec_combine_args(3, 5, opt & 1, opt & 2, opt & 4));
+        through_bounce(feldman_verify_args(3, 5, 25, opt & 1, opt & 2, opt & 4));
+        through_bounce(aes_gcm_auth_args(12, opt & 1 ? 20 : 0, opt & 2 ? 33 : 0, 65, opt & 4));
+        if (opt < 3) through_bounce(h2c_args(65, opt == 1, opt == 2));
+    }
+    through_bounce(shamir_combine_args(20, 4055));
+    through_bounce(shamir_combine_args(0, 1));  // T = 0: the sum over nothing
+    through_bounce(ec_mul_args(65));
+    // the optional arrays are exactly the ones the flags name
+    const ArgList f = feldman_verify_args(3, 5, 25, false, true, false), e = ecdsa_verify_args(7, false);
+    CHECK(f.n == 7 && !f.a[1].present && f.a[5].present && !f.a[6].present && f.a[0].present && f.a[4].is_out);
+    CHECK(e.n == 5 && !e.a[4].present && e.a[3].present && e.a[3].is_out && !e.a[2].is_out);
+    const ArgList seal = aes_gcm_auth_args(12, 0, 0, 4, false), open = aes_gcm_auth_args(12, 1, 1, 4, true);
+    CHECK(!seal.a[2].present && !seal.a[3].present && !seal.a[4].present && seal.a[5].is_out && !seal.a[6].present);
+    CHECK(open.a[2].present && open.a[3].in_place && open.a[4].in_place && !open.a[5].is_out && open.a[6].is_out);
+}
+
+static void check_deal() {
+    // ---- flm_shamir_deal
+    CHECK(shamir_deal_dims_error(0, 1, 1) && shamir_deal_dims_error(-1, 1, 1));
+    CHECK(shamir_deal_dims_error(1, 1, 0) && shamir_deal_dims_error(1, 1, -3));
+    CHECK(shamir_deal_dims_error(1, -1, 1));
+    CHECK(shamir_deal_dims_error(1 << 14, 1 << 13, 1) && shamir_deal_dims_error(1, 1 << 20, 1 << 7));
+    CHECK(shamir_deal_dims_error(0x7fffffff, 0x7fffffff, 0x7fffffff));  // no overflow on the way to "too large"
+    CHECK(!shamir_deal_dims_error(1, 0, 1) && !shamir_deal_dims_error(20, 4096, 60));
+    CHECK(!shamir_deal_dims_error(1 << 13, 1 << 13, 1 << 13));  // exactly 2^26 lanes
+    const uint32_t ok[4] = {1, 2, 2, 0xffffffffu}, bad[4] = {1, 2, 0, 0};
+    CHECK(shamir_deal_zero_x(ok, 4) == -1 && shamir_deal_zero_x(bad, 4) == 2 && shamir_deal_zero_x(bad, 2) == -1);
+    const int deals[][3] = {{1, 1, 1}, {1, 2, 3}, {2, 1, 3}, {3, 65, 5}, {40, 130, 60}, {20, 4096, 60}};
+    for (const auto &d : deals) {
+        CHECK(!shamir_deal_dims_error(d[0], d[1], d[2]));
+        const ArgList l = shamir_deal_args(d[0], d[1], d[2]);
+        CHECK(bytes_are(l, {(size_t)d[0] * d[1] * 32, (size_t)d[2] * 4, (size_t)d[2] * d[1] * 32}));
+        through_bounce(l);
+    }
+    // ---- flm_aes_gcm_xor
+    CHECK(aes_gcm_dims_error(13, 32, 1) && aes_gcm_dims_error(0, 32, 1) && aes_gcm_dims_error(-16, 32, 1));
+    CHECK(aes_gcm_dims_error(16, 0, 1) && aes_gcm_dims_error(16, 257, 1) && aes_gcm_dims_error(12, (size_t)-1, 1));
+    CHECK(aes_gcm_dims_error(16, 32, -1) && aes_gcm_dims_error(16, 32, (1 << 26) + 1));
+    CHECK(!aes_gcm_dims_error(12, 1, 0) && !aes_gcm_dims_error(16, 256, 1 << 26));
+    const size_t lens[] = {1, 15, 16, 17, 32, 33, 64, 256};
+    for (int nonce_len : {12, 16})
+        for (size_t len : lens)
+            for (int n : {1, 65, 245760}) {
+                CHECK(!aes_gcm_dims_error(nonce_len, len, n));
+                const ArgList l = aes_gcm_xor_args(nonce_len, len, n);
+                CHECK(bytes_are(l, {(size_t)n * 16, (size_t)n * nonce_len, (size_t)n * len, (size_t)n * len}));
+                if ((size_t)n * len >= kStageBytes) continue;  // 245,760 x 256 B streams through the ring instead
+                through_bounce(l);
+            }
+}
+
+static void check_gcm() {
+    // ---- sizes
+    CHECK(aes_gcm_auth_dims_error(13, 16, 32, 1) && aes_gcm_auth_dims_error(0, 16, 32, 1) &&
+          aes_gcm_auth_dims_error(-16, 16, 32, 1) && aes_gcm_auth_dims_error(8, 0, 0, 0));
+    CHECK(aes_gcm_auth_dims_error(16, 16, 257, 1) && aes_gcm_auth_dims_error(12, 0, (size_t)-1, 1));
+    CHECK(aes_gcm_auth_dims_error(16, 65, 32, 1) && aes_gcm_auth_dims_error(16, (size_t)-1, 32, 1) &&
+          aes_gcm_auth_dims_error(16, (size_t)(int)-4, 32, 1));
+    CHECK(aes_gcm_auth_dims_error(16, 16, 32, -1) && aes_gcm_auth_dims_error(16, 16, 32, (1 << 26) + 1));
+    CHECK(!aes_gcm_auth_dims_error(12, 0, 0, 0) && !aes_gcm_auth_dims_error(16, 64, 256, 1 << 26));
+    CHECK(!aes_gcm_auth_dims_error(16, 0, 0, 1));   // a tag over nothing at all is still a tag
+    CHECK(!aes_gcm_auth_dims_error(12, 16, 0, 1));  // len 0: a tag over the AAD alone
+    CHECK(aes_gcm_dims_error(16, 0, 1));            // flm_aes_gcm_xor's own rule stands: len 0 refused
+    // ---- arrays
+    const uint8_t a = 0;
+    const void *p = &a;
+    for (bool open : {false, true}) {
+        const void *ok = open ? p : nullptr;
+        CHECK(!aes_gcm_auth_null_error(p, p, p, 16, p, p, 32, p, ok, open));
+        CHECK(!aes_gcm_auth_null_error(p, p, nullptr, 0, p, p, 32, p, ok, open));
+        CHECK(!aes_gcm_auth_null_error(p, p, p, 16, nullptr, nullptr, 0, p, ok, open));
+        CHECK(aes_gcm_auth_null_error(nullptr, p, p, 16, p, p, 32, p, ok, open));
+        CHECK(aes_gcm_auth_null_error(p, nullptr, p, 16, p, p, 32, p, ok, open));
+        CHECK(aes_gcm_auth_null_error(p, p, nullptr, 16, p, p, 32, p, ok, open));  // aad_len without aad
+        CHECK(aes_gcm_auth_null_error(p, p, p, 0, p, p, 32, p, ok, open));         // aad without aad_len
+        CHECK(aes_gcm_auth_null_error(p, p, p, 16, nullptr, p, 32, p, ok, open));
+        CHECK(aes_gcm_auth_null_error(p, p, p, 16, p, nullptr, 32, p, ok, open));
+        CHECK(aes_gcm_auth_null_error(p, p, p, 16, p, p, 32, nullptr, ok, open));
+    }
+    CHECK(aes_gcm_auth_null_error(p, p, p, 16, p, p, 32, p, nullptr, true));  // open needs ok_out
+    // ---- byte counts and the bounce layout
+    const size_t lens[] = {0, 1, 15, 16, 17, 32, 33, 64, 256}, aads[] = {0, 1, 16, 20, 64};
+    for (int nonce_len : {12, 16})
+        for (size_t len : lens)
+            for (size_t aad_len : aads)
+                for (int n : {1, 65, 245760})
+                    for (bool open : {false, true}) {
+                        CHECK(!aes_gcm_auth_dims_error(nonce_len, aad_len, len, n));
+                        const ArgList l = aes_gcm_auth_args(nonce_len, aad_len, len, n, open);
+                        CHECK(bytes_are(l, {(size_t)n * 16, (size_t)n * nonce_len, (size_t)n * aad_len, (size_t)n * len,
+                                            (size_t)n * len, (size_t)n * 16, (size_t)n}));
+                        if ((size_t)n * len >= kStageBytes) continue;  // 245,760 x 256 B streams through the ring instead
+                        through_bounce(l);
+                    }
+}
+
+static void check_ecdsa() {
+    CHECK(ecdsa_verify_dims_error(-1) && ecdsa_verify_dims_error(-0x7fffffff - 1));
+    CHECK(ecdsa_verify_dims_error((1 << 26) + 1) && ecdsa_verify_dims_error(0x7fffffff));
+    CHECK(!ecdsa_verify_dims_error(0) && !ecdsa_verify_dims_error(1) && !ecdsa_verify_dims_error(61));
+    CHECK(!ecdsa_verify_dims_error(1 << 26));  // exactly the EC size limit
+    CHECK(ecdsa_verify_aligned(0x1000, 0x2010, 0x30f0));
+    CHECK(!ecdsa_verify_aligned(0x1001, 0x2000, 0x3000) && !ecdsa_verify_aligned(0x1000, 0x2008, 0x3000) &&
+          !ecdsa_verify_aligned(0x1000, 0x2000, 0x300f));
+    // no overflow at the limit
+    CHECK(bytes_are(ecdsa_verify_args(1 << 26, true),
+                    {size_t(1) << 32, size_t(1) << 31, size_t(1) << 32, size_t(1) << 26, size_t(1) << 28}));
+    CHECK(bytes_are(ecdsa_verify_args(0, true), {0, 0, 0, 0, 0}));
+    for (int n : {1, 2, 61, 63, 64, 65, 255, 256, 257, 3660, 4096, 245760}) {
+        CHECK(!ecdsa_verify_dims_error(n));
+        CHECK(bytes_are(ecdsa_verify_args(n, true), {(size_t)n * 64, (size_t)n * 32, (size_t)n * 64, (size_t)n, (size_t)n * 4}));
+        through_bounce(ecdsa_verify_args(n, true));
+        through_bounce(ecdsa_verify_args(n, false));
+    }
+}
+
+static void check_feldman() {
+    CHECK(feldman_verify_dims_error(0, 5, 6, 1) && feldman_verify_dims_error(-1, 5, 6, 1));
+    CHECK(feldman_verify_dims_error(3, 0, 6, 1) && feldman_verify_dims_error(3, -2, 6, 1));
+    CHECK(feldman_verify_dims_error(3, 5, 0, 1) && feldman_verify_dims_error(3, 5, 33, 1) &&
+          feldman_verify_dims_error(3, 5, -1, 1));
+    CHECK(feldman_verify_dims_error(3, 5, 6, -1) && feldman_verify_dims_error(3, 5, 6, -0x7fffffff - 1));
+    CHECK(feldman_verify_dims_error(3, 5, 6, (1 << 26) + 1) && feldman_verify_dims_error(3, 5, 6, 0x7fffffff));
+    CHECK(feldman_verify_dims_error(1 << 14, (1 << 12) + 1, 6, 1));               // T x M above the limit
+    CHECK(feldman_verify_dims_error(0x7fffffff, 0x7fffffff, 6, 1));               // ... and no overflow on the way
+    CHECK(!feldman_verify_dims_error(1, 1, 1, 0) && !feldman_verify_dims_error(22, 60, 6, 3600) &&
+          !feldman_verify_dims_error(3, 5, 32, 1 << 26) && !feldman_verify_dims_error(1 << 14, 1 << 12, 6, 1));
+    const uint32_t dl[4] = {0, 4, 5, 9};
+    CHECK(feldman_bad_dealer(dl, 4, 10) == -1 && feldman_bad_dealer(dl, 4, 9) == 3 && feldman_bad_dealer(dl, 4, 5) == 2 &&
+          feldman_bad_dealer(dl, 2, 5) == -1 && feldman_bad_dealer(nullptr, 4, 1) == -1 && feldman_bad_dealer(dl, 0, 1) == -1);
+    CHECK(feldman_verify_aligned(0x1000, 0x2010, 0x30f0) && feldman_verify_aligned(0x1000, 0x2010, 0));
+    CHECK(!feldman_verify_aligned(0x1001, 0x2000, 0x3000) && !feldman_verify_aligned(0x1000, 0x2008, 0x3000) &&
+          !feldman_verify_aligned(0x1000, 0x2000, 0x300f));
+    // no overflow at the limits
+    CHECK(bytes_are(feldman_verify_args(1 << 14, 1 << 12, 1 << 26, true, true, true),
+                    {size_t(1) << 32, size_t(1) << 28, size_t(1) << 28, size_t(1) << 31, size_t(1) << 26, size_t(1) << 32,
+                     size_t(1) << 28}));
+    CHECK(bytes_are(feldman_verify_args(3, 5, 0, true, true, true), {3 * 5 * 64, 0, 0, 0, 0, 0, 0}));
+    const int shapes[][3] = {{1, 1, 1}, {3, 5, 25}, {4, 6, 36}, {22, 60, 60}, {22, 60, 3600}, {3, 7, 63}, {3, 7, 64},
+                             {3, 7, 65}, {2, 129, 129}};
+    for (const auto &s : shapes) {
+        CHECK(!feldman_verify_dims_error(s[0], s[1], 6, s[2]));
+        for (int opt = 0; opt < 8; ++opt) through_bounce(feldman_verify_args(s[0], s[1], s[2], opt & 1, opt & 2, opt & 4));
+        // a dealer array the rule lets through reads inside the T x M commitments, as a row's lane does
+        const int T = s[0], M = s[1], n = s[2];
+        std::vector<uint32_t> dealer(n);
+        for (int i = 0; i < n; ++i) dealer[i] = (uint32_t)((i * 5 + 2) % M);
+        CHECK(feldman_bad_dealer(dealer.data(), n, M) == -1);
+        const std::vector<uint8_t> com(feldman_verify_args(T, M, n, true, true, true).a[0].bytes, 1);
+        uint32_t sum = 0;
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < T; ++k) sum += com[((size_t)k * M + dealer[i]) * 64 + 63];
+        CHECK(sum == (uint32_t)n * T);
+    }
+}
+
+int main() {
+    check_lists();
+    check_deal();
+    check_gcm();
+    check_ecdsa();
+    check_feldman();
+    std::printf(failures ? "%d checks failed\n" : "args_check: all checks passed\n", failures);
+    return failures ? 1 : 0;
+}
