@@ -16,6 +16,7 @@ _u8p = ctypes.POINTER(ctypes.c_uint8)
 _i8p = ctypes.POINTER(ctypes.c_int8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_f32p = ctypes.POINTER(ctypes.c_float)
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _u64 = ctypes.c_uint64
@@ -38,6 +39,13 @@ SIGNATURES = {
     "flm_seed_table_dev": (_int, [_vp, _vp, _vp, _int, _vp]),
     "flm_aggregate_dev": (_int, [_vp, _vp, _sz, _int, _int, _sz, _sz, _sz, _u64, _vp, _vp]),
     "flm_client_mask_dev": (_int, [_vp, _vp, _sz, _int, _i64p, _vp, _i8p, _sz, _vp, _vp]),
+    "flm_codec_check": (_int, [_int, ctypes.c_float, ctypes.c_int64]),
+    "flm_client_encode_mask": (_int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _u8p, _u32p,
+                                      _u32p]),
+    "flm_client_encode_mask_dev": (_int, [_vp, _vp, _sz, _int, _i64p, _vp, _i8p, _sz, _int, ctypes.c_float, _vp, _vp,
+                                          _sz, _vp, _vp]),
+    "flm_decode_sum": (_int, [_vp, _u32p, _sz, _int, ctypes.c_int64, _f32p]),
+    "flm_decode_sum_dev": (_int, [_vp, _vp, _sz, _int, ctypes.c_int64, _vp, _vp]),
     "flm_prg_expand_dev": (_int, [_vp, _vp, _int, _sz, _u64, _vp, _sz, _vp]),
     "flm_check_signs": (_int, [_vp, ctypes.POINTER(_int)]),
     "flm_last_plan": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
@@ -102,6 +110,7 @@ SIGNATURES = {
     "flm_store_partial_wait": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "flm_store_partial_host": (_int, [_vp, _u32p]),
     "flm_store_unmask": (_int, [_vp, _u8p, _i8p, _int, _u32p]),
+    "flm_store_unmask_f32": (_int, [_vp, _u8p, _i8p, _int, _int, ctypes.c_int64, _f32p]),
     "flm_store_unmask_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "flm_store_reset": (_int, [_vp]),
     "flm_host_alloc": (_vp, [_sz]),
@@ -146,6 +155,10 @@ def p_i8(a):
 
 def p_u32(a):
     return a.ctypes.data_as(_u32p)
+
+
+def p_f32(a):
+    return a.ctypes.data_as(_f32p)
 
 
 def p_i64(a):

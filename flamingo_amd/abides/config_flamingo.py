@@ -73,8 +73,22 @@ def parse(argv):
     # and sends no COMMITTEE_SHARED_SK; off by default.  --host_dkg: that DKG's dealing and checks on the host
     ap.add_argument("--dkg", action="store_true")
     ap.add_argument("--host_dkg", action="store_true")
+    # the clients' inputs are float32 updates, encoded in fixed point inside the masking kernel, and the server
+    # also decodes the sum to final_mean (protocol.configure(codec=...)): F fractional bits, clip CLIP, nearest-even
+    # rounding or, with ",sr", stochastic rounding; off by default
+    ap.add_argument("--float_inputs", default=None, metavar="F,CLIP[,sr]")
     args, _ = ap.parse_known_args(argv)
     return ap, args
+
+
+def parse_float_inputs(spec):
+    """"F,CLIP" or "F,CLIP,sr" -> (frac_bits, clip, "nearest" | "stochastic"); None or "" -> False (off)."""
+    if not spec:
+        return False
+    parts = [s.strip() for s in spec.split(",")]
+    if len(parts) not in (2, 3) or (len(parts) == 3 and parts[2] != "sr"):
+        raise ValueError("--float_inputs takes F,CLIP or F,CLIP,sr")
+    return int(parts[0]), float(parts[1]), "stochastic" if len(parts) == 3 else "nearest"
 
 
 def offline_schedule(n: int, iterations: int, always=(), dropout: float = 0.0) -> dict:
@@ -144,7 +158,7 @@ def _run(args):
                     check_signatures=True if args.check_signatures else None,
                     gpu_verify=True if args.gpu_verify else None,
                     authenticate_shares=True if args.authenticate_shares else None,
-                    dkg=True if args.dkg else None)
+                    dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs))
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -203,6 +217,12 @@ def _run(args):
               f"final_sum == |U| in every slot: {bool(np.all(out == u))}; report GPU {gpu.get('report', 0):.3f} ms, "
               f"unmask + D2H {gpu.get('reconstruction_unmask_gpu', 0):.3f} ms GPU "
               f"({gpu.get('reconstruction_unmask_wall', 0):.3f} ms wall)")
+        if it in server.means:      # float inputs: the decoded mean against the mean of the clients' own floats
+            exact = np.mean([np.asarray(agents[i].input_vector, np.float64) for i in server.online_ids[it]], axis=0)
+            print(f"    iteration {it}: float inputs {param.codec()}: largest |final_mean - mean of the clients' floats| = "
+                  f"{float(np.max(np.abs(server.means[it].astype(np.float64) - exact))):.3e}, "
+                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped")
     print()
     results["server"] = server
+    results["clients"] = agents[:n]
     return results

@@ -92,7 +92,9 @@ class SA_ClientAgent(Agent):
         # iterations in which this client crashes before sending (explicit dropout injection;
         # in the reference dropouts only come from late messages)
         self.offline_iterations = set(offline_iterations)
-        self.input_vector = None     # None -> all ones (:304)
+        self.input_vector = None     # None -> all ones (:304); with float inputs: a synthetic float32 update
+        self.clipped = 0             # float inputs: elements of the last update that were clipped
+        self.dither_seed = None      # float inputs, stochastic rounding: the last iteration's dither seed
         pki = param.pki(num_clients)
         self.secret_key = pki.client_sk[id]
         self.public_key = pki.client_pk[id]
@@ -222,8 +224,25 @@ class SA_ClientAgent(Agent):
         if gpu_deal:      # after elgamal_masks: every client's r's are drawn before the batch draws for it
             enc_mi_shares = param.mi_shares(self, self.current_iteration)
 
-        x = None if self.input_vector is None else np.asarray(self.input_vector, np.uint32)[None, :]
-        vec = param.engine().client_mask(np.array([0, len(seeds)], np.int64), seeds, signs, self.vector_len, x=x)[0]
+        codec = param.codec()
+        if codec is None:
+            x = None if self.input_vector is None else np.asarray(self.input_vector, np.uint32)[None, :]
+            vec = param.engine().client_mask(np.array([0, len(seeds)], np.int64), seeds, signs, self.vector_len, x=x)[0]
+        else:
+            # float inputs ("replace it with model weights", :300-304): the fixed-point encoding is fused into
+            # the masking, the VECTOR body is the same uint32 row.  The dither seed is this client's last draw.
+            frac_bits, clip, rounding = codec
+            if self.input_vector is None:
+                from ...synthetic import float_update
+                self.input_vector = float_update(self.id, self.vector_len, clip)
+            x = np.asarray(self.input_vector, np.float32)[None, :]
+            dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
+                if rounding == "stochastic" else None
+            vec, clipped = param.engine().client_encode_mask(np.array([0, len(seeds)], np.int64), seeds, signs,
+                                                             self.vector_len, x, frac_bits, clip, dither=dither,
+                                                             return_clipped=True)
+            vec, self.clipped = vec[0], int(clipped[0])
+            self.dither_seed = dither[0] if dither else None
         self.sendMessage(self.serviceAgentID, Message({
             "msg": "VECTOR", "iteration": self.current_iteration, "sender": self.id, "vector": vec,
             "enc_mi_shares": wire.serialize_tuples_bytes(enc_mi_shares),

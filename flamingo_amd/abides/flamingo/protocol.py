@@ -62,15 +62,28 @@ _signature_quorum = 2 / 3               # configure(signature_quorum=...): the s
 # set-up, SA_ServiceAgent.py:261-279): off by default, so a run sends what it always sent.
 _dkg: bool = False                      # configure(dkg=...)
 _dkg_result = None                      # (group key, {committee member id: (member index, key share)})
+# Float inputs (config_flamingo's --float_inputs F,CLIP[,sr]): a client's input_vector is float32 and goes through
+# the fixed-point codec fused into its masking (MaskEngine.client_encode_mask); the server keeps final_sum and
+# adds final_mean.  Off by default, so a run sends what it always sent and draws what it always drew.
+_codec = None                           # configure(codec=(frac_bits, clip, "nearest" | "stochastic"))
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
-              authenticate_shares: bool | None = None, dkg: bool | None = None):
-    """Reset the protocol parameters (between simulations / in tests)."""
+              authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None):
+    """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
+    "stochastic") turns the float inputs on, False turns them off, None leaves them as they are."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares, _dkg, _dkg_result
+    global _authenticate_shares, _dkg, _dkg_result, _codec
+    if codec is not None:
+        if codec is False:
+            _codec = None
+        else:
+            f, c, mode = codec
+            if mode not in ("nearest", "stochastic"):
+                raise ValueError("codec rounding must be 'nearest' or 'stochastic'")
+            _codec = (int(f), float(c), mode)
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -234,6 +247,11 @@ def pki(num_clients: int):
             raise RuntimeError("configure(dkg=True): the committee's key generation has not run (set_dkg_result)")
         _pkis[key] = PKI(root_seed, num_clients, engine(), system_pk=_dkg_result[0] if _dkg else None)
     return _pkis[key]
+
+
+def codec():
+    """(frac_bits, clip, rounding) of the float inputs, or None when they are off (configure(codec=...))."""
+    return _codec
 
 
 def dkg_on() -> bool:

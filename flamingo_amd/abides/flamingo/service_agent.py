@@ -75,6 +75,12 @@ class SA_ServiceAgent(Agent):
         self.current_iteration = 1
         self.current_round = 0
         self.results = {}            # iteration -> final_sum (kept for inspection / tests)
+        self.final_mean = None       # float inputs: final_sum decoded as the mean over the online clients
+        self.means = {}              # float inputs: iteration -> final_mean
+        self.online_ids = {}         # float inputs: iteration -> the clients whose vectors were summed
+        if param.codec() is not None:
+            # n updates of magnitude up to clip must fit the 32-bit ring: refuse the run, never wrap (FLM_ERANGE)
+            param.engine().codec_check(param.codec()[0], param.codec()[1], max(1, len(users) or num_clients))
         self.online_counts = {}      # iteration -> |U|
         self.pairs_per_iteration = {}  # iteration -> D dropout pairs recovered
         self.aggProcessingMap = {0: self.initialize, 1: self.report, 2: self.forward_signatures,
@@ -320,8 +326,12 @@ class SA_ServiceAgent(Agent):
         # K masks over its own slot shard of the device-resident S, then the one copy to the host
         t0 = pd.Timestamp("now")
         st = self.store()
+        codec = param.codec()
+        self.final_mean = None
         if getattr(st, "has_partial", True):
             self.final_sum = st.unmask(seeds, signs)
+            if codec is not None:      # float inputs: the same sum, decoded on the GPU(s) as the mean over U
+                self.final_mean = st.unmask_f32(seeds, signs, codec[0], max(1, len(self.user_vectors)))
         else:
             # no report this iteration: the reference-style assigned partial sum (vec_sum_partial
             # setter, :540/:605) is the S the masks are added to, on the GPU
@@ -334,6 +344,11 @@ class SA_ServiceAgent(Agent):
             rec["reconstruction_unmask_gpu"] = gpu
         self.agent_print(f"reconstruction unmask: {len(seeds)} masks over S on the GPU(s) + D2H, {ms:.3f} ms wall"
                          + (f", {gpu:.3f} ms GPU" if gpu is not None else ""))
+        if codec is not None and self.final_mean is None:
+            self.final_mean = param.engine().decode_sum(self.final_sum, codec[0], max(1, len(self.user_vectors)))
+        if codec is not None:
+            self.means[self.current_iteration] = self.final_mean
+            self.online_ids[self.current_iteration] = sorted(self.user_vectors)
         self.results[self.current_iteration] = self.final_sum
         self.online_counts[self.current_iteration] = len(self.user_vectors)
         self.pairs_per_iteration[self.current_iteration] = len(self.recon_symbol)

@@ -40,6 +40,15 @@ hipError_t launch_small_round(int B, const uint32_t *d_rows, uint64_t pitch, int
 hipError_t launch_small_client_mask(const uint32_t *d_x, uint64_t pitch, int N, const int64_t *d_seg,
                                    const uint8_t *d_seeds, const int8_t *d_signs, uint64_t L, uint32_t bias,
                                    uint32_t *d_out, hipStream_t stream);
+// Fixed-point codec (encode_mask_kernel, decode_sum_kernel).  d_out[i][l] = encode(d_x[i][l]) + client i's masks, one
+// workgroup per (client, 1024-slot tile) of a one-dimensional grid (encode_mask_groups of them, at most 2^31 - 1);
+// d_dither N x 32 selects stochastic rounding, NULL nearest-even; d_clipped N words, zeroed by the caller, or NULL.
+uint64_t encode_mask_groups(int N, uint64_t L);
+hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                              const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
+                              uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream);
+// d_out[l] = float32(float64(int32(d_sum[l])) / denom), l < n; d_out may be d_sum; both 16-byte aligned
+hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, float *d_out, hipStream_t stream);
 uint32_t pair_units_count(int K, uint64_t L, uint32_t *n_tiles);
 hipError_t launch_pair_units(bool side, const SeedRec *d_recs, int K, uint32_t *d_dst, uint64_t L, uint32_t *d_ws,
                              int groups, hipStream_t stream);

@@ -874,10 +874,198 @@ __global__ __launch_bounds__(256) void shard_sum_kernel(PartPtrs parts, int G, u
     }
 }
 
+// ------------------------------------------------------------ fixed-point codec
+// Float updates in, float mean out (the "replace it with model weights" of SA_ClientAgent.py:300-304).
+// The codec's one definition is in DESIGN.md section 5 and, restated in numpy, tests/codec_cases.py:
+//   encode: NaN -> 0, clip to [-c, c], t = x 2^f (exact), nearest-even or stochastic rounding, two's complement
+//   decode: float32(float64(int32(s)) / (count 2^f))
+
+// m[i] += ChaCha20_block(key at p, ctr)[i] ^ xc from the raw 32 key bytes (wave-uniform: scalar loads), as
+// small_round_kernel's SEG mode does: no SeedRec table, so the call is one launch and touches no table ring.
+__device__ __forceinline__ void chacha_raw_add(const uint8_t *__restrict__ p, uint32_t ctr, uint32_t xc,
+                                               uint32_t (&m)[16]) {
+    uint32_t k[8];
+    if (((uintptr_t)p & 15) == 0) {
+        const uint4 a0 = reinterpret_cast<const uint4 *>(p)[0], a1 = reinterpret_cast<const uint4 *>(p)[1];
+        k[0] = a0.x; k[1] = a0.y; k[2] = a0.z; k[3] = a0.w;
+        k[4] = a1.x; k[5] = a1.y; k[6] = a1.z; k[7] = a1.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            k[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) |
+                   ((uint32_t)p[4 * i + 3] << 24);
+    }
+    uint32_t x0 = kSigma0, x1 = kSigma1, x2 = kSigma2, x3 = kSigma3;
+    uint32_t x4 = k[0], x5 = k[1], x6 = k[2], x7 = k[3], x8 = k[4], x9 = k[5], x10 = k[6], x11 = k[7];
+    uint32_t x12 = ctr, x13 = 0u, x14 = 0u, x15 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        FLM_QR4(x0, x4, x8, x12, x1, x5, x9, x13, x2, x6, x10, x14, x3, x7, x11, x15);
+        FLM_QR4(x0, x5, x10, x15, x1, x6, x11, x12, x2, x7, x8, x13, x3, x4, x9, x14);
+    }
+    m[0] += (x0 + kSigma0) ^ xc;
+    m[1] += (x1 + kSigma1) ^ xc;
+    m[2] += (x2 + kSigma2) ^ xc;
+    m[3] += (x3 + kSigma3) ^ xc;
+    m[4] += (x4 + k[0]) ^ xc;
+    m[5] += (x5 + k[1]) ^ xc;
+    m[6] += (x6 + k[2]) ^ xc;
+    m[7] += (x7 + k[3]) ^ xc;
+    m[8] += (x8 + k[4]) ^ xc;
+    m[9] += (x9 + k[5]) ^ xc;
+    m[10] += (x10 + k[6]) ^ xc;
+    m[11] += (x11 + k[7]) ^ xc;
+    m[12] += (x12 + ctr) ^ xc;
+    m[13] += x13 ^ xc;
+    m[14] += x14 ^ xc;
+    m[15] += x15 ^ xc;
+}
+
+// One element of the codec.  r: the dither word of this slot (stochastic rounding only).
+template <bool STOCHASTIC>
+__device__ __forceinline__ uint32_t codec_encode(float x, float clip, float scale, uint32_t r, uint32_t &nclip) {
+#pragma clang fp contract(off)
+    const bool nan = x != x;
+    nclip += (nan || fabsf(x) > clip) ? 1u : 0u;
+    x = nan ? 0.0f : x;
+    const float t = fminf(fmaxf(x, -clip), clip) * scale;  // a power-of-two scale: exact
+    if constexpr (!STOCHASTIC) {
+        return (uint32_t)(int32_t)rintf(t);  // ties to even
+    } else {
+        const float ti = truncf(t), fr = fabsf(t - ti);           // fr exact: its bits are a subset of t's
+        const uint32_t thr = (uint32_t)(fr * 4294967296.0f);      // < 2^32: fr <= 1 - 2^-24
+        int32_t q = (int32_t)ti;
+        if (r < thr) q += t < 0.0f ? -1 : 1;
+        return (uint32_t)q;
+    }
+}
+
+// out[i][l] = encode(x[i][l]) + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l]   (SA_ClientAgent.py:300-324)
+// Workgroup g = (client i, 1024-slot tile) = (g / tiles, g % tiles) of a one-dimensional grid; four waves.
+// Every wave's lane t owns ChaCha block t of the tile (slots 16t..16t+15).  Client i's seeds go round the four
+// waves; the last wave, which gets the fewest, also loads the lane's 16 floats (four 16-byte loads, the same block
+// layout), makes the dither block in stochastic mode, and adds the encoded words to its mask accumulator: they
+// exist only in registers.  The four accumulators meet in LDS and the tile is stored once, 16 bytes per thread.
+// Slots past L read as 0.0 (a predicate per element: the padding of a row may hold anything), encode to 0 and
+// are never counted as clipped or stored.  clipped[i] (zeroed by the call) gets one atomic add per workgroup.
+template <bool STOCHASTIC>
+__global__ __launch_bounds__(256) void encode_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
+                                                          const int64_t *__restrict__ seg,
+                                                          const uint8_t *__restrict__ seeds,
+                                                          const int8_t *__restrict__ signs,
+                                                          const uint8_t *__restrict__ dither, uint64_t L, uint32_t tiles,
+                                                          float clip, float scale, uint32_t *__restrict__ out,
+                                                          uint64_t out_pitch, uint32_t *__restrict__ clipped) {
+    __shared__ u32x4 lds[4 * 256];  // 16 KiB: one 4 KiB region per wave
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
+    const uint64_t slot0 = (uint64_t)tile * 1024u + 16u * (uint64_t)lane;
+    const uint32_t ctr = tile * 64u + (uint32_t)lane;
+    const int64_t k_lo = seg[i], k_hi = seg[i + 1];
+
+    uint32_t m[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m[j] = 0u;
+    uint32_t nneg = 0;
+    // seed u of the client runs on the wave of rank (u + 1) % 4; rank 0 (wave 3) has the encoding as its unit 0
+    const int rank = 3 - w;
+    for (int64_t k = k_lo + ((rank + 3) & 3); k < k_hi; k += 4) {
+        const bool neg = signs[k] < 0;
+        nneg += neg ? 1u : 0u;
+        chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
+    }
+    if (rank == 0) {
+        uint32_t r[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) r[j] = 0u;
+        if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, ctr, kAbcd, r);
+        const float *xr = x + (uint64_t)i * x_pitch;
+        uint32_t nclip = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t s = slot0 + 4u * j;
+            // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+            const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+            m[4 * j + 0] += codec_encode<STOCHASTIC>(s + 0 < L ? v.x : 0.0f, clip, scale, r[4 * j + 0], nclip);
+            m[4 * j + 1] += codec_encode<STOCHASTIC>(s + 1 < L ? v.y : 0.0f, clip, scale, r[4 * j + 1], nclip);
+            m[4 * j + 2] += codec_encode<STOCHASTIC>(s + 2 < L ? v.z : 0.0f, clip, scale, r[4 * j + 2], nclip);
+            m[4 * j + 3] += codec_encode<STOCHASTIC>(s + 3 < L ? v.w : 0.0f, clip, scale, r[4 * j + 3], nclip);
+        }
+        if (clipped) {  // only this wave counts: its total is the workgroup's
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
+            if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
+        }
+    }
+
+    u32x4 *R = lds + w * 256 + 4 * lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        R[j] = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
+    __syncthreads();
+    const int p = threadIdx.x;  // quad p of the tile: 1 KiB contiguous per wave store
+    const u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p];
+    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
+    uint32_t *dst = out + (uint64_t)i * out_pitch + slot;
+    if (slot + 3 < L) {
+        *reinterpret_cast<u32x4 *>(dst) = acc;
+    } else {
+        if (slot + 0 < L) dst[0] = acc.x;
+        if (slot + 1 < L) dst[1] = acc.y;
+        if (slot + 2 < L) dst[2] = acc.z;
+    }
+}
+
+// out[l] = float32(float64(int32(sum[l])) / denom), denom = count 2^f (SA_ServiceAgent.py:538-540, 605: the
+// final sum, as a mean).  16-byte loads and stores; a thread reads its quad before it writes it, so out may be
+// sum.  HBM-bound: the double division hides under the stream.
+__global__ __launch_bounds__(256) void decode_sum_kernel(const uint32_t *sum, uint64_t n, double denom, float *out) {
+    const uint64_t quads = n / 4, stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t q = t0; q < quads; q += stride) {
+        const uint4 s = reinterpret_cast<const uint4 *>(sum)[q];
+        float4 v;
+        v.x = (float)((double)(int32_t)s.x / denom);
+        v.y = (float)((double)(int32_t)s.y / denom);
+        v.z = (float)((double)(int32_t)s.z / denom);
+        v.w = (float)((double)(int32_t)s.w / denom);
+        reinterpret_cast<float4 *>(out)[q] = v;
+    }
+    const uint64_t t = 4 * quads + t0;
+    if (t < n) out[t] = (float)((double)(int32_t)sum[t] / denom);
+}
+
 #undef FLM_QR
 #undef FLM_ROTL
 
 // ----------------------------------------------------------------- launchers
+uint64_t encode_mask_groups(int N, uint64_t L) { return (uint64_t)N * ((L + 1023) / 1024); }
+
+hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                              const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
+                              uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream) {
+    const uint64_t groups = encode_mask_groups(N, L);
+    if (groups == 0) return hipSuccess;
+    if (groups > 0x7fffffffull || frac_bits < 0 || frac_bits > 30) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)((L + 1023) / 1024);
+    const float scale = (float)(1u << frac_bits);
+    if (d_dither)
+        hipLaunchKernelGGL(encode_mask_kernel<true>, dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
+                           d_seeds, d_signs, d_dither, L, tiles, clip, scale, d_out, out_pitch, d_clipped);
+    else
+        hipLaunchKernelGGL(encode_mask_kernel<false>, dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
+                           d_seeds, d_signs, d_dither, L, tiles, clip, scale, d_out, out_pitch, d_clipped);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, float *d_out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint64_t g = std::min<uint64_t>(4096, (n / 4 + 255) / 256 + 1);
+    hipLaunchKernelGGL(decode_sum_kernel, dim3((unsigned)g), dim3(256), 0, stream, d_sum, n, denom, d_out);
+    return hipGetLastError();
+}
+
 // Workgroups of the seed-schedule launch: one per 256 seeds, more when it also zero-fills
 // (about 16 KiB per workgroup, at most 1024).  meta needs 2 + 2 * this many words.
 int seed_schedule_groups(int K, uint64_t zero_n) {

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1033,7 +1034,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1266,6 +1267,130 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
     }
     // signs go to the device with the work items (the schedule folds them into xorc)
     return run_rows_jobs(ctx, d_x, pitch, N, seg, signs, d_seeds, (int)K, 1u, L, 0, d_out, s);
+}
+
+// The codec's parameter and headroom rule: n ceil(clip 2^f) <= 2^31 - 1.  clip 2^f is exact in double (a float
+// times a power of two), so is its ceiling, and the product is compared in integers.
+static int codec_check(flm_ctx *ctx, int frac_bits, float clip, int64_t n) {
+    if (frac_bits < 0 || frac_bits > 30) return fail(ctx, FLM_EINVAL, "frac_bits %d outside 0..30", frac_bits);
+    if (!(clip > 0.0f) || !std::isfinite(clip)) return fail(ctx, FLM_EINVAL, "clip must be finite and positive");
+    if (n < 1) return fail(ctx, FLM_EINVAL, "a count of contributors must be at least 1");
+    const double m = std::ceil((double)clip * std::ldexp(1.0, frac_bits));
+    if (m > 2147483647.0 || (uint64_t)n > 2147483647ull / (uint64_t)m)
+        return fail(ctx, FLM_ERANGE, "%lld contributors of magnitude up to %.0f can wrap the 32-bit sum", (long long)n, m);
+    return 0;
+}
+
+int flm_codec_check(int frac_bits, float clip, int64_t n_clients) { return codec_check(nullptr, frac_bits, clip, n_clients); }
+
+// flm_client_mask[_dev]'s rules for seg and signs; *K_out = seg[N]
+static int check_seg_signs(flm_ctx *ctx, int N, const int64_t *seg, const int8_t *signs, int64_t *K_out) {
+    if (seg[0] != 0) return fail(ctx, FLM_EINVAL, "seg[0] must be 0");
+    for (int i = 0; i < N; ++i)
+        if (seg[i + 1] < seg[i]) return fail(ctx, FLM_EINVAL, "seg must be non-decreasing");
+    const int64_t K = seg[N];
+    if (K > 0x7fffffff) return fail(ctx, FLM_EINVAL, "too many seeds");
+    if (K > 0 && !signs) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (!signs_ok(signs, (int)K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
+    *K_out = K;
+    return 0;
+}
+
+int flm_client_encode_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                           const int8_t *signs, size_t L, int frac_bits, float clip, const uint8_t *dither,
+                           uint32_t *out, uint32_t *clipped) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (int rc = codec_check(ctx, frac_bits, clip, 1)) return rc;
+    if (N == 0 || L == 0) return 0;
+    if (!x || !seg || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    int64_t K = 0;
+    if (int rc = check_seg_signs(ctx, N, seg, signs, &K)) return rc;
+    if (K > 0 && !seeds) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (int rc = check_range(ctx, 0, L)) return rc;
+    FLM_ON_DEVICE(ctx);
+    const uint64_t pitch = round_up(L, 64);
+    // as flm_client_mask: one client's call reads x from and writes y to the pinned bounce buffer in place
+    HostCopies hc(ctx, ctx->stream);
+    const auto *hx = hc.in(x, L * 4, L * 4, (size_t)N, ctx->rows, pitch * 4, HostCopies::kMayRunInPlace);
+    hc.in(seeds, (size_t)K * 32, ctx->seeds);
+    const auto *hd = dither ? hc.in(dither, (size_t)N * 32, ctx->bytes_in) : nullptr;
+    const auto *hy = hc.out(out, L * 4, L * 4, (size_t)N, ctx->out, pitch * 4, HostCopies::kMayRunInPlace);
+    const auto *hcl = clipped ? hc.out(clipped, (size_t)N * 4, ctx->bytes_out) : nullptr;
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_client_encode_mask_dev(ctx, hx->as<const float>(), hx->pitch / 4, N, seg, ctx->seeds.as<uint8_t>(),
+                                            signs, L, frac_bits, clip, hd ? hd->as<const uint8_t>() : nullptr,
+                                            hy->as<uint32_t>(), hy->pitch / 4, hcl ? hcl->as<uint32_t>() : nullptr,
+                                            ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                               const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
+                               const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
+                               void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = codec_check(ctx, frac_bits, clip, 1)) return rc;
+    if (N <= 0 || L == 0) return 0;
+    if (!d_x || !seg || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (x_pitch % 4 || x_pitch < round_up(L, 4) || out_pitch % 4 || out_pitch < round_up(L, 4))
+        return fail(ctx, FLM_EINVAL, "pitch must be a multiple of 4 and >= L");
+    if (((uintptr_t)d_out & 15) || ((uintptr_t)d_x & 15)) return fail(ctx, FLM_EINVAL, "x/out must be 16-byte aligned");
+    int64_t K = 0;
+    if (int rc = check_seg_signs(ctx, N, seg, signs, &K)) return rc;
+    if (K > 0 && !d_seeds) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (int rc = check_range(ctx, 0, L)) return rc;
+    if (flm::encode_mask_groups(N, L) > 0x7fffffffull)
+        return fail(ctx, FLM_EINVAL, "N=%d x %zu slots: more than 2^31 - 1 1024-slot tiles", N, L);
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+    FLM_ON_DEVICE(ctx);
+    // seg and signs travel in one host-to-device copy through a staging slot (never waits on queued work)
+    const size_t seg_bytes = (size_t)(N + 1) * sizeof(int64_t), need = seg_bytes + (size_t)K;
+    int rc = 0;
+    StageSlot *slot = stage_acquire(ctx, need, &rc);
+    if (!slot) return rc;
+    std::memcpy(slot->host, seg, seg_bytes);
+    if (K > 0) std::memcpy(static_cast<uint8_t *>(slot->host) + seg_bytes, signs, (size_t)K);
+    FLM_HIP(ctx, stage_upload(slot, need, s));
+    hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
+    if (e == hipSuccess)
+        e = flm::launch_encode_mask(d_x, x_pitch, N, slot->dev.as<int64_t>(), d_seeds,
+                                    reinterpret_cast<const int8_t *>(slot->dev.as<uint8_t>() + seg_bytes), d_dither, L,
+                                    frac_bits, clip, d_out, out_pitch, d_clipped, s);
+    FLM_HIP(ctx, stage_commit(slot, s));
+    FLM_HIP(ctx, e);
+    return 0;
+}
+
+int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, int64_t count, float *out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (frac_bits < 0 || frac_bits > 30) return fail(ctx, FLM_EINVAL, "frac_bits %d outside 0..30", frac_bits);
+    if (count < 1) return fail(ctx, FLM_EINVAL, "count must be at least 1");
+    if (L == 0) return 0;
+    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    const auto *hs = hc.in(sum, L * 4, ctx->rows, HostCopies::kMayRunInPlace);
+    const auto *ho = hc.out(out, L * 4, ctx->out, HostCopies::kMayRunInPlace);
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_decode_sum_dev(ctx, hs->as<const uint32_t>(), L, frac_bits, count, ho->as<float>(), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, int64_t count, float *d_out,
+                       void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (frac_bits < 0 || frac_bits > 30) return fail(ctx, FLM_EINVAL, "frac_bits %d outside 0..30", frac_bits);
+    if (count < 1) return fail(ctx, FLM_EINVAL, "count must be at least 1");
+    if (L == 0) return 0;
+    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (((uintptr_t)d_sum & 15) || ((uintptr_t)d_out & 15)) return fail(ctx, FLM_EINVAL, "sum/out must be 16-byte aligned");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_decode_sum(d_sum, L, (double)count * std::ldexp(1.0, frac_bits), d_out,
+                                        static_cast<hipStream_t>(stream)));
+    return 0;
 }
 
 int flm_prg_expand(flm_ctx *ctx, const uint8_t *seeds, int K, size_t L, uint64_t slot0, uint32_t *out) {

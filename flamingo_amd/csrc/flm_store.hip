@@ -350,7 +350,10 @@ int flm_store_partial_host(flm_store *st, uint32_t *out) {
     return 0;
 }
 
-int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out) {
+// flm_store_unmask, and flm_store_unmask_f32 when count > 0: then every device decodes its shard in place
+// (float and uint32 shards are the same size) before the copy it makes anyway, and `out` holds floats.
+static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out, int frac_bits,
+                        int64_t count) {
     flm::rt::DeviceScope dev_scope_;  // the caller's device comes back on return
     if (!st || !out || K < 0 || (K > 0 && (!seeds || !signs))) return sfail(st, FLM_EINVAL, "bad argument");
     if (!st->have_partial) return sfail(st, FLM_EINVAL, "no partial sum: call flm_store_partial at report");
@@ -396,6 +399,9 @@ int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, i
                                               K ? reinterpret_cast<const int8_t *>(k.seeds + (size_t)K * 32) : nullptr,
                                               K, n, 0, n, k.lo, k.out, s))
             return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
+        if (count > 0)
+            if (int rc = flm_decode_sum_dev(k.ctx, k.out, n, frac_bits, count, reinterpret_cast<float *>(k.out), s))
+                return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
         FLM_SHIP(st, hipMemcpyAsync(st->hout + k.lo, k.out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
     FLM_SHIP(st, hipSetDevice(st->rk[0].device));
@@ -409,6 +415,16 @@ int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, i
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, st->u0, st->u1) == hipSuccess) st->unmask_ms = ms;
     return 0;
+}
+
+int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out) {
+    return store_unmask(st, seeds, signs, K, out, 0, 0);
+}
+
+int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, int frac_bits, int64_t count,
+                         float *out) {
+    if (frac_bits < 0 || frac_bits > 30 || count < 1) return sfail(st, FLM_EINVAL, "frac_bits outside 0..30 or count < 1");
+    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), frac_bits, count);
 }
 
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms) {

@@ -30,7 +30,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import p_i8, p_i64, p_u8, p_u32
+from ._lib import p_f32, p_i8, p_i64, p_u8, p_u32
 
 NONCE = b"\x00" * 8
 
@@ -255,6 +255,54 @@ class MaskEngine:
         self._check(rc, "flm_client_mask")
         return out
 
+    # ------------------------------------------------- fixed-point codec
+    def codec_check(self, frac_bits: int, clip: float, n_clients: int = 1):
+        """Raise unless n_clients updates of magnitude <= clip fit the 32-bit ring at frac_bits
+        (flm_codec_check: n * ceil(clip * 2^frac_bits) <= 2^31 - 1); no device call."""
+        rc = self.lib.flm_codec_check(int(frac_bits), float(clip), int(n_clients))
+        self._check(rc, "flm_codec_check")
+
+    def client_encode_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float, dither=None,
+                           return_clipped: bool = False):
+        """y_i = encode(x_i) + sum_{k in seg i} signs[k]*PRG(seeds[k]) for float32 x (N, L); (N, L) uint32.
+
+        dither: N 32-byte seeds for stochastic rounding, None for nearest-even.  With
+        return_clipped, also the (N,) uint32 counts of elements that were NaN or beyond +-clip."""
+        seg = np.ascontiguousarray(seg, dtype=np.int64)
+        N = seg.shape[0] - 1
+        seeds = _seeds_array(seeds)
+        signs = _signs_array(signs, seeds.shape[0])
+        if seg[-1] != seeds.shape[0]:
+            raise RuntimeError("seg[-1] must equal the number of seeds")
+        if x is None:
+            raise RuntimeError("x is required")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.shape != (N, L):
+            raise RuntimeError("x must be (N, L)")
+        dp = None
+        if dither is not None:
+            dither = _seeds_array(dither)
+            if dither.shape[0] != N:
+                raise RuntimeError("one 32-byte dither seed per client")
+            dp = p_u8(dither)
+        out = np.empty((N, L), dtype=np.uint32)
+        clipped = np.zeros(N, dtype=np.uint32)
+        rc = self.lib.flm_client_encode_mask(self.ctx, p_f32(x), N, p_i64(seg), p_u8(seeds), p_i8(signs), L,
+                                             int(frac_bits), float(clip), dp, p_u32(out),
+                                             p_u32(clipped) if return_clipped else None)
+        self._check(rc, "flm_client_encode_mask")
+        return (out, clipped) if return_clipped else out
+
+    def decode_sum(self, total: np.ndarray, frac_bits: int, count: int = 1) -> np.ndarray:
+        """float32(int32(total) / (count * 2^frac_bits)): the ring sum as the mean of `count` contributors."""
+        total = np.ascontiguousarray(total, dtype=np.uint32)
+        if total.ndim != 1:
+            raise RuntimeError("total must be a vector")
+        out = np.empty(total.shape[0], dtype=np.float32)
+        rc = self.lib.flm_decode_sum(self.ctx, p_u32(total), total.shape[0], int(frac_bits), int(count), p_f32(out))
+        self._check(rc, "flm_decode_sum")
+        return out
+
     def prg_expand(self, seeds, L: int, slot0: int = 0) -> np.ndarray:
         """PRG(seed_k)[slot0:slot0+L] for every seed; (K, L) uint32."""
         seeds = _seeds_array(seeds)
@@ -382,6 +430,54 @@ class MaskEngine:
                                           p_i64(seg), ctypes.c_void_p(seeds_dev.data_ptr()), p_i8(signs), L,
                                           ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
         self._check(rc, "flm_client_mask_dev")
+        return out
+
+    def client_encode_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float,
+                               dither_dev=None, clipped=None, stream=None):
+        """Device client_encode_mask: seg/signs host arrays; seeds_dev (K, 32) uint8, x (>= N, >= L) float32,
+        out (>= N, >= L) 32-bit, dither_dev (N, 32) uint8 or None, clipped (>= N,) 32-bit or None: CUDA
+        tensors, rows at their own strides.  Enqueued on `stream`; nothing is synchronised."""
+        import torch
+        seg = np.ascontiguousarray(seg, dtype=np.int64)
+        N = seg.shape[0] - 1
+        signs = np.ascontiguousarray(signs, dtype=np.int8)
+        K = int(seg[-1]) if N >= 0 else 0
+        if N < 0 or seg[0] != 0 or np.any(np.diff(seg) < 0):
+            raise RuntimeError("seg must be non-decreasing from 0")
+        if signs.ndim != 1 or signs.shape[0] != K:
+            raise RuntimeError(f"{signs.shape[0] if signs.ndim else 0} signs for seg[-1] = {K} seeds")
+        if K and (seeds_dev.dim() != 2 or seeds_dev.shape[1] != 32 or seeds_dev.element_size() != 1
+                  or seeds_dev.shape[0] < K or not seeds_dev.is_contiguous()):
+            raise RuntimeError(f"seeds_dev must be a contiguous (>= {K}, 32) uint8 tensor, got {tuple(seeds_dev.shape)}")
+        for name, t in (("x", x), ("out", out)):
+            if t is None or t.dim() != 2 or t.shape[0] < N or t.shape[1] < L or t.element_size() != 4 or t.stride(1) != 1:
+                raise RuntimeError(f"{name} must be (>= {N}, >= {L}) 32-bit with unit column stride")
+        if x.dtype != torch.float32:
+            raise RuntimeError("x must be float32")
+        if dither_dev is not None and (tuple(dither_dev.shape) != (N, 32) or dither_dev.element_size() != 1
+                                       or not dither_dev.is_contiguous()):
+            raise RuntimeError(f"dither_dev must be a contiguous ({N}, 32) uint8 tensor")
+        if clipped is not None and (clipped.dim() != 1 or clipped.shape[0] < N or clipped.element_size() != 4
+                                    or not clipped.is_contiguous()):
+            raise RuntimeError(f"clipped must be a contiguous (>= {N},) 32-bit tensor")
+        rc = self.lib.flm_client_encode_mask_dev(
+            self.ctx, ctypes.c_void_p(x.data_ptr()), x.stride(0) if N > 1 else x.shape[1], N, p_i64(seg),
+            ctypes.c_void_p(seeds_dev.data_ptr() if K else 0), p_i8(signs), L, int(frac_bits), float(clip),
+            ctypes.c_void_p(dither_dev.data_ptr() if dither_dev is not None else 0), ctypes.c_void_p(out.data_ptr()),
+            out.stride(0) if N > 1 else out.shape[1], ctypes.c_void_p(clipped.data_ptr() if clipped is not None else 0),
+            self._stream_handle(stream))
+        self._check(rc, "flm_client_encode_mask_dev")
+        return out
+
+    def decode_sum_dev(self, total, out, L: int, frac_bits: int, count: int = 1, stream=None):
+        """out[:L] = decode(total[:L]) on CUDA tensors (32-bit in, float32 out); out may be a float32 view of total."""
+        import torch
+        if total.element_size() != 4 or total.numel() < L or out.dtype != torch.float32 or out.numel() < L \
+                or not total.is_contiguous() or not out.is_contiguous():
+            raise RuntimeError(f"total must hold >= {L} 32-bit words and out >= {L} float32, both contiguous")
+        rc = self.lib.flm_decode_sum_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), int(count),
+                                         ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
+        self._check(rc, "flm_decode_sum_dev")
         return out
 
     def prg_expand_dev(self, seeds_dev, out, L: int, slot0: int = 0, stream=None):

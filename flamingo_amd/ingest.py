@@ -27,7 +27,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import p_i8, p_u32, p_u8
+from ._lib import p_f32, p_i8, p_u32, p_u8
 
 
 class VectorStore:
@@ -121,6 +121,17 @@ class VectorStore:
         out = np.empty(self.L, np.uint32)
         self._check(self.lib.flm_store_unmask(self.h, p_u8(seeds), p_i8(signs), seeds.shape[0], p_u32(out)),
                     "flm_store_unmask")
+        return out
+
+    def unmask_f32(self, seeds, signs, frac_bits: int, count: int = 1) -> np.ndarray:
+        """unmask(), with every device's shard decoded in place before the copy to the host: the final sum
+        as the float32 mean of `count` contributors (flm_store_unmask_f32; the codec of client_encode_mask)."""
+        from .engine import _seeds_array, _signs_array
+        seeds = _seeds_array(seeds)
+        signs = _signs_array(signs, seeds.shape[0])
+        out = np.empty(self.L, np.float32)
+        self._check(self.lib.flm_store_unmask_f32(self.h, p_u8(seeds), p_i8(signs), seeds.shape[0], int(frac_bits),
+                                                  int(count), p_f32(out)), "flm_store_unmask_f32")
         return out
 
     def unmask_ms(self) -> float:

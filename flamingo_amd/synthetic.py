@@ -29,6 +29,13 @@ from . import params as P
 from .abides.flamingo.seeds import lagrange_at_zero, shamir_share
 
 
+def float_update(client_id: int, L: int, clip: float) -> np.ndarray:
+    """A client's float32 update for the agents' float_inputs option when none is set: L normal draws of
+    deviation clip / 8 from PCG64(client_id): nothing reaches +-clip, so the decoded mean is within half a step of theirs."""
+    rng = np.random.Generator(np.random.PCG64(int(client_id)))
+    return (rng.standard_normal(L) * (clip / 8.0)).astype(np.float32)
+
+
 def _g_rows(n: int) -> np.ndarray:
     return np.tile(np.frombuffer(C.point_bytes(C.G), np.uint8), (n, 1))
 

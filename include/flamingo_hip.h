@@ -143,6 +143,48 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
                         const uint8_t *d_seeds, const int8_t *signs, size_t L, uint32_t *d_out,
                         void *stream);
 
+/* ------------------------------------------------------ fixed-point codec */
+
+/* Float updates in, float mean out: the fixed-point codec around the ring sum, for the use the
+ * reference names at agent/flamingo/SA_ClientAgent.py:300-304 ("For machine learning, replace it
+ * with model weights").  Parameters: frac_bits f in 0..30; clip c, a finite float32 > 0.
+ *   encode(x): NaN -> 0; xc = min(max(x, -c), c); t = xc * 2^f in float32 (exact);
+ *     nearest (no dither seed): q = int32(rint(t)), ties to even;
+ *     stochastic (a 32-byte dither seed per client): ti = trunc(t), fr = |t - ti|,
+ *       thr = uint32(trunc(fr * 2^32)), r = PRG(dither_i)[l], q = int32(ti) + sgn(t) * [r < thr];
+ *     the ring word is uint32(q), two's complement.  An element is *clipped* when it was NaN or |x| > c.
+ *   decode(s, count) = float32(float64(int32(s)) / (float64(count) * 2^f)).
+ * Headroom for n contributors: n * ceil(c * 2^f) <= 2^31 - 1, or the sum can wrap.
+ *
+ * flm_codec_check: FLM_EINVAL for f outside 0..30, a clip that is not finite and positive, or
+ * n_clients < 1; FLM_ERANGE outside the headroom; needs no context and no device.  What a caller,
+ * or the agents' server (SA_ServiceAgent.py:538-540, 605: its final sum), calls with the real n. */
+int flm_codec_check(int frac_bits, float clip, int64_t n_clients);
+
+/* Client masking of float input, the encoding fused in (SA_ClientAgent.py:300-324):
+ *   out[i][l] = encode(x[i][l]) + sum_{k in [seg[i], seg[i+1])} signs[k] * PRG(seeds[k])[l]
+ * x: N x L row-major float32 (required); dither: N x 32 bytes, or NULL for nearest-even;
+ * clipped: N counts of clipped elements (written), or NULL.  The encoded word is never stored
+ * unmasked.  flm_client_mask's rules for seg and signs; the codec's rules with n = 1. */
+int flm_client_encode_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                           const int8_t *signs, size_t L, int frac_bits, float clip, const uint8_t *dither,
+                           uint32_t *out, uint32_t *clipped);
+/* The same on device buffers (SA_ClientAgent.py:300-324), enqueued on `stream` (NULL: the null
+ * stream); nothing is synchronised.  seg and signs are host arrays; x rows are x_pitch floats
+ * apart, out rows out_pitch words (each a multiple of 4 and >= round_up(L, 4)); x and out 16-byte
+ * aligned.  Whatever the padding of an x row holds is not read as input.  d_clipped (N words or
+ * NULL) is zeroed on the stream first. */
+int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                               const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
+                               const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
+                               void *stream);
+/* out[l] = decode(sum[l], count): the server's final sum (SA_ServiceAgent.py:538-540, 605) as the
+ * mean of `count` contributors; count = 1 gives the sum.  FLM_EINVAL for count < 1 or f outside 0..30. */
+int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, int64_t count, float *out);
+/* The same on device buffers (SA_ServiceAgent.py:538-540, 605), 16-byte aligned; d_out may alias d_sum. */
+int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, int64_t count, float *d_out,
+                       void *stream);
+
 /* Device-resident PRG expansion: d_out[k*pitch + l] = PRG(seed k)[slot0 + l]. */
 int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, uint64_t slot0,
                        uint32_t *d_out, size_t pitch, void *stream);
@@ -507,6 +549,11 @@ int flm_store_partial(flm_store *st);
 int flm_store_partial_wait(flm_store *st, float *gpu_ms);
 int flm_store_partial_host(flm_store *st, uint32_t *out);
 int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out);
+/* flm_store_unmask with each device's slot shard decoded in place (flm_decode_sum_dev) before its copy to the
+ * host: out[0..L) = decode(final sum, count), the mean of `count` contributors as float32
+ * (SA_ServiceAgent.py:538-540, 605 and the codec above; SA_ClientAgent.py:300-324 made the input). */
+int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, int frac_bits,
+                         int64_t count, float *out);
 /* Device time (ms, rank 0's stream) of the last flm_store_unmask, from its seed upload to the end of
  * its copy of final_sum to the host: the part of the call's wall time the GPU accounts for. */
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms);

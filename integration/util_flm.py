@@ -26,6 +26,7 @@ _lib = ctypes.CDLL(os.environ.get("FLM_LIB", "libflamingo_hip.so"))
 _vp, _int, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _u8p, _i8p, _u32p, _i64p = (ctypes.POINTER(t) for t in (ctypes.c_uint8, ctypes.c_int8, ctypes.c_uint32,
                                                          ctypes.c_int64))
+_f32p = ctypes.POINTER(ctypes.c_float)
 for _name, _res, _args in (
         ("flm_init", _int, [ctypes.POINTER(_vp), _int]),
         ("flm_last_error", ctypes.c_char_p, [_vp]),
@@ -48,7 +49,12 @@ for _name, _res, _args in (
         ("flm_store_add", _int, [_vp, ctypes.c_int64, _vp, _sz]),
         ("flm_store_partial", _int, [_vp]),
         ("flm_store_unmask", _int, [_vp, _u8p, _i8p, _int, _u32p]),
+        ("flm_store_unmask_f32", _int, [_vp, _u8p, _i8p, _int, _int, ctypes.c_int64, _f32p]),
         ("flm_store_reset", _int, [_vp]),
+        ("flm_codec_check", _int, [_int, ctypes.c_float, ctypes.c_int64]),
+        ("flm_client_encode_mask", _int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _u8p, _u32p,
+                                          _u32p]),
+        ("flm_decode_sum", _int, [_vp, _u32p, _sz, _int, ctypes.c_int64, _f32p]),
         ("flm_hash_to_curve", _int, [_vp, _u8p, _u32p, _int, _u8p, _u32p]),
         ("flm_hash_to_curve_decimal", _int, [_vp, ctypes.c_uint32, _int, _u8p, _u32p])):
     _f = getattr(_lib, _name)
@@ -339,6 +345,45 @@ def client_mask(seeds, signs, L, x=None):
     return out
 
 
+def codec_check(frac_bits, clip, n_clients):
+    """Raise unless n_clients float updates of magnitude <= clip fit the 32-bit ring at frac_bits fractional
+    bits (n ceil(clip 2^frac_bits) <= 2^31 - 1): the server's check at set-up, with the real n."""
+    _check(_lib.flm_codec_check(int(frac_bits), float(clip), int(n_clients)))
+
+
+def client_encode_mask(seeds, signs, L, x, frac_bits, clip, dither=None):
+    """client_mask for a float32 update x ("For machine learning, replace it with model weights",
+    SA_ClientAgent.py:300-304): encode(x) + sum_k signs[k] * PRG(seeds[k]) with the fixed-point encoding
+    (clip to +-clip, frac_bits fractional bits; nearest-even, or stochastic with a 32-byte dither seed) fused
+    into the masking of SA_ClientAgent.py:304-324.  Returns (uint32[L], number of clipped elements)."""
+    seg = np.array([0, len(seeds)], np.int64)
+    sd, sg, K = _seed_arrays(seeds, signs)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.shape != (L,):
+        raise RuntimeError("vector length error")
+    dp = None
+    if dither is not None:
+        if len(dither) != 32:
+            raise RuntimeError("the dither seed must be 32 bytes")
+        d = np.frombuffer(bytes(dither), np.uint8).copy()
+        dp = d.ctypes.data_as(_u8p)
+    out, clipped = np.empty(L, np.uint32), np.zeros(1, np.uint32)
+    _check(_lib.flm_client_encode_mask(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p),
+                                       sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), L, int(frac_bits), float(clip),
+                                       dp, out.ctypes.data_as(_u32p), clipped.ctypes.data_as(_u32p)))
+    return out, int(clipped[0])
+
+
+def decode_sum(total, frac_bits, count=1):
+    """final_sum (SA_ServiceAgent.py:538-540, 605) as the float32 mean of `count` contributors:
+    float32(int32(total) / (count 2^frac_bits))."""
+    total = np.ascontiguousarray(total, dtype=np.uint32)
+    out = np.empty(total.shape[0], np.float32)
+    _check(_lib.flm_decode_sum(_context(), total.ctypes.data_as(_u32p), total.shape[0], int(frac_bits), int(count),
+                               out.ctypes.data_as(_f32p)))
+    return out
+
+
 class VectorStore:
     """The server's VECTOR bodies on the GPU(s) from arrival to final_sum (flm_store_*): hand each
     body to add() in receiveMessage (:205-210), call partial() in report_process (:346-350) and
@@ -388,6 +433,15 @@ class VectorStore:
         out = np.empty(self.L, np.uint32)
         self._check(_lib.flm_store_unmask(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
                                           out.ctypes.data_as(_u32p)))
+        return out
+
+    def unmask_f32(self, seeds, signs, frac_bits, count=1):
+        """unmask() decoded on the GPU(s) before the copy to the host: the float32 mean of `count`
+        contributors (:538-540, :605, and the codec of client_encode_mask)."""
+        sd, sg, K = _seed_arrays(seeds, signs)
+        out = np.empty(self.L, np.float32)
+        self._check(_lib.flm_store_unmask_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
+                                              int(frac_bits), int(count), out.ctypes.data_as(_f32p)))
         return out
 
     def reset(self):
