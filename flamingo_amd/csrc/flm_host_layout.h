@@ -1,7 +1,8 @@
 // flm_host_layout.h -- where each array of a host-pointer call goes (HostCopies, flm_runtime.hip),
 // and how a large one is cut into staging-buffer pieces.  Plain C++ with no HIP in it, so the rules
-// are checked on the CPU (tests/test_host_layout_cpu.py, tools/planner_check.cpp).  Which arrays a batch
-// crypto call declares, and in which of the context's buffers, is flm_call_args.h (tools/args_check.cpp).
+// are checked on the CPU (tests/test_host_layout_cpu.py, tools/planner_check.cpp).  Which arrays a call
+// declares -- the round path's and the batch crypto calls' alike -- at which width, rows and pitches, and in
+// which of the context's buffers, is flm_call_args.h (tools/args_check.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,7 +1,8 @@
 // flm_internal.h -- the kernel launchers (flm_kernels.hip, flm_p256.hip) and the host-runtime hooks (flm::rt)
 // that flm_runtime.hip shares with flm_comm.hip and flm_store.hip.  The records the launchers take (Item, SeedRec,
 // ItemsVariant) are in the HIP-free flm_items.h, filled by flm_planner.h; the argument rules and array lists of the
-// batch crypto calls whose launchers are declared here are in the HIP-free flm_call_args.h.  Not part of the public ABI.
+// calls whose launchers are declared here (the round path's and the batch crypto calls') are in the HIP-free
+// flm_call_args.h.  Not part of the public ABI.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>

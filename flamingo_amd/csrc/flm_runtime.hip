@@ -275,7 +275,24 @@ int fail(flm_ctx *ctx, int code, const char *fmt, ...) {
                         __LINE__);                                                                    \
     } while (0)
 
-inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
+using flm::rt::round_up;
+
+// A rule's answer (flm_call_args.h) as a refusal: 0, or `code` with the rule's text as the error.
+int refuse(flm_ctx *ctx, const char *why, int code = FLM_EINVAL) { return why ? fail(ctx, code, "%s", why) : 0; }
+int check_range(flm_ctx *ctx, uint64_t slot0, uint64_t n) {
+    return refuse(ctx, flm::rt::slot_range_error(slot0, n), FLM_ERANGE);
+}
+int check_codec(flm_ctx *ctx, int frac_bits, float clip, int64_t n) {
+    bool headroom = false;
+    const char *why = flm::rt::codec_error(frac_bits, clip, n, &headroom);
+    return refuse(ctx, why, headroom ? FLM_ERANGE : FLM_EINVAL);
+}
+int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
+                         size_t mask_hi, uint64_t prg_slot0, const uint32_t *d_out) {
+    bool range = false;
+    const char *why = flm::rt::aggregate_error(d_rows, row_pitch, N, K, L, mask_lo, mask_hi, prg_slot0, d_out, &range);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
 
 // The tuning keys: the context member behind each, the values it takes and the refusal of any
 // other (which may print the value).  flm_set_tuning and flm_get_tuning read this one table.
@@ -386,16 +403,49 @@ void stage_prealloc(flm_ctx *ctx) {
     }
 }
 
-// Copy the slot's first `bytes` host bytes to its device buffer on `s`.
-hipError_t stage_upload(StageSlot *slot, size_t bytes, hipStream_t s) {
-    return bytes ? hipMemcpyAsync(slot->dev.p, slot->host, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-}
-
 // The slot is free again once the work enqueued on `s` so far (its readers) has completed.
 hipError_t stage_commit(StageSlot *slot, hipStream_t s) {
     hipError_t e = hipEventRecord(slot->done, s);
     if (e == hipSuccess) slot->busy = true;
     return e;
+}
+
+// The small tables a *_dev call's kernels read (seg, signs, work items), each `bytes` bytes from `host` or,
+// with host NULL, of the byte `fill`.  stage_put packs them back to back into a staging slot that no
+// queued work reads (stage_acquire: the host does not wait while the pool can grow) and uploads them on
+// `s` as one copy; dev[i] is the device address of piece i.
+struct StagePiece {
+    const void *host;
+    size_t bytes;
+    uint8_t fill;
+};
+struct Staged {
+    StageSlot *slot = nullptr;
+    const uint8_t *dev[2] = {nullptr, nullptr};
+};
+int stage_put(flm_ctx *ctx, std::initializer_list<StagePiece> pieces, hipStream_t s, Staged *up) {
+    assert(pieces.size() <= 2);
+    size_t total = 0;
+    for (const StagePiece &p : pieces) total += p.bytes;
+    int rc = 0;
+    up->slot = stage_acquire(ctx, std::max<size_t>(total, 1), &rc);  // an empty table still has an address
+    if (!up->slot) return rc;
+    uint8_t *h = static_cast<uint8_t *>(up->slot->host);
+    size_t at = 0, i = 0;
+    for (const StagePiece &p : pieces) {
+        up->dev[i++] = up->slot->dev.as<uint8_t>() + at;
+        if (p.bytes && p.host) std::memcpy(h + at, p.host, p.bytes);
+        else if (p.bytes) std::memset(h + at, p.fill, p.bytes);
+        at += p.bytes;
+    }
+    if (total) FLM_HIP(ctx, hipMemcpyAsync(up->slot->dev.p, h, total, hipMemcpyHostToDevice, s));
+    return 0;
+}
+// After the launches that read the tables, with `rc` what became of them: the slot is busy until the work
+// enqueued so far has run, whether or not it all got enqueued.  -> rc, or the failure to mark the slot.
+int stage_done(flm_ctx *ctx, const Staged &up, hipStream_t s, int rc) {
+    FLM_HIP(ctx, stage_commit(up.slot, s));
+    return rc;
 }
 
 // The items go through a staging slot on `s` and the plan records `ready` for launches on
@@ -469,24 +519,6 @@ Plan *aggregate_plan(flm_ctx *ctx, uint64_t pitch, int N, int K, uint64_t L, uin
     plan->last_use = ++ctx->plan_clock;
     ctx->plans[key] = plan;
     return plan;
-}
-
-bool signs_ok(const int8_t *signs, int K, int *nneg) {
-    int n = 0;
-    for (int k = 0; k < K; ++k) {
-        if (signs[k] == -1) ++n;
-        else if (signs[k] != 1) return false;
-    }
-    if (nneg) *nneg = n;
-    return true;
-}
-
-// The one rule for a PRG window of n slots from slot0 (flm::plan::slot_range_ok), as an error.
-int check_range(flm_ctx *ctx, uint64_t slot0, uint64_t n) {
-    if (!flm::plan::slot_range_ok(slot0, n))
-        return fail(ctx, FLM_ERANGE, "PRG slots [%llu, +%llu) end beyond 2^36 (block counter high word must stay 0)",
-                    (unsigned long long)slot0, (unsigned long long)n);
-    return 0;
 }
 
 // No read or write of `t` on a stream other than s is still pending: s may rewrite it at once.
@@ -770,12 +802,11 @@ int upload_rows(flm_ctx *ctx, const uint32_t *const *rows, int N, size_t L, uint
 // Copies of kStageBytes or more skip it and stream through the context's two staging buffers instead
 // (inputs in begin(), outputs in finish()), so no call pins more host memory than its small copies
 // plus 2 x 32 MiB, whatever its size (a 962 x 2^20 prg_expand returns 4 GiB).
-// A call declares every array it moves (in(), out()), then begin(), then launches its kernels on the
-// handles' pointers and pitches, then finish().  The routes and the bounce layout come from the
-// declarations alone (flm::rt::host_layout): no call site adds up bytes or chooses a path.
+// A call declares the arrays it moves, as its list in flm_call_args.h (declare()), then begin(), then runs
+// its *_dev twin on the arrays' device pointers and pitches, then finish().  The routes and the bounce layout
+// come from the list alone (flm::rt::host_layout): no call site adds up bytes, picks a buffer or chooses a path.
 class HostCopies {
   public:
-    enum Place { kDevice, kMayRunInPlace };
     // A declared array.  After begin(): `dev`, rows `pitch` bytes apart, is where the kernel reads or
     // writes it -- the named DevBuf at the declared pitch, or the bounce buffer itself in place.
     struct Span {
@@ -787,29 +818,23 @@ class HostCopies {
     HostCopies(flm_ctx *ctx, hipStream_t s) : ctx_(ctx), s_(s) {}
     // an error return between begin() and finish() leaves nothing queued on the bounce buffer
     ~HostCopies() { if (open_) (void)hipStreamSynchronize(s_); }
-    // rows x width bytes, host rows at h_pitch; through device memory they land in `buf` at d_pitch
-    const Span *in(const void *h, size_t h_pitch, size_t width, size_t rows, DevBuf &buf, size_t d_pitch, Place p = kDevice) {
-        return add(const_cast<void *>(h), h_pitch, width, rows, buf, d_pitch, false, p);
-    }
-    const Span *out(void *h, size_t h_pitch, size_t width, size_t rows, DevBuf &buf, size_t d_pitch, Place p = kDevice) {
-        return add(h, h_pitch, width, rows, buf, d_pitch, true, p);
-    }
-    const Span *in(const void *h, size_t n, DevBuf &buf, Place p = kDevice) { return in(h, n, n, 1, buf, n, p); }
-    const Span *out(void *h, size_t n, DevBuf &buf, Place p = kDevice) { return out(h, n, n, 1, buf, n, p); }
-    // A batch crypto call: every array of its list (flm_call_args.h) that is present, with the host
-    // pointer at the same position; after begin(), dev<T>(i) is where the kernel finds array i (NULL: absent).
+    // Every array of the call's list (flm_call_args.h) that is present, with the host pointer at the same
+    // position: rows x width bytes, host rows at h_pitch; through device memory they land in the list's
+    // scratch buffer at d_pitch.  After begin(), dev<T>(i) is where the kernel finds array i (NULL: absent)
+    // and pitch(i) the bytes between its rows there.
     void declare(const flm::rt::ArgList &l, std::initializer_list<const void *> host) {
         assert((int)host.size() == l.n);
         twice_ = flm::rt::names_slot_twice(l);
         for (int i = 0; i < l.n; ++i) {
             const flm::rt::Arg &a = l.a[i];
             arg_[i] = !a.present ? nullptr
-                                 : add(const_cast<void *>(host.begin()[i]), a.bytes, a.bytes, 1, ctx_->*kSlot[a.slot], a.bytes,
-                                       a.is_out, a.in_place ? kMayRunInPlace : kDevice);
+                                 : add(const_cast<void *>(host.begin()[i]), a.h_pitch, a.width, a.rows, ctx_->*kSlot[a.slot],
+                                       a.d_pitch, a.is_out, a.in_place ? kMayRunInPlace : kDevice);
         }
     }
     template <class T>
     T *dev(int i) const { return arg_[i] ? arg_[i]->as<T>() : nullptr; }
+    size_t pitch(int i) const { return arg_[i]->pitch; }
     // Lays the call out, grows the bounce buffer and the DevBufs, copies the inputs into pinned memory
     // and enqueues their DMAs (large ones stream through the staging ring at once).
     int begin() {
@@ -868,11 +893,13 @@ class HostCopies {
     void hand_over() { open_ = false; }
 
   private:
+    enum Place { kDevice, kMayRunInPlace };
     static constexpr int kMaxSpans = flm::rt::kMaxArgs;
     // flm::rt::Slot -> the context's buffer of that name
     static constexpr DevBuf flm_ctx::*kSlot[flm::rt::kSlots] = {
         &flm_ctx::ec_in,  &flm_ctx::ec_base,  &flm_ctx::ec_scal,  &flm_ctx::ec_out,
-        &flm_ctx::ec_dig, &flm_ctx::ec_flags, &flm_ctx::bytes_in, &flm_ctx::bytes_out};
+        &flm_ctx::ec_dig, &flm_ctx::ec_flags, &flm_ctx::bytes_in, &flm_ctx::bytes_out,
+        &flm_ctx::rows,   &flm_ctx::out,      &flm_ctx::seeds,    &flm_ctx::signs};
     struct Decl : Span {  // a declaration behind its handle; its width, rows and route are lay_[i], as host_layout takes them
         void *host;
         size_t h_pitch, d_pitch;
@@ -945,51 +972,56 @@ class HostCopies {
     bool open_ = false;  // begin() has queued work or handed out in-place memory, finish() has not waited yet
 };
 
-// K seeds and signs into ctx->seeds and ctx->signs (K = 0: both still allocated, nothing copied)
-void declare_seeds(flm_ctx *ctx, HostCopies &hc, const uint8_t *seeds, const int8_t *signs, int K) {
-    hc.in(seeds, (size_t)K * 32, ctx->seeds);
-    hc.in(signs, (size_t)K, ctx->signs);
-}
-
-// Client masking / expansion (flm::plan::plan_rows_jobs plans it): stages the items and the signs,
-// builds the seed table and launches.  signs: K host signs, or NULL for all +1 (expansion).
-// The items and the signs travel in one staging slot (StageSlot): nothing here waits on the host.
+// Client masking / expansion (flm::plan::plan_rows_jobs plans it): stages the items and the signs
+// (stage_put), builds the seed table and launches.  signs: K host signs, or NULL for all +1 (expansion).
 int run_rows_jobs(flm_ctx *ctx, const uint32_t *d_x, uint64_t pitch, int N, const int64_t *seg, const int8_t *signs,
                   const uint8_t *d_seeds, int K, uint32_t base_bias, size_t L, uint64_t slot0, uint32_t *d_out,
                   hipStream_t s) {
     std::vector<Item> items;
     const PlanShape shape = flm::plan::plan_rows_jobs(d_x != nullptr, pitch, N, seg, signs, K, base_bias, L, slot0, items);
     const int n_items = (int)items.size();
-    const size_t item_bytes = items.size() * sizeof(Item);
-    int rc = 0;
-    StageSlot *slot = stage_acquire(ctx, item_bytes + std::max(K, 1), &rc);
-    if (!slot) return rc;
-    uint8_t *h = static_cast<uint8_t *>(slot->host);
-    if (item_bytes) std::memcpy(h, items.data(), item_bytes);
-    if (K > 0) {
-        if (signs) std::memcpy(h + item_bytes, signs, (size_t)K);
-        else std::memset(h + item_bytes, 1, (size_t)K);
-    }
-    FLM_HIP(ctx, stage_upload(slot, item_bytes + (size_t)K, s));
-    const uint8_t *d = slot->dev.as<uint8_t>();
+    Staged up;
+    if (int rc = stage_put(ctx, {{items.data(), items.size() * sizeof(Item), 0}, {signs, (size_t)K, 1}}, s, &up)) return rc;
     SeedTable *table = nullptr;
-    rc = run_seed_schedule(ctx, d_seeds, reinterpret_cast<const int8_t *>(d + item_bytes), K, s, &table);
+    int rc = run_seed_schedule(ctx, d_seeds, reinterpret_cast<const int8_t *>(up.dev[1]), K, s, &table);
     if (!rc && shape.needs_zero) {
         const hipError_t e = hipMemsetAsync(d_out, 0, (size_t)N * pitch * sizeof(uint32_t), s);
         if (e != hipSuccess) rc = fail(ctx, FLM_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
     const int variant_id = flm::plan::pick_variant(ctx->tune_variant, shape);
     if (!rc && n_items) {
-        hipError_t e = flm::launch_items(shape.subtiles, variant_id, reinterpret_cast<const Item *>(d), n_items, d_x,
+        hipError_t e = flm::launch_items(shape.subtiles, variant_id, reinterpret_cast<const Item *>(up.dev[0]), n_items, d_x,
                                          pitch, table->recs.as<SeedRec>(), table->meta.as<uint32_t>(), d_out, s);
         if (e == hipSuccess) e = table_read(table, s);
         if (e != hipSuccess) rc = fail(ctx, FLM_EHIP, "items launch: %s", hipGetErrorString(e));
     }
     if (table && (rc || !n_items)) table_cover(table, s);  // no read recorded after the table's write
-    // the slot is busy until the work enqueued so far has run, whether or not it all got enqueued
-    FLM_HIP(ctx, stage_commit(slot, s));
-    if (rc) return rc;
+    if ((rc = stage_done(ctx, up, s, rc))) return rc;
     set_last_plan(ctx, n_items, flm::kWaveSlots * shape.subtiles, shape.atomics, variant_id);
+    return 0;
+}
+
+// A round on host rows: flm_aggregate_unmask (out: the caller's array; the call returns with it written)
+// and one rank's share of a group's round (out NULL: the sum stays in d_out on the device, and the group
+// synchronises every rank before its call returns).
+int host_round(flm_ctx *ctx, const uint32_t *const *rows, int N, const uint8_t *seeds, const int8_t *signs, int K,
+               size_t L, size_t mask_lo, size_t mask_hi, uint32_t *out, uint32_t *d_out) {
+    if (N < 0 || K < 0) return fail(ctx, FLM_EINVAL, "negative N or K");
+    if ((N > 0 && !rows) || (!out && !d_out)) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (K > 0 && (!seeds || !signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (int rc = refuse(ctx, flm::rt::signs_error(signs, K))) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
+    FLM_ON_DEVICE(ctx);
+    const uint64_t pitch = round_up(L, 64);
+    if (int rc = upload_rows(ctx, rows, N, L, pitch)) return rc;
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::aggregate_unmask_args(K, L, out != nullptr), {seeds, signs, out});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_aggregate_unmask_dev(ctx, ctx->rows.as<uint32_t>(), pitch, N, hc.dev<uint8_t>(0), hc.dev<int8_t>(1), K,
+                                          L, mask_lo, mask_hi, 0, out ? hc.dev<uint32_t>(2) : d_out, ctx->stream))
+        return rc;
+    if (out) return hc.finish();
+    hc.hand_over();
     return 0;
 }
 
@@ -1005,21 +1037,7 @@ void host_copy(flm_ctx *ctx, void *dst, const void *src, size_t n) { ctx->copies
 
 int host_round_async(flm_ctx *ctx, const uint32_t *const *rows, int N, const uint8_t *seeds, const int8_t *signs,
                      int K, size_t L, size_t mask_lo, size_t mask_hi, uint32_t *d_out) {
-    if (N < 0 || K < 0) return fail(ctx, FLM_EINVAL, "negative N or K");
-    if ((N > 0 && !rows) || (K > 0 && (!seeds || !signs)) || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (!signs_ok(signs, K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, 0, L)) return rc;
-    FLM_ON_DEVICE(ctx);
-    const uint64_t pitch = round_up(L, 64);
-    if (int rc = upload_rows(ctx, rows, N, L, pitch)) return rc;
-    HostCopies hc(ctx, ctx->stream);
-    declare_seeds(ctx, hc, seeds, signs, K);
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_aggregate_unmask_dev(ctx, ctx->rows.as<uint32_t>(), pitch, N, ctx->seeds.as<uint8_t>(),
-                                          ctx->signs.as<int8_t>(), K, L, mask_lo, mask_hi, 0, d_out, ctx->stream))
-        return rc;
-    hc.hand_over();  // the group synchronises every rank before its call returns
-    return 0;
+    return host_round(ctx, rows, N, seeds, signs, K, L, mask_lo, mask_hi, nullptr, d_out);
 }
 
 }  // namespace rt
@@ -1110,45 +1128,15 @@ const char *flm_last_error(const flm_ctx *ctx) {
 int flm_aggregate_unmask(flm_ctx *ctx, const uint32_t *const *rows, int N, const uint8_t *seeds, const int8_t *signs,
                          int K, size_t L, uint32_t *out) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (N < 0 || K < 0) return fail(ctx, FLM_EINVAL, "negative N or K");
-    if (L == 0) return 0;
-    if (!out || (N > 0 && !rows) || (K > 0 && (!seeds || !signs))) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (!signs_ok(signs, K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    if (int rc = check_range(ctx, 0, L)) return rc;
-    FLM_ON_DEVICE(ctx);
-    const uint64_t pitch = round_up(L, 64);
-    if (int rc = upload_rows(ctx, rows, N, L, pitch)) return rc;
-    HostCopies hc(ctx, ctx->stream);
-    declare_seeds(ctx, hc, seeds, signs, K);
-    const HostCopies::Span *y = hc.out(out, L * sizeof(uint32_t), ctx->out);
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_aggregate_unmask_dev(ctx, ctx->rows.as<uint32_t>(), pitch, N, ctx->seeds.as<uint8_t>(),
-                                          ctx->signs.as<int8_t>(), K, L, 0, L, 0, y->as<uint32_t>(), ctx->stream))
-        return rc;
-    return hc.finish();
-}
-
-static int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pitch, int N, int K, size_t L,
-                                size_t mask_lo, size_t mask_hi, uint64_t prg_slot0, const uint32_t *d_out) {
-    if (N < 0 || K < 0) return fail(ctx, FLM_EINVAL, "negative N or K");
-    if (N > 0 && (row_pitch % 4 != 0 || row_pitch < round_up(L, 4)))
-        return fail(ctx, FLM_EINVAL, "row_pitch %zu must be a multiple of 4 and >= round_up(L=%zu, 4)", row_pitch, L);
-    if ((N > 0 && ((uintptr_t)d_rows & 15)) || ((uintptr_t)d_out & 15))
-        return fail(ctx, FLM_EINVAL, "rows and out must be 16-byte aligned");
-    if (mask_hi > L || mask_lo > mask_hi)
-        return fail(ctx, FLM_EINVAL, "mask window [%zu,%zu) outside [0,%zu)", mask_lo, mask_hi, L);
-    if ((mask_hi > mask_lo && mask_lo % 16) || prg_slot0 % 16)
-        return fail(ctx, FLM_EINVAL, "mask_lo and prg_slot0 must be multiples of 16");
-    if (int rc = check_range(ctx, prg_slot0, mask_hi)) return rc;
-    if (N > 0 && !d_rows) return fail(ctx, FLM_EINVAL, "rows is NULL");
-    if (!d_out) return fail(ctx, FLM_EINVAL, "out is NULL");
-    return 0;
+    if (N >= 0 && K >= 0 && L == 0) return 0;  // no slots: nothing read, nothing written
+    if (!out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    return host_round(ctx, rows, N, seeds, signs, K, L, 0, L, out, nullptr);
 }
 
 int flm_seed_table_dev(flm_ctx *ctx, const uint8_t *d_seeds, const int8_t *d_signs, int K, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (K < 0) return fail(ctx, FLM_EINVAL, "negative K");
-    if (K > 0 && (!d_seeds || !d_signs)) return fail(ctx, FLM_EINVAL, "seeds/signs NULL");
+    if (K > 0 && (!d_seeds || !d_signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
     SeedTable *t = nullptr;
@@ -1176,7 +1164,7 @@ int flm_aggregate_unmask_dev(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pi
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (L == 0) return 0;
     if (int rc = check_aggregate_args(ctx, d_rows, row_pitch, N, K, L, mask_lo, mask_hi, prg_slot0, d_out)) return rc;
-    if (K > 0 && (!d_seeds || !d_signs)) return fail(ctx, FLM_EINVAL, "seeds/signs NULL");
+    if (K > 0 && (!d_seeds || !d_signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
     int rc = 0;
@@ -1198,32 +1186,26 @@ int flm_aggregate_unmask_dev(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pi
     return rc;
 }
 
+// The round path's calls in their two forms.  Each host form: the rule it shares with its twin, its own
+// checks (what it must know before it reads an array or returns for an empty call), then its list of
+// arrays (flm_call_args.h) through HostCopies around the *_dev twin on the context's stream.  Which
+// sizes count as empty is one line per form (DESIGN.md has the table).
+
 int flm_client_mask(flm_ctx *ctx, const uint32_t *x, int N, const int64_t *seg, const uint8_t *seeds,
                     const int8_t *signs, size_t L, uint32_t *out) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
     if (N == 0 || L == 0) return 0;
-    if (!seg || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (seg[0] != 0) return fail(ctx, FLM_EINVAL, "seg[0] must be 0");
-    for (int i = 0; i < N; ++i)
-        if (seg[i + 1] < seg[i]) return fail(ctx, FLM_EINVAL, "seg must be non-decreasing");
-    const int64_t K = seg[N];
-    if (K > 0 && (!seeds || !signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
-    if (K > 0x7fffffff) return fail(ctx, FLM_EINVAL, "too many seeds");
-    if (!signs_ok(signs, (int)K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
+    int64_t K = 0;
+    if (int rc = refuse(ctx, flm::rt::client_args_error(out != nullptr, N, seg, seeds, signs, &K))) return rc;
     if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
-    const uint64_t pitch = round_up(L, 64);
-    // one client's call (c5: 4 MiB in, 4 MiB out) runs in place: the kernel reads x from and writes y to the pinned
-    // bounce buffer, so the link carries both at once instead of a DMA each way.  x and y: one shape, so one pitch
     HostCopies hc(ctx, ctx->stream);
-    const auto *hx = x ? hc.in(x, L * 4, L * 4, (size_t)N, ctx->rows, pitch * 4, HostCopies::kMayRunInPlace) : nullptr;
-    declare_seeds(ctx, hc, seeds, signs, (int)K);
-    const auto *hy = hc.out(out, L * 4, L * 4, (size_t)N, ctx->out, pitch * 4, HostCopies::kMayRunInPlace);
+    hc.declare(flm::rt::client_mask_args(N, K, L, x), {x, seeds, signs, out});
     if (int rc = hc.begin()) return rc;
-    assert(!hx || hx->pitch == hy->pitch);
-    if (int rc = flm_client_mask_dev(ctx, hx ? hx->as<const uint32_t>() : nullptr, hy->pitch / 4, N, seg,
-                                     ctx->seeds.as<uint8_t>(), signs, L, hy->as<uint32_t>(), ctx->stream))
+    assert(!x || hc.pitch(0) == hc.pitch(3));
+    if (int rc = flm_client_mask_dev(ctx, hc.dev<uint32_t>(0), hc.pitch(3) / 4, N, seg, hc.dev<uint8_t>(1), signs, L,
+                                     hc.dev<uint32_t>(3), ctx->stream))
         return rc;
     return hc.finish();
 }
@@ -1232,17 +1214,10 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
                         const uint8_t *d_seeds, const int8_t *signs, size_t L, uint32_t *d_out, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (N <= 0 || L == 0) return 0;
-    if (!seg || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (pitch % 4 || pitch < round_up(L, 4)) return fail(ctx, FLM_EINVAL, "pitch must be a multiple of 4 and >= L");
-    if (((uintptr_t)d_out & 15) || ((uintptr_t)d_x & 15)) return fail(ctx, FLM_EINVAL, "x/out must be 16-byte aligned");
-    // seg sizes the launch: a decreasing pair would wrap a seed count and read past the table
-    if (seg[0] != 0) return fail(ctx, FLM_EINVAL, "seg[0] must be 0");
-    for (int i = 0; i < N; ++i)
-        if (seg[i + 1] < seg[i]) return fail(ctx, FLM_EINVAL, "seg must be non-decreasing");
-    const int64_t K = seg[N];
-    if (K > 0x7fffffff) return fail(ctx, FLM_EINVAL, "too many seeds");
-    if (K > 0 && (!d_seeds || !signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
-    if (!signs_ok(signs, (int)K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
+    int64_t K = 0;  // seg sizes the launch
+    if (int rc = refuse(ctx, flm::rt::client_args_error(d_out != nullptr, N, seg, d_seeds, signs, &K))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
     if (int rc = check_range(ctx, 0, L)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
@@ -1250,17 +1225,12 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
     // kernel, one workgroup per (client, 256-slot tile), instead of a seed schedule + one 1024-thread
     // workgroup per client row.  seg and signs travel in ONE host-to-device copy.
     if (N <= 65535 /* grid.y */ && (ctx->tune_small == 2 || (ctx->tune_small == 1 && (uint64_t)K * L <= (1ull << 26)))) {
-        const size_t seg_bytes = (size_t)(N + 1) * sizeof(int64_t), need = seg_bytes + (size_t)K;
-        int rc = 0;
-        StageSlot *slot = stage_acquire(ctx, need, &rc);  // never waits on queued work (StageSlot)
-        if (!slot) return rc;
-        std::memcpy(slot->host, seg, seg_bytes);
-        if (K > 0) std::memcpy(static_cast<uint8_t *>(slot->host) + seg_bytes, signs, (size_t)K);
-        FLM_HIP(ctx, stage_upload(slot, need, s));
-        const hipError_t e = flm::launch_small_client_mask(
-            d_x, pitch, N, slot->dev.as<int64_t>(), d_seeds,
-            reinterpret_cast<const int8_t *>(slot->dev.as<uint8_t>() + seg_bytes), L, d_x ? 0u : 1u, d_out, s);
-        FLM_HIP(ctx, stage_commit(slot, s));
+        Staged up;
+        if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
+        const hipError_t e = flm::launch_small_client_mask(d_x, pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
+                                                           reinterpret_cast<const int8_t *>(up.dev[1]), L, d_x ? 0u : 1u,
+                                                           d_out, s);
+        if (int rc = stage_done(ctx, up, s, 0)) return rc;
         FLM_HIP(ctx, e);
         set_last_plan(ctx, (int)(((L + 255) / 256) * (uint64_t)N), 256, 0, kSmallRoundVariant);
         return 0;
@@ -1269,59 +1239,25 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
     return run_rows_jobs(ctx, d_x, pitch, N, seg, signs, d_seeds, (int)K, 1u, L, 0, d_out, s);
 }
 
-// The codec's parameter and headroom rule: n ceil(clip 2^f) <= 2^31 - 1.  clip 2^f is exact in double (a float
-// times a power of two), so is its ceiling, and the product is compared in integers.
-static int codec_check(flm_ctx *ctx, int frac_bits, float clip, int64_t n) {
-    if (frac_bits < 0 || frac_bits > 30) return fail(ctx, FLM_EINVAL, "frac_bits %d outside 0..30", frac_bits);
-    if (!(clip > 0.0f) || !std::isfinite(clip)) return fail(ctx, FLM_EINVAL, "clip must be finite and positive");
-    if (n < 1) return fail(ctx, FLM_EINVAL, "a count of contributors must be at least 1");
-    const double m = std::ceil((double)clip * std::ldexp(1.0, frac_bits));
-    if (m > 2147483647.0 || (uint64_t)n > 2147483647ull / (uint64_t)m)
-        return fail(ctx, FLM_ERANGE, "%lld contributors of magnitude up to %.0f can wrap the 32-bit sum", (long long)n, m);
-    return 0;
-}
-
-int flm_codec_check(int frac_bits, float clip, int64_t n_clients) { return codec_check(nullptr, frac_bits, clip, n_clients); }
-
-// flm_client_mask[_dev]'s rules for seg and signs; *K_out = seg[N]
-static int check_seg_signs(flm_ctx *ctx, int N, const int64_t *seg, const int8_t *signs, int64_t *K_out) {
-    if (seg[0] != 0) return fail(ctx, FLM_EINVAL, "seg[0] must be 0");
-    for (int i = 0; i < N; ++i)
-        if (seg[i + 1] < seg[i]) return fail(ctx, FLM_EINVAL, "seg must be non-decreasing");
-    const int64_t K = seg[N];
-    if (K > 0x7fffffff) return fail(ctx, FLM_EINVAL, "too many seeds");
-    if (K > 0 && !signs) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
-    if (!signs_ok(signs, (int)K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
-    *K_out = K;
-    return 0;
-}
+int flm_codec_check(int frac_bits, float clip, int64_t n_clients) { return check_codec(nullptr, frac_bits, clip, n_clients); }
 
 int flm_client_encode_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
                            const int8_t *signs, size_t L, int frac_bits, float clip, const uint8_t *dither,
                            uint32_t *out, uint32_t *clipped) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    if (int rc = codec_check(ctx, frac_bits, clip, 1)) return rc;
+    if (int rc = check_codec(ctx, frac_bits, clip, 1)) return rc;
     if (N == 0 || L == 0) return 0;
-    if (!x || !seg || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
     int64_t K = 0;
-    if (int rc = check_seg_signs(ctx, N, seg, signs, &K)) return rc;
-    if (K > 0 && !seeds) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
     if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
-    const uint64_t pitch = round_up(L, 64);
-    // as flm_client_mask: one client's call reads x from and writes y to the pinned bounce buffer in place
     HostCopies hc(ctx, ctx->stream);
-    const auto *hx = hc.in(x, L * 4, L * 4, (size_t)N, ctx->rows, pitch * 4, HostCopies::kMayRunInPlace);
-    hc.in(seeds, (size_t)K * 32, ctx->seeds);
-    const auto *hd = dither ? hc.in(dither, (size_t)N * 32, ctx->bytes_in) : nullptr;
-    const auto *hy = hc.out(out, L * 4, L * 4, (size_t)N, ctx->out, pitch * 4, HostCopies::kMayRunInPlace);
-    const auto *hcl = clipped ? hc.out(clipped, (size_t)N * 4, ctx->bytes_out) : nullptr;
+    hc.declare(flm::rt::client_encode_mask_args(N, K, L, dither, clipped), {x, seeds, dither, out, clipped});
     if (int rc = hc.begin()) return rc;
-    if (int rc = flm_client_encode_mask_dev(ctx, hx->as<const float>(), hx->pitch / 4, N, seg, ctx->seeds.as<uint8_t>(),
-                                            signs, L, frac_bits, clip, hd ? hd->as<const uint8_t>() : nullptr,
-                                            hy->as<uint32_t>(), hy->pitch / 4, hcl ? hcl->as<uint32_t>() : nullptr,
-                                            ctx->stream))
+    if (int rc = flm_client_encode_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs, L,
+                                            frac_bits, clip, hc.dev<uint8_t>(2), hc.dev<uint32_t>(3), hc.pitch(3) / 4,
+                                            hc.dev<uint32_t>(4), ctx->stream))
         return rc;
     return hc.finish();
 }
@@ -1331,62 +1267,49 @@ int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, i
                                const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
                                void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = codec_check(ctx, frac_bits, clip, 1)) return rc;
+    if (int rc = check_codec(ctx, frac_bits, clip, 1)) return rc;
     if (N <= 0 || L == 0) return 0;
-    if (!d_x || !seg || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (x_pitch % 4 || x_pitch < round_up(L, 4) || out_pitch % 4 || out_pitch < round_up(L, 4))
-        return fail(ctx, FLM_EINVAL, "pitch must be a multiple of 4 and >= L");
-    if (((uintptr_t)d_out & 15) || ((uintptr_t)d_x & 15)) return fail(ctx, FLM_EINVAL, "x/out must be 16-byte aligned");
     int64_t K = 0;
-    if (int rc = check_seg_signs(ctx, N, seg, signs, &K)) return rc;
-    if (K > 0 && !d_seeds) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (int rc = refuse(ctx, flm::rt::client_args_error(d_x && d_out, N, seg, d_seeds, signs, &K))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
     if (int rc = check_range(ctx, 0, L)) return rc;
-    if (flm::encode_mask_groups(N, L) > 0x7fffffffull)
-        return fail(ctx, FLM_EINVAL, "N=%d x %zu slots: more than 2^31 - 1 1024-slot tiles", N, L);
+    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, L)))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
-    // seg and signs travel in one host-to-device copy through a staging slot (never waits on queued work)
-    const size_t seg_bytes = (size_t)(N + 1) * sizeof(int64_t), need = seg_bytes + (size_t)K;
-    int rc = 0;
-    StageSlot *slot = stage_acquire(ctx, need, &rc);
-    if (!slot) return rc;
-    std::memcpy(slot->host, seg, seg_bytes);
-    if (K > 0) std::memcpy(static_cast<uint8_t *>(slot->host) + seg_bytes, signs, (size_t)K);
-    FLM_HIP(ctx, stage_upload(slot, need, s));
+    Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
+    if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
     hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
     if (e == hipSuccess)
-        e = flm::launch_encode_mask(d_x, x_pitch, N, slot->dev.as<int64_t>(), d_seeds,
-                                    reinterpret_cast<const int8_t *>(slot->dev.as<uint8_t>() + seg_bytes), d_dither, L,
-                                    frac_bits, clip, d_out, out_pitch, d_clipped, s);
-    FLM_HIP(ctx, stage_commit(slot, s));
+        e = flm::launch_encode_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
+                                    reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, L, frac_bits, clip, d_out,
+                                    out_pitch, d_clipped, s);
+    if (int rc = stage_done(ctx, up, s, 0)) return rc;
     FLM_HIP(ctx, e);
     return 0;
 }
 
 int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, int64_t count, float *out) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (frac_bits < 0 || frac_bits > 30) return fail(ctx, FLM_EINVAL, "frac_bits %d outside 0..30", frac_bits);
-    if (count < 1) return fail(ctx, FLM_EINVAL, "count must be at least 1");
+    if (int rc = refuse(ctx, flm::rt::decode_error(frac_bits, count))) return rc;
     if (L == 0) return 0;
     if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
     HostCopies hc(ctx, ctx->stream);
-    const auto *hs = hc.in(sum, L * 4, ctx->rows, HostCopies::kMayRunInPlace);
-    const auto *ho = hc.out(out, L * 4, ctx->out, HostCopies::kMayRunInPlace);
+    hc.declare(flm::rt::decode_sum_args(L), {sum, out});
     if (int rc = hc.begin()) return rc;
-    if (int rc = flm_decode_sum_dev(ctx, hs->as<const uint32_t>(), L, frac_bits, count, ho->as<float>(), ctx->stream))
-        return rc;
+    if (int rc = flm_decode_sum_dev(ctx, hc.dev<uint32_t>(0), L, frac_bits, count, hc.dev<float>(1), ctx->stream)) return rc;
     return hc.finish();
 }
 
 int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, int64_t count, float *d_out,
                        void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (frac_bits < 0 || frac_bits > 30) return fail(ctx, FLM_EINVAL, "frac_bits %d outside 0..30", frac_bits);
-    if (count < 1) return fail(ctx, FLM_EINVAL, "count must be at least 1");
+    if (int rc = refuse(ctx, flm::rt::decode_error(frac_bits, count))) return rc;
     if (L == 0) return 0;
     if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (((uintptr_t)d_sum & 15) || ((uintptr_t)d_out & 15)) return fail(ctx, FLM_EINVAL, "sum/out must be 16-byte aligned");
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
     FLM_ON_DEVICE(ctx);
     FLM_HIP(ctx, flm::launch_decode_sum(d_sum, L, (double)count * std::ldexp(1.0, frac_bits), d_out,
                                         static_cast<hipStream_t>(stream)));
@@ -1397,16 +1320,13 @@ int flm_prg_expand(flm_ctx *ctx, const uint8_t *seeds, int K, size_t L, uint64_t
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (K < 0) return fail(ctx, FLM_EINVAL, "negative K");
     if (K == 0 || L == 0) return 0;
-    if (!seeds || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (slot0 % 16) return fail(ctx, FLM_EINVAL, "slot0 must be a multiple of 16");
+    if (int rc = refuse(ctx, flm::rt::prg_expand_error(seeds, out, slot0))) return rc;
     if (int rc = check_range(ctx, slot0, L)) return rc;
     FLM_ON_DEVICE(ctx);
-    const uint64_t pitch = round_up(L, 64);
     HostCopies hc(ctx, ctx->stream);
-    hc.in(seeds, (size_t)K * 32, ctx->seeds);
-    const HostCopies::Span *y = hc.out(out, L * 4, L * 4, (size_t)K, ctx->out, pitch * 4, HostCopies::kMayRunInPlace);
+    hc.declare(flm::rt::prg_expand_args(K, L), {seeds, out});
     if (int rc = hc.begin()) return rc;
-    if (int rc = flm_prg_expand_dev(ctx, ctx->seeds.as<uint8_t>(), K, L, slot0, y->as<uint32_t>(), y->pitch / 4, ctx->stream))
+    if (int rc = flm_prg_expand_dev(ctx, hc.dev<uint8_t>(0), K, L, slot0, hc.dev<uint32_t>(1), hc.pitch(1) / 4, ctx->stream))
         return rc;
     return hc.finish();
 }
@@ -1415,23 +1335,19 @@ int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, ui
                        size_t pitch, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (K <= 0 || L == 0) return 0;
-    if (slot0 % 16) return fail(ctx, FLM_EINVAL, "slot0 must be a multiple of 16");
-    if (pitch % 4 || pitch < round_up(L, 4)) return fail(ctx, FLM_EINVAL, "pitch must be a multiple of 4 and >= L");
-    if ((uintptr_t)d_out & 15) return fail(ctx, FLM_EINVAL, "out must be 16-byte aligned");
+    if (int rc = refuse(ctx, flm::rt::prg_expand_error(d_seeds, d_out, slot0))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_out}))) return rc;
     if (int rc = check_range(ctx, slot0, L)) return rc;
-    if ((uint64_t)K * ((L + 1023) / 1024) > 0xFFFFFFFFull)
-        return fail(ctx, FLM_EINVAL, "K=%d x %zu slots: more than 2^32 1024-slot units", K, L);
+    if (int rc = refuse(ctx, flm::rt::prg_expand_launch_error(K, L))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
-    // +1 signs through a staging slot (no host wait), the seed schedule, then prg_expand_kernel
-    int rc = 0;
-    StageSlot *slot = stage_acquire(ctx, (size_t)K, &rc);
-    if (!slot) return rc;
-    std::memset(slot->host, 1, (size_t)K);
-    FLM_HIP(ctx, stage_upload(slot, (size_t)K, s));
+    // +1 signs through a staging slot, the seed schedule, then prg_expand_kernel
+    Staged up;
+    if (int rc = stage_put(ctx, {{nullptr, (size_t)K, 1}}, s, &up)) return rc;
     SeedTable *table = nullptr;
     const int groups = std::max(1, ctx->n_cus * ctx->tune_expand_waves);
-    rc = run_seed_schedule(ctx, d_seeds, slot->dev.as<int8_t>(), K, s, &table);
+    int rc = run_seed_schedule(ctx, d_seeds, reinterpret_cast<const int8_t *>(up.dev[0]), K, s, &table);
     if (!rc) {
         hipError_t e = flm::launch_prg_expand(table->recs.as<SeedRec>(), K, L, pitch, (uint32_t)(slot0 / 16), d_out,
                                               groups, s);
@@ -1439,11 +1355,9 @@ int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, ui
         if (e != hipSuccess) rc = fail(ctx, FLM_EHIP, "prg_expand launch: %s", hipGetErrorString(e));
         if (rc) table_cover(table, s);
     }
-    // the slot is busy until the work enqueued so far has run, whether or not it all got enqueued
-    FLM_HIP(ctx, stage_commit(slot, s));
-    if (rc) return rc;
-    const uint64_t units = (uint64_t)K * ((L + 1023) / 1024);
-    set_last_plan(ctx, (int)std::min<uint64_t>(units, (uint64_t)groups), flm::kWaveSlots, 0, kExpandVariant);
+    if ((rc = stage_done(ctx, up, s, rc))) return rc;
+    set_last_plan(ctx, (int)std::min<uint64_t>(flm::rt::prg_expand_units(K, L), (uint64_t)groups), flm::kWaveSlots, 0,
+                  kExpandVariant);
     return 0;
 }
 
@@ -1452,21 +1366,17 @@ int flm_mask_accumulate(flm_ctx *ctx, const uint8_t *seeds, const int8_t *signs,
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
     if (K < 0) return fail(ctx, FLM_EINVAL, "negative K");
     if (L == 0) return 0;
-    if (!acc || (K > 0 && (!seeds || !signs))) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (slot0 % 16) return fail(ctx, FLM_EINVAL, "slot0 must be a multiple of 16");
-    if (!signs_ok(signs, K, nullptr)) return fail(ctx, FLM_EINVAL, "signs must be +1 or -1");
+    if (!acc) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (K > 0 && (!seeds || !signs)) return fail(ctx, FLM_EINVAL, "NULL seeds/signs");
+    if (int rc = refuse(ctx, flm::rt::slot0_error(slot0))) return rc;
+    if (int rc = refuse(ctx, flm::rt::signs_error(signs, K))) return rc;
     if (int rc = check_range(ctx, slot0, L)) return rc;
     FLM_ON_DEVICE(ctx);
-    const uint64_t pitch = round_up(L, 64);
     HostCopies hc(ctx, ctx->stream);
-    // acc is read and written in place in the bounce buffer when it fits (flm_client_mask); x and y first, seeds after:
-    // with the seeds between them, y off a 4 KiB boundary, the call measured 0.41 ms against 0.34-0.37
-    const auto *hx = hc.in(acc, L * 4, L * 4, 1, ctx->rows, pitch * 4, HostCopies::kMayRunInPlace);
-    const auto *hy = hc.out(acc, L * 4, L * 4, 1, ctx->out, pitch * 4, HostCopies::kMayRunInPlace);
-    declare_seeds(ctx, hc, seeds, signs, K);
+    hc.declare(flm::rt::mask_accumulate_args(K, L), {acc, acc, seeds, signs});
     if (int rc = hc.begin()) return rc;
-    if (int rc = flm_aggregate_unmask_dev(ctx, hx->as<const uint32_t>(), hx->pitch / 4, 1, ctx->seeds.as<uint8_t>(),
-                                          ctx->signs.as<int8_t>(), K, L, 0, L, slot0, hy->as<uint32_t>(), ctx->stream))
+    if (int rc = flm_aggregate_unmask_dev(ctx, hc.dev<uint32_t>(0), hc.pitch(0) / 4, 1, hc.dev<uint8_t>(2), hc.dev<int8_t>(3),
+                                          K, L, 0, L, slot0, hc.dev<uint32_t>(1), ctx->stream))
         return rc;
     return hc.finish();
 }
@@ -1485,11 +1395,9 @@ int flm_chacha20_xor(flm_ctx *ctx, const uint8_t key[32], const uint8_t nonce[8]
         nn[i] = (uint32_t)nonce[4 * i] | ((uint32_t)nonce[4 * i + 1] << 8) | ((uint32_t)nonce[4 * i + 2] << 16) |
                 ((uint32_t)nonce[4 * i + 3] << 24);
     HostCopies hc(ctx, ctx->stream);
-    // read and written in place in the bounce buffer when it fits (flm_client_mask)
-    const HostCopies::Span *hi = hc.in(in, n, ctx->bytes_in, HostCopies::kMayRunInPlace);
-    const HostCopies::Span *ho = hc.out(out, n, ctx->bytes_out, HostCopies::kMayRunInPlace);
+    hc.declare(flm::rt::chacha20_xor_args(n), {in, out});
     if (int rc = hc.begin()) return rc;
-    FLM_HIP(ctx, flm::launch_chacha20_xor(k, nn, counter, hi->as<const uint8_t>(), ho->as<uint8_t>(), n, ctx->stream));
+    FLM_HIP(ctx, flm::launch_chacha20_xor(k, nn, counter, hc.dev<uint8_t>(0), hc.dev<uint8_t>(1), n, ctx->stream));
     return hc.finish();
 }
 

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/flamingo_hip.h"
+#include "flm_call_args.h"
 #include "flm_internal.h"
 
 namespace {
@@ -423,7 +424,7 @@ int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, i
 
 int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, int frac_bits, int64_t count,
                          float *out) {
-    if (frac_bits < 0 || frac_bits > 30 || count < 1) return sfail(st, FLM_EINVAL, "frac_bits outside 0..30 or count < 1");
+    if (const char *why = flm::rt::decode_error(frac_bits, count)) return sfail(st, FLM_EINVAL, why);
     return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), frac_bits, count);
 }
 

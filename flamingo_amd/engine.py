@@ -83,6 +83,24 @@ def _dev_rows(rows, L: int) -> int:
     return pitch
 
 
+def _client_seeds(seg, signs, seeds_dev):
+    """seg and signs of a client_*_dev call as the C side reads them, with N and K = seg[-1].  The C side
+    reads signs[0..K) from the host array and indexes the K device seeds by seg, 32 bytes apart: all
+    three are checked here, where the shapes are known."""
+    seg = np.ascontiguousarray(seg, dtype=np.int64)
+    N = seg.shape[0] - 1
+    signs = np.ascontiguousarray(signs, dtype=np.int8)
+    K = int(seg[-1]) if N >= 0 else 0
+    if N < 0 or seg[0] != 0 or np.any(np.diff(seg) < 0):
+        raise RuntimeError("seg must be non-decreasing from 0")
+    if signs.ndim != 1 or signs.shape[0] != K:
+        raise RuntimeError(f"{signs.shape[0] if signs.ndim else 0} signs for seg[-1] = {K} seeds")
+    if K and (seeds_dev.dim() != 2 or seeds_dev.shape[1] != 32 or seeds_dev.element_size() != 1
+              or seeds_dev.shape[0] < K or not seeds_dev.is_contiguous()):
+        raise RuntimeError(f"seeds_dev must be a contiguous (>= {K}, 32) uint8 tensor, got {tuple(seeds_dev.shape)}")
+    return seg, signs, N, K
+
+
 class MaskEngine:
     """One GPU's mask-and-aggregate engine (a flm_ctx)."""
 
@@ -408,19 +426,7 @@ class MaskEngine:
 
     def client_mask_dev(self, seg, seeds_dev, signs, out, L: int, x=None, stream=None):
         """Device client masking: seg/signs host arrays, seeds_dev/x/out CUDA tensors (rows at out.shape[1])."""
-        seg = np.ascontiguousarray(seg, dtype=np.int64)
-        N = seg.shape[0] - 1
-        signs = np.ascontiguousarray(signs, dtype=np.int8)
-        K = int(seg[-1]) if N >= 0 else 0
-        # the C side reads signs[0..seg[N]) from this host array and indexes the device seed
-        # table by seg: check both here, where the shapes are known
-        if N < 0 or seg[0] != 0 or np.any(np.diff(seg) < 0):
-            raise RuntimeError("seg must be non-decreasing from 0")
-        if signs.ndim != 1 or signs.shape[0] != K:
-            raise RuntimeError(f"{signs.shape[0] if signs.ndim else 0} signs for seg[-1] = {K} seeds")
-        if K and (seeds_dev.dim() != 2 or seeds_dev.shape[1] != 32 or seeds_dev.element_size() != 1
-                  or seeds_dev.shape[0] < K):
-            raise RuntimeError(f"seeds_dev must be a (>= {K}, 32) uint8 tensor, got {tuple(seeds_dev.shape)}")
+        seg, signs, N, K = _client_seeds(seg, signs, seeds_dev)
         if out.dim() != 2 or out.shape[0] < N or out.element_size() != 4 or out.shape[1] < L:
             raise RuntimeError(f"out must be (>= {N}, >= {L}) 32-bit, got {tuple(out.shape)}")
         if x is not None and (tuple(x.shape) != tuple(out.shape) or x.element_size() != 4):
@@ -438,17 +444,7 @@ class MaskEngine:
         out (>= N, >= L) 32-bit, dither_dev (N, 32) uint8 or None, clipped (>= N,) 32-bit or None: CUDA
         tensors, rows at their own strides.  Enqueued on `stream`; nothing is synchronised."""
         import torch
-        seg = np.ascontiguousarray(seg, dtype=np.int64)
-        N = seg.shape[0] - 1
-        signs = np.ascontiguousarray(signs, dtype=np.int8)
-        K = int(seg[-1]) if N >= 0 else 0
-        if N < 0 or seg[0] != 0 or np.any(np.diff(seg) < 0):
-            raise RuntimeError("seg must be non-decreasing from 0")
-        if signs.ndim != 1 or signs.shape[0] != K:
-            raise RuntimeError(f"{signs.shape[0] if signs.ndim else 0} signs for seg[-1] = {K} seeds")
-        if K and (seeds_dev.dim() != 2 or seeds_dev.shape[1] != 32 or seeds_dev.element_size() != 1
-                  or seeds_dev.shape[0] < K or not seeds_dev.is_contiguous()):
-            raise RuntimeError(f"seeds_dev must be a contiguous (>= {K}, 32) uint8 tensor, got {tuple(seeds_dev.shape)}")
+        seg, signs, N, K = _client_seeds(seg, signs, seeds_dev)
         for name, t in (("x", x), ("out", out)):
             if t is None or t.dim() != 2 or t.shape[0] < N or t.shape[1] < L or t.element_size() != 4 or t.stride(1) != 1:
                 raise RuntimeError(f"{name} must be (>= {N}, >= {L}) 32-bit with unit column stride")

@@ -1,6 +1,8 @@
-// args_check.cpp -- the host side of the batch crypto calls (flm_shamir_combine / _deal, flm_aes_gcm_xor /
-// _seal / _open, flm_ecdsa_verify, flm_feldman_verify, flm_ec_combine, flm_ec_mul, hash to curve) without
-// a GPU, for the host sanitizers:
+// args_check.cpp -- the host side of the calls that come in a host-pointer and a *_dev form, without a GPU, for
+// the host sanitizers: the round path (flm_client_mask, flm_client_encode_mask, flm_decode_sum, flm_prg_expand,
+// flm_mask_accumulate, flm_aggregate_unmask, flm_chacha20_xor) and the batch crypto calls (flm_shamir_combine /
+// _deal, flm_aes_gcm_xor / _seal / _open, flm_ecdsa_verify, flm_feldman_verify, flm_ec_combine, flm_ec_mul,
+// hash to curve):
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -I flamingo_amd/csrc tools/args_check.cpp -o build/args_check && build/args_check
 // It runs the argument rules (flm_call_args.h) over accepted and refused calls, and for the accepted
@@ -10,6 +12,7 @@
 // byte and writes every output byte, every output copied out and compared.  A span placed past the
 // buffer or overlapping another is then a sanitizer report or a failed check; so is a list that names
 // one scratch buffer twice, for any combination of its optional arrays.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,43 +35,62 @@ static int failures = 0;
 // n bytes at p all equal v
 static bool all_bytes(const uint8_t *p, size_t n, uint8_t v) { return !n || (p[0] == v && !std::memcmp(p, p + 1, n - 1)); }
 
-// One call's list through a heap "bounce buffer", as HostCopies::declare, begin() and finish() move it.
-// Array i holds the byte i + 1 on the way in and 0x80 + i on the way out, so a span that overlaps
-// another loses bytes that the stand-in or the caller then misses.
+// One call's list through a heap "bounce buffer", as HostCopies::declare, begin() and finish() move it:
+// rows x width bytes per array, row by row between the host rows at h_pitch and the bounce rows at the
+// layout's pitch (the padded round_up(width, 16) in place, else packed).  Array i holds the byte i + 1
+// on the way in and 0x80 + i on the way out, and the bounce buffer 0xEE wherever no array's bytes
+// lie, so a span that overlaps another, or a row that runs into the next one's, loses bytes that the
+// stand-in or the caller then misses.
 static void through_bounce(const ArgList &l) {
     CHECK(l.n <= kMaxArgs && !names_slot_twice(l));
     std::vector<HostSpan> spans;
     std::vector<Arg> args;
     for (int i = 0; i < l.n; ++i)
-        if (l.a[i].present) spans.push_back({l.a[i].bytes, 1, l.a[i].in_place}), args.push_back(l.a[i]);
+        if (l.a[i].present) spans.push_back({l.a[i].width, l.a[i].rows, l.a[i].in_place}), args.push_back(l.a[i]);
     const size_t total = host_layout(spans.data(), (int)spans.size());
-    std::vector<uint8_t> bounce(total);
+    std::vector<uint8_t> bounce(total, 0xEE);
     std::vector<std::vector<uint8_t>> host(spans.size());
     size_t end = 0;
     for (size_t i = 0; i < spans.size(); ++i) {
         const HostSpan &s = spans[i];
-        CHECK(s.route == (args[i].in_place ? kRouteInPlace : kRouteBounce));  // every shape here is below the staging size
+        const Arg &a = args[i];
+        CHECK(s.route == (a.in_place ? kRouteInPlace : kRouteBounce));  // every shape here is below the staging size
+        CHECK(s.pitch == (a.in_place ? (s.width + 15) / 16 * 16 : s.width));
+        CHECK(a.h_pitch >= a.width && a.d_pitch >= a.width);
         CHECK(s.offset >= end && s.offset % 256 == 0);
         CHECK(s.offset + s.rows * s.pitch <= total);
         end = s.offset + s.rows * s.pitch;
-        host[i].assign(s.width, (uint8_t)(i + 1));
-        if (!args[i].is_out && s.width) std::memcpy(bounce.data() + s.offset, host[i].data(), s.width);  // inputs in
+        host[i].assign(a.rows * a.h_pitch, (uint8_t)(i + 1));
+        if (a.is_out) continue;
+        for (size_t r = 0; r < s.rows && s.width; ++r)  // inputs in
+            std::memcpy(bounce.data() + s.offset + r * s.pitch, host[i].data() + r * a.h_pitch, s.width);
     }
     for (size_t i = 0; i < spans.size(); ++i)  // the kernel's stand-in: every input byte read ...
-        if (!args[i].is_out) CHECK(all_bytes(bounce.data() + spans[i].offset, spans[i].width, (uint8_t)(i + 1)));
+        for (size_t r = 0; r < spans[i].rows && !args[i].is_out; ++r)
+            CHECK(all_bytes(bounce.data() + spans[i].offset + r * spans[i].pitch, spans[i].width, (uint8_t)(i + 1)));
     for (size_t i = 0; i < spans.size(); ++i)  // ... and every output byte written
-        if (args[i].is_out && spans[i].width) std::memset(bounce.data() + spans[i].offset, (int)(0x80 + i), spans[i].width);
-    for (size_t i = 0; i < spans.size(); ++i) {  // outputs out
-        if (!args[i].is_out || !spans[i].width) continue;
-        std::memcpy(host[i].data(), bounce.data() + spans[i].offset, spans[i].width);
-        CHECK(all_bytes(host[i].data(), spans[i].width, (uint8_t)(0x80 + i)));
+        for (size_t r = 0; r < spans[i].rows && args[i].is_out && spans[i].width; ++r)
+            std::memset(bounce.data() + spans[i].offset + r * spans[i].pitch, (int)(0x80 + i), spans[i].width);
+    size_t held = 0;
+    for (size_t i = 0; i < spans.size(); ++i) {  // outputs out; the inputs are still whole
+        const HostSpan &s = spans[i];
+        for (size_t r = 0; r < s.rows && s.width; ++r) {
+            const uint8_t *b = bounce.data() + s.offset + r * s.pitch;
+            if (args[i].is_out) std::memcpy(host[i].data() + r * args[i].h_pitch, b, s.width);
+            CHECK(all_bytes(b, s.width, (uint8_t)(args[i].is_out ? 0x80 + i : i + 1)));
+        }
+        held += s.rows * s.width;
+        if (args[i].is_out) CHECK(all_bytes(host[i].data(), host[i].size(), (uint8_t)(0x80 + i)));  // h_pitch == width here
     }
+    size_t padding = 0;
+    for (uint8_t b : bounce) padding += b == 0xEE;
+    CHECK(padding == total - held);  // nothing written between the rows or the spans
 }
 
 static bool bytes_are(const ArgList &l, std::initializer_list<size_t> want) {
     if ((size_t)l.n != want.size()) return false;
     for (int i = 0; i < l.n; ++i)
-        if (l.a[i].bytes != want.begin()[i]) return false;
+        if (l.a[i].width != want.begin()[i]) return false;
     return true;
 }
 
@@ -94,6 +116,102 @@ static void check_lists() {
     const ArgList seal = aes_gcm_auth_args(12, 0, 0, 4, false), open = aes_gcm_auth_args(12, 1, 1, 4, true);
     CHECK(!seal.a[2].present && !seal.a[3].present && !seal.a[4].present && seal.a[5].is_out && !seal.a[6].present);
     CHECK(open.a[2].present && open.a[3].in_place && open.a[4].in_place && !open.a[5].is_out && open.a[6].is_out);
+}
+
+// The round path's lists: every combination of the optional arrays, at the GPU test's shapes (L = 1: a row
+// below one 16-byte quad, 5: a quad and a tail, 1025) and one that fills whole 64-word pitches.
+static void check_round_lists() {
+    // a two-row, 20-byte span in place: rows at 32, the 12 bytes after each untouched
+    const ArgList padded = {{in_place(pitched(arg_in(20, rows), 2, 256)), in_place(pitched(arg_out(20, out), 2, 256))}, 2};
+    HostSpan sp[2] = {{20, 2, true}, {20, 2, true}};
+    CHECK(host_layout(sp, 2) == 512 && sp[0].pitch == 32 && sp[1].offset == 256 && sp[1].route == kRouteInPlace);
+    through_bounce(padded);
+    for (size_t L : {size_t(1), size_t(5), size_t(64), size_t(1025)})
+        for (size_t N : {size_t(1), size_t(3)})
+            for (size_t K : {size_t(0), size_t(3)})
+                for (int opt = 0; opt < 4; ++opt) {
+                    through_bounce(client_encode_mask_args(N, K, L, opt & 1, opt & 2));
+                    if (opt < 2) through_bounce(client_mask_args(N, K, L, opt & 1));
+                    if (opt < 2) through_bounce(aggregate_unmask_args(K, L, opt & 1));
+                    if (opt) continue;
+                    through_bounce(prg_expand_args(K, L));
+                    through_bounce(mask_accumulate_args(K, L));
+                    through_bounce(decode_sum_args(L));
+                    through_bounce(chacha20_xor_args(L));
+                }
+    // rows travel at the host forms' pitch; what is optional is exactly what the flags name
+    const ArgList m = client_mask_args(3, 7, 5, false), e = client_encode_mask_args(3, 7, 5, false, true);
+    CHECK(host_row_pitch(1) == 256 && host_row_pitch(64) == 256 && host_row_pitch(65) == 512);
+    CHECK(m.n == 4 && !m.a[0].present && m.a[3].is_out && m.a[3].in_place && m.a[3].rows == 3 && m.a[3].width == 20 &&
+          m.a[3].h_pitch == 20 && m.a[3].d_pitch == 256 && m.a[1].width == 7 * 32 && m.a[2].width == 7);
+    CHECK(e.n == 5 && e.a[0].present && !e.a[2].present && e.a[4].present && e.a[4].is_out && e.a[4].width == 12);
+    const ArgList z = client_mask_args(3, 0, 5, true);  // K = 0: seeds and signs declared, no bytes
+    CHECK(z.a[1].present && z.a[2].present && !z.a[1].width && !z.a[2].width);
+    CHECK(!aggregate_unmask_args(3, 5, false).a[2].present && aggregate_unmask_args(3, 5, true).a[2].width == 20);
+    const ArgList acc = mask_accumulate_args(3, 1025);  // the rows first, the seeds after
+    CHECK(acc.a[0].slot == rows && acc.a[1].slot == out && acc.a[1].is_out && acc.a[2].slot == seeds && acc.a[3].slot == signs);
+}
+
+// The round path's rules at their edges.
+static void check_round_rules() {
+    int64_t K = -1;
+    const int64_t seg_ok[4] = {0, 0, 2, 3}, seg_from1[2] = {1, 1}, seg_down[4] = {0, 2, 1, 3};
+    const int64_t seg_max[2] = {0, 0x7fffffff}, seg_over[2] = {0, 0x80000000ll};
+    const int8_t sg[3] = {1, -1, 1}, sg0[3] = {1, 0, 1}, sg2[3] = {1, 1, 2};
+    CHECK(!seg_signs_error(3, seg_ok, sg, &K) && K == 3);
+    CHECK(seg_signs_error(3, nullptr, sg, &K) && seg_signs_error(1, seg_from1, sg, &K) && seg_signs_error(3, seg_down, sg, &K));
+    CHECK(seg_signs_error(3, seg_ok, nullptr, &K) && seg_signs_error(3, seg_ok, sg0, &K) && seg_signs_error(3, seg_ok, sg2, &K));
+    CHECK(!seg_signs_error(2, seg_ok, sg2, &K) && K == 2);      // the first two clients: two seeds, signs[2] not read
+    CHECK(!seg_signs_error(1, seg_ok, nullptr, &K) && K == 0);  // the first alone: none, and no signs needed
+    // K = 2^31 - 1 passes the count (its signs are then read: none given here), 2^31 does not
+    CHECK(std::strcmp(seg_signs_error(1, seg_max, nullptr, &K), "NULL seeds/signs") == 0);
+    CHECK(std::strcmp(seg_signs_error(1, seg_over, nullptr, &K), "too many seeds") == 0);
+    CHECK(!client_args_error(true, 3, seg_ok, sg, sg, &K) && client_args_error(false, 3, seg_ok, sg, sg, &K) &&
+          client_args_error(true, 3, seg_ok, nullptr, sg, &K) && !client_args_error(true, 1, seg_ok, nullptr, nullptr, &K));
+    // pitch = round_up(L, 4) and one less
+    for (size_t L : {size_t(1), size_t(4), size_t(5), size_t(1025)}) {
+        const size_t p = round_up(L, 4);
+        CHECK(!row_pitch_error(p, L) && !row_pitch_error(p + 4, L) && row_pitch_error(p - 1, L) && row_pitch_error(p + 1, L));
+        CHECK(p < 4 || row_pitch_error(p - 4, L));
+    }
+    CHECK(row_pitch_error(5, 5) && row_pitch_error(0, 1));
+    alignas(16) static uint8_t buf[32];
+    CHECK(!align16_error({buf, buf + 16, nullptr}) && align16_error({buf + 8}) && align16_error({buf, buf + 1}) &&
+          align16_error({nullptr, buf + 24}) && !align16_error({}));
+    CHECK(std::strstr(align16_error({buf + 8}), "16-byte aligned"));
+    // frac_bits 0, 30, 31; the clip; n ceil(clip 2^f) exactly 2^31 - 1 and one more
+    bool range = true;
+    CHECK(!codec_error(0, 1.0f, 1, &range) && !range && !codec_error(30, 1.0f, 1, &range) && !range);
+    CHECK(codec_error(31, 1.0f, 1, &range) && !range && codec_error(-1, 1.0f, 1, &range) && !range);
+    CHECK(codec_error(16, 0.0f, 1, &range) && !range && codec_error(16, -1.0f, 1, &range) && !range);
+    CHECK(codec_error(16, INFINITY, 1, &range) && !range && codec_error(16, NAN, 1, &range) && !range);
+    CHECK(codec_error(16, 1.0f, 0, &range) && !range);
+    CHECK(!codec_error(0, 1.0f, 2147483647, &range) && !range);                       // n x 1 = 2^31 - 1
+    CHECK(codec_error(0, 1.0f, 2147483648ll, &range) && range);                       // ... and one more
+    CHECK(!codec_error(16, 0.5f, 65535, &range) && !range);                           // 65535 x 2^15 < 2^31 - 1
+    CHECK(codec_error(16, 0.5f, 65536, &range) && range);                             // 2^31
+    CHECK(!codec_error(4, 1.01f, 126322567, &range) && codec_error(4, 1.01f, 126322568, &range) && range);  // m = 17
+    CHECK(!codec_error(30, 1.9999999f, 1, &range) && codec_error(30, 2.0f, 1, &range) && range);  // m alone past 2^31 - 1
+    CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
+    CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));
+    CHECK(!slot_range_error(0, 1ull << 36) && slot_range_error(16, 1ull << 36) && slot_range_error(1ull << 36, 1) &&
+          !slot_range_error(1ull << 36, 0) && slot_range_error(~0ull, 2));
+    CHECK(!prg_expand_error(buf, buf, 16) && prg_expand_error(nullptr, buf, 16) && prg_expand_error(buf, nullptr, 16) &&
+          prg_expand_error(buf, buf, 8));
+    CHECK(!encode_mask_launch_error(0x7fffffffull) && encode_mask_launch_error(0x80000000ull));
+    CHECK(prg_expand_units(3, 1025) == 6 && !prg_expand_launch_error(0x7fffffff, 2048) &&
+          prg_expand_launch_error(0x7fffffff, 2049) && !prg_expand_launch_error(1, 0xFFFFFFFFull * 1024));
+    // the round's own: codes as the order of the checks gives them
+    CHECK(!aggregate_error(buf, 8, 1, 0, 5, 0, 5, 0, buf + 16, &range) && !range);
+    CHECK(aggregate_error(buf, 4, 1, 0, 5, 0, 5, 0, buf + 16, &range) && !range);       // pitch below round_up(L, 4)
+    CHECK(!aggregate_error(nullptr, 0, 0, 0, 5, 0, 5, 0, buf, &range));                 // no rows: no pitch, no pointer
+    CHECK(std::strstr(aggregate_error(buf + 8, 8, 1, 0, 5, 0, 5, 0, buf, &range), "16-byte aligned"));
+    CHECK(aggregate_error(buf, 8, 1, 0, 5, 0, 6, 0, buf, &range) && aggregate_error(buf, 8, 1, 0, 5, 3, 2, 0, buf, &range));
+    CHECK(aggregate_error(buf, 8, 1, 0, 5, 0, 5, 8, buf, &range) && !range);
+    CHECK(aggregate_error(buf, 8, 1, 0, 5, 0, 5, 1ull << 36, buf, &range) && range);
+    CHECK(aggregate_error(buf, 8, 1, 0, 5, 0, 5, 1ull << 36, nullptr, &range) && range);  // the range before the NULL
+    CHECK(aggregate_error(buf, 8, 1, 0, 5, 0, 5, 0, nullptr, &range) && !range && aggregate_error(nullptr, 8, 1, 0, 5, 0, 5, 0, buf, &range));
+    CHECK(aggregate_error(buf, 8, -1, 0, 5, 0, 5, 0, buf, &range) && aggregate_error(buf, 8, 1, -1, 5, 0, 5, 0, buf, &range));
 }
 
 static void check_deal() {
@@ -228,7 +346,7 @@ static void check_feldman() {
         std::vector<uint32_t> dealer(n);
         for (int i = 0; i < n; ++i) dealer[i] = (uint32_t)((i * 5 + 2) % M);
         CHECK(feldman_bad_dealer(dealer.data(), n, M) == -1);
-        const std::vector<uint8_t> com(feldman_verify_args(T, M, n, true, true, true).a[0].bytes, 1);
+        const std::vector<uint8_t> com(feldman_verify_args(T, M, n, true, true, true).a[0].width, 1);
         uint32_t sum = 0;
         for (int i = 0; i < n; ++i)
             for (int k = 0; k < T; ++k) sum += com[((size_t)k * M + dealer[i]) * 64 + 63];
@@ -238,6 +356,8 @@ static void check_feldman() {
 
 int main() {
     check_lists();
+    check_round_lists();
+    check_round_rules();
     check_deal();
     check_gcm();
     check_ecdsa();
