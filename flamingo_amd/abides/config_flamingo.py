@@ -75,20 +75,26 @@ def parse(argv):
     ap.add_argument("--host_dkg", action="store_true")
     # the clients' inputs are float32 updates, encoded in fixed point inside the masking kernel, and the server
     # also decodes the sum to final_mean (protocol.configure(codec=...)): F fractional bits, clip CLIP, nearest-even
-    # rounding or, with ",sr", stochastic rounding; off by default
-    ap.add_argument("--float_inputs", default=None, metavar="F,CLIP[,sr]")
+    # rounding or, with ",sr", stochastic rounding; ",pack2" or ",pack4": that many parameters per ring word (the
+    # packed codec: n 2 ceil(CLIP 2^F) must fit 16 or 8 bits, so pack4 serves small cohorts only); off by default
+    ap.add_argument("--float_inputs", default=None, metavar="F,CLIP[,sr][,pack2|pack4]")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
 
 def parse_float_inputs(spec):
-    """"F,CLIP" or "F,CLIP,sr" -> (frac_bits, clip, "nearest" | "stochastic"); None or "" -> False (off)."""
+    """"F,CLIP" or "F,CLIP,sr" -> (frac_bits, clip, "nearest" | "stochastic"); with a last ",pack2" or ",pack4"
+    -> (frac_bits, clip, rounding, 2 | 4); None or "" -> False (off)."""
     if not spec:
         return False
     parts = [s.strip() for s in spec.split(",")]
+    pack = None
+    if len(parts) > 2 and parts[-1] in ("pack2", "pack4"):
+        pack = int(parts.pop()[4:])
     if len(parts) not in (2, 3) or (len(parts) == 3 and parts[2] != "sr"):
-        raise ValueError("--float_inputs takes F,CLIP or F,CLIP,sr")
-    return int(parts[0]), float(parts[1]), "stochastic" if len(parts) == 3 else "nearest"
+        raise ValueError("--float_inputs takes F,CLIP[,sr][,pack2|pack4]")
+    codec = (int(parts[0]), float(parts[1]), "stochastic" if len(parts) == 3 else "nearest")
+    return codec if pack is None else codec + (pack,)
 
 
 def offline_schedule(n: int, iterations: int, always=(), dropout: float = 0.0) -> dict:
@@ -219,7 +225,8 @@ def _run(args):
               f"({gpu.get('reconstruction_unmask_wall', 0):.3f} ms wall)")
         if it in server.means:      # float inputs: the decoded mean against the mean of the clients' own floats
             exact = np.mean([np.asarray(agents[i].input_vector, np.float64) for i in server.online_ids[it]], axis=0)
-            print(f"    iteration {it}: float inputs {param.codec()}: largest |final_mean - mean of the clients' floats| = "
+            packed = f", {param.codec_pack()} per word" if param.codec_pack() > 1 else ""
+            print(f"    iteration {it}: float inputs {param.codec()}{packed}: largest |final_mean - mean of the clients' floats| = "
                   f"{float(np.max(np.abs(server.means[it].astype(np.float64) - exact))):.3e}, "
                   f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped")
     print()

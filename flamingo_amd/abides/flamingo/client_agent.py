@@ -238,9 +238,14 @@ class SA_ClientAgent(Agent):
             x = np.asarray(self.input_vector, np.float32)[None, :]
             dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
                 if rounding == "stochastic" else None
-            vec, clipped = param.engine().client_encode_mask(np.array([0, len(seeds)], np.int64), seeds, signs,
-                                                             self.vector_len, x, frac_bits, clip, dither=dither,
-                                                             return_clipped=True)
+            seg = np.array([0, len(seeds)], np.int64)
+            if param.codec_pack() == 1:
+                vec, clipped = param.engine().client_encode_mask(seg, seeds, signs, self.vector_len, x, frac_bits, clip,
+                                                                 dither=dither, return_clipped=True)
+            else:   # packed: the body is param.ring_len() words, the masks with it
+                vec, clipped = param.engine().client_encode_pack_mask(seg, seeds, signs, self.vector_len, x, frac_bits,
+                                                                      clip, param.codec_pack(), dither=dither,
+                                                                      return_clipped=True)
             vec, self.clipped = vec[0], int(clipped[0])
             self.dither_seed = dither[0] if dither else None
         self.sendMessage(self.serviceAgentID, Message({

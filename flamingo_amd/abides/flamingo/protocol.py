@@ -66,6 +66,10 @@ _dkg_result = None                      # (group key, {committee member id: (mem
 # the fixed-point codec fused into its masking (MaskEngine.client_encode_mask); the server keeps final_sum and
 # adds final_mean.  Off by default, so a run sends what it always sent and draws what it always drew.
 _codec = None                           # configure(codec=(frac_bits, clip, "nearest" | "stochastic"))
+# ... and, with a fourth element 2 or 4, that many parameters per ring word (the packed codec): a VECTOR body,
+# the store, the masks and the sums are ring_len() = ceil(vector_len / pack) words; vector_len stays the
+# parameter count and final_mean's length
+_codec_pack: int = 1
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
@@ -73,17 +77,23 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
               authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
-    "stochastic") turns the float inputs on, False turns them off, None leaves them as they are."""
+    "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
+    many parameters into a ring word, False turns them off, None leaves them as they are."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares, _dkg, _dkg_result, _codec
+    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack
     if codec is not None:
         if codec is False:
-            _codec = None
+            _codec, _codec_pack = None, 1
         else:
-            f, c, mode = codec
+            f, c, mode = codec[:3]
+            pack = int(codec[3]) if len(codec) == 4 else 1
+            if len(codec) not in (3, 4):
+                raise ValueError("codec is (frac_bits, clip, rounding) or (frac_bits, clip, rounding, pack)")
             if mode not in ("nearest", "stochastic"):
                 raise ValueError("codec rounding must be 'nearest' or 'stochastic'")
-            _codec = (int(f), float(c), mode)
+            if pack not in (1, 2, 4):
+                raise ValueError("codec pack must be 1, 2 or 4")
+            _codec, _codec_pack = (int(f), float(c), mode), pack
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -252,6 +262,16 @@ def pki(num_clients: int):
 def codec():
     """(frac_bits, clip, rounding) of the float inputs, or None when they are off (configure(codec=...))."""
     return _codec
+
+
+def codec_pack() -> int:
+    """Parameters per ring word of the float inputs: 1 (also when they are off), 2 or 4."""
+    return _codec_pack if _codec is not None else 1
+
+
+def ring_len() -> int:
+    """Words of a ring row (a VECTOR body, a mask, the sums): ceil(vector_len / codec_pack())."""
+    return -(-vector_len // codec_pack())
 
 
 def dkg_on() -> bool:

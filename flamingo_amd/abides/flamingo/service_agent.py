@@ -54,12 +54,14 @@ class SA_ServiceAgent(Agent):
         self.num_clients = num_clients
         self.users = users
         self.vector_len = param.vector_len
+        # words of a ring row (VECTOR bodies, the store, the sums): fewer than vector_len with packed float inputs
+        self.ring_len = param.ring_len()
         self.vector_dtype = param.vector_type
         self._store = None           # VectorStore: the VECTOR bodies on the GPU(s), from arrival on
         self._accepting = True       # False between report and the end of reconstruction (:488-497)
-        self._host_partial = np.zeros(self.vector_len, dtype=self.vector_dtype)
+        self._host_partial = np.zeros(self.ring_len, dtype=self.vector_dtype)
         self.gpu_ms = {}             # iteration -> {"report": ms, "reconstruction": ms} (device time)
-        self.final_sum = np.zeros(self.vector_len, dtype=self.vector_dtype)
+        self.final_sum = np.zeros(self.ring_len, dtype=self.vector_dtype)
         self.prime = P256_N
         self.key_length = key_length
         self.neighborhood_size = neighborhood_size
@@ -80,7 +82,12 @@ class SA_ServiceAgent(Agent):
         self.online_ids = {}         # float inputs: iteration -> the clients whose vectors were summed
         if param.codec() is not None:
             # n updates of magnitude up to clip must fit the 32-bit ring: refuse the run, never wrap (FLM_ERANGE)
-            param.engine().codec_check(param.codec()[0], param.codec()[1], max(1, len(users) or num_clients))
+            # (packed: no field of the sum may carry into its neighbour, n 2 ceil(clip 2^f) <= 2^(32/pack) - 1)
+            n = max(1, len(users) or num_clients)
+            if param.codec_pack() == 1:
+                param.engine().codec_check(param.codec()[0], param.codec()[1], n)
+            else:
+                param.engine().codec_check(param.codec()[0], param.codec()[1], n, pack=param.codec_pack())
         self.online_counts = {}      # iteration -> |U|
         self.pairs_per_iteration = {}  # iteration -> D dropout pairs recovered
         self.aggProcessingMap = {0: self.initialize, 1: self.report, 2: self.forward_signatures,
@@ -135,7 +142,7 @@ class SA_ServiceAgent(Agent):
     # ------------------------------------------------------- device state
     def store(self):
         if self._store is None:
-            self._store = param.vector_store(self.vector_len, max(1, len(self.users) or self.num_clients))
+            self._store = param.vector_store(self.ring_len, max(1, len(self.users) or self.num_clients))
         return self._store
 
     @property
@@ -156,7 +163,7 @@ class SA_ServiceAgent(Agent):
             raise RuntimeError("vec_sum_partial is device-resident after report; assign it before report "
                                "or after the iteration's reset")
         v = np.asarray(value)
-        if v.shape != (self.vector_len,):
+        if v.shape != (self.ring_len,):
             raise RuntimeError("Client sends vector of incorrect length.")   # the guard of :348-349
         self._host_partial = np.ascontiguousarray(v, dtype=self.vector_dtype)
 
@@ -292,7 +299,7 @@ class SA_ServiceAgent(Agent):
             if getattr(self._store, "_owner", None) is not None and self._store._owner is not param.server_engine():
                 self._store.close()
                 self._store = None
-        self._host_partial = np.zeros(self.vector_len, dtype=self.vector_dtype)
+        self._host_partial = np.zeros(self.ring_len, dtype=self.vector_dtype)
         self._accepting = True
 
     def reconstruction_process(self):
@@ -326,12 +333,15 @@ class SA_ServiceAgent(Agent):
         # K masks over its own slot shard of the device-resident S, then the one copy to the host
         t0 = pd.Timestamp("now")
         st = self.store()
-        codec = param.codec()
+        codec, pack = param.codec(), param.codec_pack()
+        count = max(1, len(self.user_vectors))
         self.final_mean = None
         if getattr(st, "has_partial", True):
             self.final_sum = st.unmask(seeds, signs)
-            if codec is not None:      # float inputs: the same sum, decoded on the GPU(s) as the mean over U
-                self.final_mean = st.unmask_f32(seeds, signs, codec[0], max(1, len(self.user_vectors)))
+            if codec is not None and pack == 1:   # float inputs: the same sum, decoded on the GPU(s) as the mean over U
+                self.final_mean = st.unmask_f32(seeds, signs, codec[0], count)
+            elif codec is not None:               # packed: every device unpacks its word shard into its floats
+                self.final_mean = st.unmask_unpack_f32(seeds, signs, self.vector_len, codec[0], codec[1], pack, count)
         else:
             # no report this iteration: the reference-style assigned partial sum (vec_sum_partial
             # setter, :540/:605) is the S the masks are added to, on the GPU
@@ -344,8 +354,10 @@ class SA_ServiceAgent(Agent):
             rec["reconstruction_unmask_gpu"] = gpu
         self.agent_print(f"reconstruction unmask: {len(seeds)} masks over S on the GPU(s) + D2H, {ms:.3f} ms wall"
                          + (f", {gpu:.3f} ms GPU" if gpu is not None else ""))
-        if codec is not None and self.final_mean is None:
-            self.final_mean = param.engine().decode_sum(self.final_sum, codec[0], max(1, len(self.user_vectors)))
+        if codec is not None and self.final_mean is None and pack == 1:
+            self.final_mean = param.engine().decode_sum(self.final_sum, codec[0], count)
+        elif codec is not None and self.final_mean is None:
+            self.final_mean = param.engine().decode_unpack(self.final_sum, self.vector_len, codec[0], codec[1], pack, count)
         if codec is not None:
             self.means[self.current_iteration] = self.final_mean
             self.online_ids[self.current_iteration] = sorted(self.user_vectors)

@@ -86,6 +86,25 @@ inline const char *codec_error(int frac_bits, float clip, int64_t n, bool *headr
     return *headroom ? "that many contributors of magnitude up to ceil(clip 2^frac_bits) can wrap the 32-bit sum" : nullptr;
 }
 
+// The packed codec's rule: pack = 2 or 4 fields of W = 32 / pack bits per ring word (pack = 1 is the unpacked
+// calls' job), each holding q + B in [0, 2B], B = ceil(clip 2^f) as above.  Headroom for n contributors:
+// n 2B <= 2^W - 1, in integers, so that no field of the sum carries into its neighbour (FLM_ERANGE).
+// *bias: B, when the rule passes.
+inline const char *packed_codec_error(int frac_bits, float clip, int pack, int64_t n, bool *headroom, uint32_t *bias) {
+    *headroom = false;
+    if (pack != 2 && pack != 4) return "pack must be 2 or 4";
+    if (const char *why = codec_error(frac_bits, clip, n, headroom)) return why;
+    const uint64_t B = (uint64_t)std::ceil((double)clip * std::ldexp(1.0, frac_bits));  // >= 1: clip > 0
+    const uint64_t field_max = (uint64_t(1) << (32 / pack)) - 1;
+    *headroom = 2 * B > field_max || (uint64_t)n > field_max / (2 * B);
+    if (bias) *bias = (uint32_t)B;
+    return *headroom ? "that many contributors of fields up to 2 ceil(clip 2^frac_bits) can carry out of a packed field"
+                     : nullptr;
+}
+
+// words of a row of L parameters
+constexpr size_t packed_words(size_t L, int pack) { return (L + (size_t)pack - 1) / (size_t)pack; }
+
 // flm_decode_sum[_dev], flm_store_unmask_f32: the mean over `count` contributors at frac_bits
 inline const char *decode_error(int frac_bits, int64_t count) {
     if (const char *why = frac_bits_error(frac_bits)) return why;
@@ -314,6 +333,17 @@ inline ArgList client_encode_mask_args(size_t N, size_t K, size_t L, bool dither
 }
 // sum, out
 inline ArgList decode_sum_args(size_t L) { return {{in_place(arg_in(L * 4, rows)), in_place(arg_out(L * 4, out))}, 2}; }
+// x (L floats a row), seeds, dither, out (Lw = packed_words(L, pack) words a row), clipped; x and out in place as
+// above, each at a pitch of its own
+inline ArgList client_encode_pack_mask_args(size_t N, size_t K, size_t L, size_t Lw, bool dither, bool clipped) {
+    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
+             arg_in(N * 32, bytes_in, dither), in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))),
+             arg_out(N * 4, bytes_out, clipped)}, 5};
+}
+// sum (Lw words), out (L floats)
+inline ArgList decode_unpack_args(size_t L, size_t Lw) {
+    return {{in_place(arg_in(Lw * 4, rows)), in_place(arg_out(L * 4, out))}, 2};
+}
 // seeds, out (K rows)
 inline ArgList prg_expand_args(size_t K, size_t L) {
     return {{arg_in(K * 32, seeds), in_place(pitched(arg_out(L * 4, out), K, host_row_pitch(L)))}, 2};

@@ -50,6 +50,17 @@ hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const i
                               uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream);
 // d_out[l] = float32(float64(int32(d_sum[l])) / denom), l < n; d_out may be d_sum; both 16-byte aligned
 hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, float *d_out, hipStream_t stream);
+// Packed codec (encode_pack_mask_kernel, decode_unpack_kernel): pack = 2 or 4 parameters per ring word, biased by
+// bias = ceil(clip 2^frac_bits).  L counts parameters; d_out rows hold ceil(L / pack) words; the grid is
+// encode_mask_groups(N, ceil(L / pack)).  d_x rows are read 16 bytes at a time up to round_up(L, 4) floats.
+hipError_t launch_encode_pack_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                                   const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
+                                   int pack, uint32_t bias, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
+                                   hipStream_t stream);
+// d_out[pack l' + j] = float32(float64(field j of d_sum[l'] - count_bias) / denom) for the L parameters; d_out is
+// not d_sum; both 16-byte aligned
+hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int64_t count_bias, double denom, float *d_out,
+                                hipStream_t stream);
 uint32_t pair_units_count(int K, uint64_t L, uint32_t *n_tiles);
 hipError_t launch_pair_units(bool side, const SeedRec *d_recs, int K, uint32_t *d_dst, uint64_t L, uint32_t *d_ws,
                              int groups, hipStream_t stream);

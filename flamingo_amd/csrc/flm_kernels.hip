@@ -1036,6 +1036,166 @@ __global__ __launch_bounds__(256) void decode_sum_kernel(const uint32_t *sum, ui
     if (t < n) out[t] = (float)((double)(int32_t)sum[t] / denom);
 }
 
+// ------------------------------------------------------------ packed fixed-point codec
+// P = 2 or 4 parameters per ring word, in fields of W = 32 / P bits (tests/pack_cases.py):
+//   field u = q + B, q the codec's encode, B = ceil(c 2^f); word l' = sum_j u[P l' + j] << (W j); fields of
+//   parameters past L hold 0.  With n 2B <= 2^W - 1 no field of a sum over n clients carries into the next.
+//   decode: s_j = (S >> W j) & (2^W - 1), out[P l' + j] = float32(float64(s_j - count B) / (count 2^f)).
+
+// One field: the codec's q of a parameter the row has, biased; 0 for a parameter past L (whatever v holds).
+template <bool STOCHASTIC>
+__device__ __forceinline__ uint32_t codec_field(bool have, float v, float clip, float scale, uint32_t r, uint32_t bias,
+                                                uint32_t &nclip) {
+    const uint32_t q = codec_encode<STOCHASTIC>(have ? v : 0.0f, clip, scale, r, nclip);
+    return have ? q + bias : 0u;
+}
+
+// out[i][l'] = pack(encode(x[i][P l' .. P l' + P - 1])) + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l']
+// encode_mask_kernel over Lw = ceil(L / P) ring words: the same grid of (client, 1024-word tile) workgroups, lane t
+// of every wave owns ChaCha block t of the tile, the four accumulators meet in LDS and the tile is stored once.
+// The encoding wave (rank 0) reads the lane's 16 P consecutive floats, one dither block's worth (16 parameters,
+// 16 / P words) at a time: in stochastic mode block P (64 tile + t) + d of the client's dither stream, which is
+// indexed by parameter.  So that wave carries E = P blocks of its own in stochastic mode (about one in nearest
+// mode: the encoding is a fraction of a block), and the seeds are dealt to even that out: the first 3 E go round
+// ranks 1..3, the rest round all four from rank 0.  E = 1 is encode_mask_kernel's order.
+template <int P, bool STOCHASTIC>
+__global__ __launch_bounds__(256) void encode_pack_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
+                                                               const int64_t *__restrict__ seg,
+                                                               const uint8_t *__restrict__ seeds,
+                                                               const int8_t *__restrict__ signs,
+                                                               const uint8_t *__restrict__ dither, uint64_t L,
+                                                               uint64_t Lw, uint32_t tiles, float clip, float scale,
+                                                               uint32_t bias, uint32_t *__restrict__ out,
+                                                               uint64_t out_pitch, uint32_t *__restrict__ clipped) {
+    static_assert(P == 2 || P == 4, "two or four fields per word");
+    constexpr int W = 32 / P;
+    constexpr int E = STOCHASTIC ? P : 1;
+    __shared__ u32x4 lds[5 * 256];  // 20 KiB: one 4 KiB region per wave, and one for the packed words
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
+    const uint32_t ctr = tile * 64u + (uint32_t)lane;
+    const int64_t k_lo = seg[i], n_k = seg[i + 1] - k_lo;
+
+    uint32_t m[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m[j] = 0u;
+    uint32_t nneg = 0;
+    const int rank = 3 - w;
+    for (int64_t u = rank ? rank - 1 : 3 * E; u < n_k; u += (u + 3 < 3 * E ? 3 : 4)) {
+        const int64_t k = k_lo + u;
+        const bool neg = signs[k] < 0;
+        nneg += neg ? 1u : 0u;
+        chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
+    }
+    if (rank == 0) {
+        const float *xr = x + (uint64_t)i * x_pitch;
+        const uint64_t par0 = (uint64_t)P * ((uint64_t)tile * 1024u + 16u * (uint64_t)lane);  // the lane's first parameter
+        uint32_t nclip = 0;
+        // One dither block's parameters per pass, and the passes not unrolled: the block's 16 / P packed words go to
+        // the lane's place in a fifth LDS region (a quad or two), so no pass indexes the accumulator registers and
+        // the footprint stays that of one ChaCha block beside m.
+        u32x4 *E4 = lds + 4 * 256 + 4 * lane;
+#pragma unroll 1
+        for (int d = 0; d < P; ++d) {
+            uint32_t r[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) r[j] = 0u;
+            // parameters below 2^36 (the call's range rule): the dither block counter stays below 2^32
+            if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, (uint32_t)P * ctr + (uint32_t)d, kAbcd, r);
+            uint32_t e[16 / P];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint64_t s = par0 + 16u * (uint32_t)d + 4u * j;
+                // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+                const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const uint32_t u0 = codec_field<STOCHASTIC>(s + 0 < L, v.x, clip, scale, r[4 * j + 0], bias, nclip);
+                const uint32_t u1 = codec_field<STOCHASTIC>(s + 1 < L, v.y, clip, scale, r[4 * j + 1], bias, nclip);
+                const uint32_t u2 = codec_field<STOCHASTIC>(s + 2 < L, v.z, clip, scale, r[4 * j + 2], bias, nclip);
+                const uint32_t u3 = codec_field<STOCHASTIC>(s + 3 < L, v.w, clip, scale, r[4 * j + 3], bias, nclip);
+                if constexpr (P == 4) {
+                    e[j] = u0 | (u1 << W) | (u2 << 2 * W) | (u3 << 3 * W);
+                } else {
+                    e[2 * j + 0] = u0 | (u1 << W);
+                    e[2 * j + 1] = u2 | (u3 << W);
+                }
+            }
+            if constexpr (P == 4) {
+                E4[d] = u32x4{e[0], e[1], e[2], e[3]};
+            } else {
+                E4[2 * d + 0] = u32x4{e[0], e[1], e[2], e[3]};
+                E4[2 * d + 1] = u32x4{e[4], e[5], e[6], e[7]};
+            }
+        }
+        if (clipped) {  // only this wave counts: its total is the workgroup's
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
+            if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
+        }
+    }
+
+    u32x4 *R = lds + w * 256 + 4 * lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        R[j] = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
+    __syncthreads();
+    const int p = threadIdx.x;  // quad p of the tile: 1 KiB contiguous per wave store
+    const u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p] + lds[1024 + p];
+    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
+    uint32_t *dst = out + (uint64_t)i * out_pitch + slot;
+    if (slot + 3 < Lw) {
+        *reinterpret_cast<u32x4 *>(dst) = acc;
+    } else {
+        if (slot + 0 < Lw) dst[0] = acc.x;
+        if (slot + 1 < Lw) dst[1] = acc.y;
+        if (slot + 2 < Lw) dst[2] = acc.z;
+    }
+}
+
+// One field of a summed word as the mean of `count` contributors; cb = count B.
+template <int P>
+__device__ __forceinline__ float unpack_field(uint32_t S, int j, int64_t cb, double denom) {
+    constexpr int W = 32 / P;
+    return (float)((double)((int64_t)((S >> (W * j)) & ((1u << W) - 1u)) - cb) / denom);
+}
+
+// the four floats of one word (P = 4), or of two (P = 2)
+template <int P>
+__device__ __forceinline__ float4 unpack_four(uint32_t S0, uint32_t S1, int64_t cb, double denom) {
+    if constexpr (P == 4)
+        return make_float4(unpack_field<4>(S0, 0, cb, denom), unpack_field<4>(S0, 1, cb, denom),
+                           unpack_field<4>(S0, 2, cb, denom), unpack_field<4>(S0, 3, cb, denom));
+    else
+        return make_float4(unpack_field<2>(S0, 0, cb, denom), unpack_field<2>(S0, 1, cb, denom),
+                           unpack_field<2>(S1, 0, cb, denom), unpack_field<2>(S1, 1, cb, denom));
+}
+
+// out[P l' + j] = float32(float64(field j of sum[l'] - count B) / denom), P l' + j < L; denom = count 2^f
+// (SA_ServiceAgent.py:538-540, 605: the final sum, as a mean).  A thread reads a quad of words (16 bytes) and
+// writes its 4 P floats with 16-byte stores; the up to 4 P - 1 parameters behind the last whole quad go one per
+// thread.  Not in place: the output is P times the input.
+template <int P>
+__global__ __launch_bounds__(256) void decode_unpack_kernel(const uint32_t *__restrict__ sum, uint64_t L, int64_t cb,
+                                                            double denom, float *__restrict__ out) {
+    const uint64_t quads = L / (4 * P), stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t q = t0; q < quads; q += stride) {
+        const uint4 s = reinterpret_cast<const uint4 *>(sum)[q];
+        float4 *dst = reinterpret_cast<float4 *>(out) + P * q;
+        if constexpr (P == 4) {
+            dst[0] = unpack_four<4>(s.x, 0u, cb, denom);
+            dst[1] = unpack_four<4>(s.y, 0u, cb, denom);
+            dst[2] = unpack_four<4>(s.z, 0u, cb, denom);
+            dst[3] = unpack_four<4>(s.w, 0u, cb, denom);
+        } else {
+            dst[0] = unpack_four<2>(s.x, s.y, cb, denom);
+            dst[1] = unpack_four<2>(s.z, s.w, cb, denom);
+        }
+    }
+    const uint64_t l = 4 * P * quads + t0;  // the tail, per element: fewer than 4 P parameters
+    if (l < L) out[l] = unpack_field<P>(sum[l / P], (int)(l % P), cb, denom);
+}
+
 #undef FLM_QR
 #undef FLM_ROTL
 
@@ -1056,6 +1216,52 @@ hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const i
     else
         hipLaunchKernelGGL(encode_mask_kernel<false>, dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
                            d_seeds, d_signs, d_dither, L, tiles, clip, scale, d_out, out_pitch, d_clipped);
+    return hipGetLastError();
+}
+
+template <int P>
+static void launch_encode_pack(bool stochastic, unsigned groups, hipStream_t stream, const float *d_x, uint64_t x_pitch,
+                               const int64_t *d_seg, const uint8_t *d_seeds, const int8_t *d_signs, const uint8_t *d_dither,
+                               uint64_t L, uint64_t Lw, uint32_t tiles, float clip, float scale, uint32_t bias,
+                               uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped) {
+    if (stochastic)
+        hipLaunchKernelGGL((encode_pack_mask_kernel<P, true>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
+                           d_seeds, d_signs, d_dither, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+    else
+        hipLaunchKernelGGL((encode_pack_mask_kernel<P, false>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
+                           d_seeds, d_signs, d_dither, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+}
+
+hipError_t launch_encode_pack_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                                   const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
+                                   int pack, uint32_t bias, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
+                                   hipStream_t stream) {
+    if (pack != 2 && pack != 4) return hipErrorInvalidValue;
+    const uint64_t Lw = (L + (uint64_t)pack - 1) / (uint64_t)pack;
+    const uint64_t groups = encode_mask_groups(N, Lw);
+    if (groups == 0) return hipSuccess;
+    if (groups > 0x7fffffffull || frac_bits < 0 || frac_bits > 30) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)((Lw + 1023) / 1024);
+    const float scale = (float)(1u << frac_bits);
+    if (pack == 2)
+        launch_encode_pack<2>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
+                              L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+    else
+        launch_encode_pack<4>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
+                              L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int64_t count_bias, double denom, float *d_out,
+                                hipStream_t stream) {
+    if (L == 0) return hipSuccess;
+    if (pack != 2 && pack != 4) return hipErrorInvalidValue;
+    const uint64_t quads = L / (4 * (uint64_t)pack);
+    const unsigned g = (unsigned)std::min<uint64_t>(4096, (quads + 255) / 256 + 1);  // + 1: the tail's threads
+    if (pack == 2)
+        hipLaunchKernelGGL(decode_unpack_kernel<2>, dim3(g), dim3(256), 0, stream, d_sum, L, count_bias, denom, d_out);
+    else
+        hipLaunchKernelGGL(decode_unpack_kernel<4>, dim3(g), dim3(256), 0, stream, d_sum, L, count_bias, denom, d_out);
     return hipGetLastError();
 }
 

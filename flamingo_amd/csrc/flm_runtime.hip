@@ -287,6 +287,11 @@ int check_codec(flm_ctx *ctx, int frac_bits, float clip, int64_t n) {
     const char *why = flm::rt::codec_error(frac_bits, clip, n, &headroom);
     return refuse(ctx, why, headroom ? FLM_ERANGE : FLM_EINVAL);
 }
+int check_packed_codec(flm_ctx *ctx, int frac_bits, float clip, int pack, int64_t n, uint32_t *bias) {
+    bool headroom = false;
+    const char *why = flm::rt::packed_codec_error(frac_bits, clip, pack, n, &headroom, bias);
+    return refuse(ctx, why, headroom ? FLM_ERANGE : FLM_EINVAL);
+}
 int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
                          size_t mask_hi, uint64_t prg_slot0, const uint32_t *d_out) {
     bool range = false;
@@ -1052,7 +1057,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4}"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1313,6 +1318,93 @@ int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_b
     FLM_ON_DEVICE(ctx);
     FLM_HIP(ctx, flm::launch_decode_sum(d_sum, L, (double)count * std::ldexp(1.0, frac_bits), d_out,
                                         static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- the packed codec: pack parameters per ring word, rows of ceil(L / pack) words (flm_call_args.h has the rule)
+
+int flm_codec_check_packed(int frac_bits, float clip, int pack, int64_t n_clients) {
+    return check_packed_codec(nullptr, frac_bits, clip, pack, n_clients, nullptr);
+}
+
+int flm_client_encode_pack_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
+                                uint32_t *out, uint32_t *clipped) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, 1, nullptr)) return rc;
+    if (N == 0 || L == 0) return 0;
+    int64_t K = 0;
+    if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::client_encode_pack_mask_args(N, K, L, flm::rt::packed_words(L, pack), dither, clipped),
+               {x, seeds, dither, out, clipped});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_client_encode_pack_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs, L,
+                                                 frac_bits, clip, pack, hc.dev<uint8_t>(2), hc.dev<uint32_t>(3),
+                                                 hc.pitch(3) / 4, hc.dev<uint32_t>(4), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_client_encode_pack_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                                    const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
+                                    int pack, const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch,
+                                    uint32_t *d_clipped, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint32_t bias = 0;
+    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, 1, &bias)) return rc;
+    if (N <= 0 || L == 0) return 0;
+    const size_t Lw = flm::rt::packed_words(L, pack);
+    int64_t K = 0;
+    if (int rc = refuse(ctx, flm::rt::client_args_error(d_x && d_out, N, seg, d_seeds, signs, &K))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, Lw))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;  // the dither stream is indexed by parameter
+    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, Lw)))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+    FLM_ON_DEVICE(ctx);
+    Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
+    if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
+    hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
+    if (e == hipSuccess)
+        e = flm::launch_encode_pack_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
+                                         reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, L, frac_bits, clip, pack,
+                                         bias, d_out, out_pitch, d_clipped, s);
+    if (int rc = stage_done(ctx, up, s, 0)) return rc;
+    FLM_HIP(ctx, e);
+    return 0;
+}
+
+int flm_decode_unpack(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int64_t count,
+                      float *out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, count, nullptr)) return rc;
+    if (L == 0) return 0;
+    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::decode_unpack_args(L, flm::rt::packed_words(L, pack)), {sum, out});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_decode_unpack_dev(ctx, hc.dev<uint32_t>(0), L, frac_bits, clip, pack, count, hc.dev<float>(1), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack, int64_t count,
+                          float *d_out, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint32_t bias = 0;
+    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, count, &bias)) return rc;
+    if (L == 0) return 0;
+    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_decode_unpack(d_sum, L, pack, count * (int64_t)bias, (double)count * std::ldexp(1.0, frac_bits),
+                                           d_out, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -39,6 +39,8 @@ struct StoreRank {
     int cap = 0, n = 0;
     uint32_t *S = nullptr;        // this rank's slots of the partial sum (S words)
     uint32_t *out = nullptr;      // unmask output (S words)
+    float *fout = nullptr;        // packed codec: this rank's decoded floats (pack x its words), grown on demand
+    size_t fout_cap = 0;          // bytes
     uint8_t *seeds = nullptr;     // K x 32 + K signs, per unmask
     size_t seeds_cap = 0;
     void *stage[kStoreRing] = {};
@@ -68,6 +70,8 @@ struct flm_store {
     uint8_t *hseeds = nullptr;   // K x 32 seeds + K signs
     size_t hseeds_cap = 0;
     uint32_t *hout = nullptr;    // L words: every rank's shard lands at its offset lo
+    float *hfout = nullptr;      // packed codec: L_params floats, every rank's at pack x lo; grown on demand
+    size_t hfout_cap = 0;        // bytes
     bool bounce_busy = false;    // a call that failed after enqueueing may have left DMAs reading them
     std::string err;
 };
@@ -139,6 +143,7 @@ void release(flm_store *st) {
         if (r.rows) (void)hipFree(r.rows);
         if (r.S) (void)hipFree(r.S);
         if (r.out) (void)hipFree(r.out);
+        if (r.fout) (void)hipFree(r.fout);
         if (r.seeds) (void)hipFree(r.seeds);
         if (r.uploaded) (void)hipEventDestroy(r.uploaded);
         if (r.consumed) (void)hipEventDestroy(r.consumed);
@@ -146,6 +151,7 @@ void release(flm_store *st) {
     }
     if (st->hseeds) (void)hipHostFree(st->hseeds);
     if (st->hout) (void)hipHostFree(st->hout);
+    if (st->hfout) (void)hipHostFree(st->hfout);
     if (st->t0) (void)hipEventDestroy(st->t0);
     if (st->t1) (void)hipEventDestroy(st->t1);
     if (st->u0) (void)hipEventDestroy(st->u0);
@@ -351,10 +357,25 @@ int flm_store_partial_host(flm_store *st, uint32_t *out) {
     return 0;
 }
 
+// What flm_store_unmask's callers want of the final sum: the words (count 0), their decode in place (pack 1), or
+// the L_params floats of the packed codec.
+struct StoreDecode {
+    int frac_bits = 0;
+    int64_t count = 0;
+    int pack = 1;
+    float clip = 0.0f;
+    size_t L_params = 0;
+};
+
 // flm_store_unmask, and flm_store_unmask_f32 when count > 0: then every device decodes its shard in place
 // (float and uint32 shards are the same size) before the copy it makes anyway, and `out` holds floats.
-static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out, int frac_bits,
-                        int64_t count) {
+// flm_store_unmask_unpack_f32 (pack > 1): every device decodes its words [lo, hi) into a float buffer of its own
+// and copies the floats [pack lo, min(pack hi, L_params)) instead.
+static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out,
+                        const StoreDecode &dec) {
+    const int frac_bits = dec.frac_bits;
+    const int64_t count = dec.count;
+    const size_t P = (size_t)dec.pack;
     flm::rt::DeviceScope dev_scope_;  // the caller's device comes back on return
     if (!st || !out || K < 0 || (K > 0 && (!seeds || !signs))) return sfail(st, FLM_EINVAL, "bad argument");
     if (!st->have_partial) return sfail(st, FLM_EINVAL, "no partial sum: call flm_store_partial at report");
@@ -374,6 +395,14 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
         }
         std::memcpy(st->hseeds, seeds, (size_t)K * 32);
         std::memcpy(st->hseeds + (size_t)K * 32, signs, (size_t)K);
+    }
+    if (P > 1 && st->hfout_cap < dec.L_params * sizeof(float)) {  // idle: the last call synced
+        if (st->hfout) (void)hipHostFree(st->hfout);
+        st->hfout = nullptr;
+        st->hfout_cap = 0;
+        const size_t want = flm::rt::grow_bytes(dec.L_params * sizeof(float));
+        FLM_SHIP(st, hipHostMalloc(&st->hfout, want, hipHostMallocPortable));
+        st->hfout_cap = want;
     }
     FLM_SHIP(st, hipSetDevice(st->rk[0].device));
     FLM_SHIP(st, hipEventRecord(st->u0, flm::rt::stream_of(st->rk[0].ctx)));
@@ -400,6 +429,23 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
                                               K ? reinterpret_cast<const int8_t *>(k.seeds + (size_t)K * 32) : nullptr,
                                               K, n, 0, n, k.lo, k.out, s))
             return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
+        if (P > 1) {
+            // the words [lo, hi) hold the parameters [P lo, P hi), of which the row has the first L_params
+            const size_t np = std::min(P * k.hi, dec.L_params) - P * k.lo;
+            if (k.fout_cap < np * sizeof(float)) {
+                if (k.fout) FLM_SHIP(st, hipStreamSynchronize(s));  // the last unmask's copy may still read it
+                if (k.fout) (void)hipFree(k.fout);
+                k.fout = nullptr;
+                k.fout_cap = 0;
+                const size_t want = flm::rt::grow_bytes(np * sizeof(float));
+                FLM_SHIP(st, hipMalloc(&k.fout, want));
+                k.fout_cap = want;
+            }
+            if (int rc = flm_decode_unpack_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, count, k.fout, s))
+                return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
+            FLM_SHIP(st, hipMemcpyAsync(st->hfout + P * k.lo, k.fout, np * sizeof(float), hipMemcpyDeviceToHost, s));
+            continue;
+        }
         if (count > 0)
             if (int rc = flm_decode_sum_dev(k.ctx, k.out, n, frac_bits, count, reinterpret_cast<float *>(k.out), s))
                 return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
@@ -412,20 +458,35 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
         FLM_SHIP(st, hipStreamSynchronize(flm::rt::stream_of(k.ctx)));
     }
     st->bounce_busy = false;
-    flm::rt::host_copy(st->rk[0].ctx, out, st->hout, st->L * sizeof(uint32_t));
+    if (P > 1) flm::rt::host_copy(st->rk[0].ctx, out, st->hfout, dec.L_params * sizeof(float));
+    else flm::rt::host_copy(st->rk[0].ctx, out, st->hout, st->L * sizeof(uint32_t));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, st->u0, st->u1) == hipSuccess) st->unmask_ms = ms;
     return 0;
 }
 
 int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *out) {
-    return store_unmask(st, seeds, signs, K, out, 0, 0);
+    return store_unmask(st, seeds, signs, K, out, StoreDecode{});
 }
 
 int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, int frac_bits, int64_t count,
                          float *out) {
     if (const char *why = flm::rt::decode_error(frac_bits, count)) return sfail(st, FLM_EINVAL, why);
-    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), frac_bits, count);
+    StoreDecode dec;
+    dec.frac_bits = frac_bits, dec.count = count;
+    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
+}
+
+int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                int frac_bits, float clip, int pack, int64_t count, float *out) {
+    bool headroom = false;
+    if (const char *why = flm::rt::packed_codec_error(frac_bits, clip, pack, count, &headroom, nullptr))
+        return sfail(st, headroom ? FLM_ERANGE : FLM_EINVAL, why);
+    if (st && st->L != flm::rt::packed_words(L_params, pack))
+        return sfail(st, FLM_EINVAL, "the store's length must be ceil(L_params / pack)");
+    StoreDecode dec;
+    dec.frac_bits = frac_bits, dec.count = count, dec.pack = pack, dec.clip = clip, dec.L_params = L_params;
+    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
 }
 
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms) {

@@ -274,11 +274,60 @@ class MaskEngine:
         return out
 
     # ------------------------------------------------- fixed-point codec
-    def codec_check(self, frac_bits: int, clip: float, n_clients: int = 1):
+    def codec_check(self, frac_bits: int, clip: float, n_clients: int = 1, pack: int = 1):
         """Raise unless n_clients updates of magnitude <= clip fit the 32-bit ring at frac_bits
-        (flm_codec_check: n * ceil(clip * 2^frac_bits) <= 2^31 - 1); no device call."""
-        rc = self.lib.flm_codec_check(int(frac_bits), float(clip), int(n_clients))
-        self._check(rc, "flm_codec_check")
+        (flm_codec_check: n * ceil(clip * 2^frac_bits) <= 2^31 - 1); no device call.  pack = 2 or 4: the
+        packed codec's rule instead (flm_codec_check_packed: n * 2 ceil(clip * 2^frac_bits) <= 2^(32/pack) - 1)."""
+        if pack == 1:
+            rc = self.lib.flm_codec_check(int(frac_bits), float(clip), int(n_clients))
+            self._check(rc, "flm_codec_check")
+        else:
+            rc = self.lib.flm_codec_check_packed(int(frac_bits), float(clip), int(pack), int(n_clients))
+            self._check(rc, "flm_codec_check_packed")
+
+    def client_encode_pack_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float,
+                                pack: int, dither=None, return_clipped: bool = False):
+        """client_encode_mask with `pack` (2 or 4) parameters per ring word: float32 x (N, L) in,
+        (N, ceil(L / pack)) uint32 out; field j of word l' is encode(x[pack l' + j]) + ceil(clip 2^frac_bits).
+        The dither stream is indexed by parameter.  flm_client_encode_pack_mask."""
+        seg = np.ascontiguousarray(seg, dtype=np.int64)
+        N = seg.shape[0] - 1
+        seeds = _seeds_array(seeds)
+        signs = _signs_array(signs, seeds.shape[0])
+        if seg[-1] != seeds.shape[0]:
+            raise RuntimeError("seg[-1] must equal the number of seeds")
+        if x is None:
+            raise RuntimeError("x is required")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.shape != (N, L):
+            raise RuntimeError("x must be (N, L)")
+        dp = None
+        if dither is not None:
+            dither = _seeds_array(dither)
+            if dither.shape[0] != N:
+                raise RuntimeError("one 32-byte dither seed per client")
+            dp = p_u8(dither)
+        pack = int(pack)
+        out = np.empty((N, -(-L // pack) if pack > 0 else 0), dtype=np.uint32)
+        clipped = np.zeros(N, dtype=np.uint32)
+        rc = self.lib.flm_client_encode_pack_mask(self.ctx, p_f32(x), N, p_i64(seg), p_u8(seeds), p_i8(signs), L,
+                                                  int(frac_bits), float(clip), pack, dp, p_u32(out),
+                                                  p_u32(clipped) if return_clipped else None)
+        self._check(rc, "flm_client_encode_pack_mask")
+        return (out, clipped) if return_clipped else out
+
+    def decode_unpack(self, total: np.ndarray, L: int, frac_bits: int, clip: float, pack: int, count: int = 1) -> np.ndarray:
+        """The L float32 means of `count` contributors held in the ceil(L / pack) summed packed words `total`
+        (flm_decode_unpack): field - count ceil(clip 2^frac_bits), over count 2^frac_bits."""
+        total = np.ascontiguousarray(total, dtype=np.uint32)
+        pack = int(pack)
+        if total.ndim != 1 or (pack > 0 and total.shape[0] != -(-L // pack)):
+            raise RuntimeError("total must be a vector of ceil(L / pack) words")
+        out = np.empty(L, dtype=np.float32)
+        rc = self.lib.flm_decode_unpack(self.ctx, p_u32(total), L, int(frac_bits), float(clip), pack, int(count),
+                                        p_f32(out))
+        self._check(rc, "flm_decode_unpack")
+        return out
 
     def client_encode_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float, dither=None,
                            return_clipped: bool = False):
@@ -474,6 +523,48 @@ class MaskEngine:
         rc = self.lib.flm_decode_sum_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), int(count),
                                          ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
         self._check(rc, "flm_decode_sum_dev")
+        return out
+
+    def client_encode_pack_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float, pack: int,
+                                    dither_dev=None, clipped=None, stream=None):
+        """Device client_encode_pack_mask: as client_encode_mask_dev, with x (>= N, >= L) float32 and out
+        (>= N, >= ceil(L / pack)) 32-bit.  Enqueued on `stream`; nothing is synchronised."""
+        import torch
+        seg, signs, N, K = _client_seeds(seg, signs, seeds_dev)
+        pack = int(pack)
+        Lw = -(-L // pack) if pack > 0 else L
+        for name, t, n in (("x", x, L), ("out", out, Lw)):
+            if t is None or t.dim() != 2 or t.shape[0] < N or t.shape[1] < n or t.element_size() != 4 or t.stride(1) != 1:
+                raise RuntimeError(f"{name} must be (>= {N}, >= {n}) 32-bit with unit column stride")
+        if x.dtype != torch.float32:
+            raise RuntimeError("x must be float32")
+        if dither_dev is not None and (tuple(dither_dev.shape) != (N, 32) or dither_dev.element_size() != 1
+                                       or not dither_dev.is_contiguous()):
+            raise RuntimeError(f"dither_dev must be a contiguous ({N}, 32) uint8 tensor")
+        if clipped is not None and (clipped.dim() != 1 or clipped.shape[0] < N or clipped.element_size() != 4
+                                    or not clipped.is_contiguous()):
+            raise RuntimeError(f"clipped must be a contiguous (>= {N},) 32-bit tensor")
+        rc = self.lib.flm_client_encode_pack_mask_dev(
+            self.ctx, ctypes.c_void_p(x.data_ptr()), x.stride(0) if N > 1 else x.shape[1], N, p_i64(seg),
+            ctypes.c_void_p(seeds_dev.data_ptr() if K else 0), p_i8(signs), L, int(frac_bits), float(clip), pack,
+            ctypes.c_void_p(dither_dev.data_ptr() if dither_dev is not None else 0), ctypes.c_void_p(out.data_ptr()),
+            out.stride(0) if N > 1 else out.shape[1], ctypes.c_void_p(clipped.data_ptr() if clipped is not None else 0),
+            self._stream_handle(stream))
+        self._check(rc, "flm_client_encode_pack_mask_dev")
+        return out
+
+    def decode_unpack_dev(self, total, out, L: int, frac_bits: int, clip: float, pack: int, count: int = 1, stream=None):
+        """out[:L] = the packed decode of total[:ceil(L / pack)] on CUDA tensors (32-bit in, float32 out, not views
+        of one another)."""
+        import torch
+        pack = int(pack)
+        Lw = -(-L // pack) if pack > 0 else L
+        if total.element_size() != 4 or total.numel() < Lw or out.dtype != torch.float32 or out.numel() < L \
+                or not total.is_contiguous() or not out.is_contiguous():
+            raise RuntimeError(f"total must hold >= {Lw} 32-bit words and out >= {L} float32, both contiguous")
+        rc = self.lib.flm_decode_unpack_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), float(clip),
+                                            pack, int(count), ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
+        self._check(rc, "flm_decode_unpack_dev")
         return out
 
     def prg_expand_dev(self, seeds_dev, out, L: int, slot0: int = 0, stream=None):

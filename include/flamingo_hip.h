@@ -185,6 +185,53 @@ int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, i
 int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, int64_t count, float *d_out,
                        void *stream);
 
+/* ------------------------------------------------ packed fixed-point codec */
+
+/* Several parameters per ring word: pack P = 2 or 4 fields of W = 32 / P bits (pack = 1 is the calls
+ * above; any other value is FLM_EINVAL).  A quantised update needs far fewer than 32 bits, and a round
+ * over L parameters becomes the same round over Lw = ceil(L / P) words: rows, masks and wire bytes
+ * fall by P.  With B = ceil(c * 2^f), the integer of the headroom rule above:
+ *   field: u = q + B, q the codec's encode(x) (|q| <= B in both roundings), so u is in [0, 2B];
+ *     stochastic rounding takes r = PRG(dither_i)[l], indexed by parameter l, not by word;
+ *   word l' = sum_{j < P} u[P * l' + j] << (W * j): consecutive parameters, parameter P * l' in the low
+ *     field; fields of parameters >= L hold 0, are not counted as clipped and are never read as input;
+ *   masks are full 32-bit words indexed by word, PRG(seed)[l'], as before.
+ *   decode(S, count): s_j = (S >> W * j) & (2^W - 1),
+ *     out[P * l' + j] = float32(float64(s_j - count * B) / (float64(count) * 2^f)) for P * l' + j < L:
+ *     bit for bit the unpacked decode of the unpacked sum whenever both codecs have headroom.
+ * Headroom for n contributors: n * 2B <= 2^W - 1, in integers, so that no field of the sum carries into
+ * its neighbour; outside it FLM_ERANGE.  At (f = 7, c = 1, P = 2) that is n <= 255, at (4, 1, 2)
+ * n <= 2047; P = 4 serves small cohorts only: n <= 31 at (2, 1, 4), n <= 127 at (0, 1, 4).
+ *
+ * flm_codec_check_packed: flm_codec_check's refusals, FLM_EINVAL for pack not 2 or 4, FLM_ERANGE outside
+ * the packed headroom; no context, no device.  The agents' server (SA_ServiceAgent.py:538-540, 605: its
+ * final sum) calls it with the real n. */
+int flm_codec_check_packed(int frac_bits, float clip, int pack, int64_t n_clients);
+
+/* Client masking of float input into packed words (SA_ClientAgent.py:300-324):
+ *   out[i][l'] = word l' of x[i] + sum_{k in [seg[i], seg[i+1])} signs[k] * PRG(seeds[k])[l']
+ * x: N x L float32; out: N x ceil(L / pack) words; dither, clipped as flm_client_encode_mask's.  The
+ * encoded word is never stored unmasked.  The packed headroom rule with n = 1. */
+int flm_client_encode_pack_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                const int8_t *signs, size_t L, int frac_bits, float clip, int pack,
+                                const uint8_t *dither, uint32_t *out, uint32_t *clipped);
+/* The same on device buffers (SA_ClientAgent.py:300-324), enqueued on `stream`; nothing is synchronised.
+ * x rows are x_pitch floats apart (a multiple of 4, >= round_up(L, 4)), out rows out_pitch words (a
+ * multiple of 4, >= round_up(ceil(L / pack), 4)); both 16-byte aligned.  The padding of an x row is not
+ * read as input and the padding of an out row is not written. */
+int flm_client_encode_pack_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                                    const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits,
+                                    float clip, int pack, const uint8_t *d_dither, uint32_t *d_out,
+                                    size_t out_pitch, uint32_t *d_clipped, void *stream);
+/* out[0..L) = decode(sum[0..ceil(L / pack)), count): the server's final sum (SA_ServiceAgent.py:538-540,
+ * 605) as the mean of `count` contributors.  The packed headroom rule with n = count. */
+int flm_decode_unpack(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack,
+                      int64_t count, float *out);
+/* The same on device buffers (SA_ServiceAgent.py:538-540, 605), 16-byte aligned; d_out is not d_sum (it
+ * is `pack` times as long). */
+int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
+                          int64_t count, float *d_out, void *stream);
+
 /* Device-resident PRG expansion: d_out[k*pitch + l] = PRG(seed k)[slot0 + l]. */
 int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, uint64_t slot0,
                        uint32_t *d_out, size_t pitch, void *stream);
@@ -554,6 +601,13 @@ int flm_store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs, i
  * (SA_ServiceAgent.py:538-540, 605 and the codec above; SA_ClientAgent.py:300-324 made the input). */
 int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, int frac_bits,
                          int64_t count, float *out);
+/* flm_store_unmask of a store of packed rows (SA_ServiceAgent.py:538-540, 605 and the packed codec above;
+ * SA_ClientAgent.py:300-324 made the input): the store's length must be ceil(L_params / pack), else
+ * FLM_EINVAL.  Each device decodes its word shard [lo, hi) into the floats [pack * lo, min(pack * hi,
+ * L_params)) of a float buffer of its own (flm_decode_unpack_dev) before its copy to the host:
+ * out[0..L_params) is the mean of `count` contributors.  The packed headroom rule with n = count. */
+int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                int frac_bits, float clip, int pack, int64_t count, float *out);
 /* Device time (ms, rank 0's stream) of the last flm_store_unmask, from its seed upload to the end of
  * its copy of final_sum to the host: the part of the call's wall time the GPU accounts for. */
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms);

@@ -55,6 +55,12 @@ for _name, _res, _args in (
         ("flm_client_encode_mask", _int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _u8p, _u32p,
                                           _u32p]),
         ("flm_decode_sum", _int, [_vp, _u32p, _sz, _int, ctypes.c_int64, _f32p]),
+        ("flm_codec_check_packed", _int, [_int, ctypes.c_float, _int, ctypes.c_int64]),
+        ("flm_client_encode_pack_mask", _int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _int, _u8p,
+                                               _u32p, _u32p]),
+        ("flm_decode_unpack", _int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, ctypes.c_int64, _f32p]),
+        ("flm_store_unmask_unpack_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, ctypes.c_int64,
+                                               _f32p]),
         ("flm_hash_to_curve", _int, [_vp, _u8p, _u32p, _int, _u8p, _u32p]),
         ("flm_hash_to_curve_decimal", _int, [_vp, ctypes.c_uint32, _int, _u8p, _u32p])):
     _f = getattr(_lib, _name)
@@ -384,6 +390,52 @@ def decode_sum(total, frac_bits, count=1):
     return out
 
 
+def codec_check_packed(frac_bits, clip, pack, n_clients):
+    """Raise unless n_clients float updates of magnitude <= clip fit `pack` (2 or 4) fields per ring word:
+    n 2 ceil(clip 2^frac_bits) <= 2^(32 / pack) - 1, so that no field of the sum carries into its neighbour.
+    The server's check at set-up, with the real n; pack = 4 serves small cohorts only (n <= 31 at 2 bits, clip 1)."""
+    _check(_lib.flm_codec_check_packed(int(frac_bits), float(clip), int(pack), int(n_clients)))
+
+
+def client_encode_pack_mask(seeds, signs, L, x, frac_bits, clip, pack, dither=None):
+    """client_encode_mask with `pack` parameters per ring word ("replace it with model weights",
+    SA_ClientAgent.py:300-304, masked as :304-324): the VECTOR body is ceil(L / pack) words, field j of word l'
+    holding encode(x[pack l' + j]) + ceil(clip 2^frac_bits).  Returns (uint32[ceil(L / pack)], clipped elements)."""
+    seg = np.array([0, len(seeds)], np.int64)
+    sd, sg, K = _seed_arrays(seeds, signs)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.shape != (L,):
+        raise RuntimeError("vector length error")
+    if pack not in (2, 4):
+        raise RuntimeError("pack must be 2 or 4")
+    dp = None
+    if dither is not None:
+        if len(dither) != 32:
+            raise RuntimeError("the dither seed must be 32 bytes")
+        d = np.frombuffer(bytes(dither), np.uint8).copy()
+        dp = d.ctypes.data_as(_u8p)
+    out, clipped = np.empty(-(-L // pack), np.uint32), np.zeros(1, np.uint32)
+    _check(_lib.flm_client_encode_pack_mask(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p),
+                                            sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), L, int(frac_bits),
+                                            float(clip), int(pack), dp, out.ctypes.data_as(_u32p),
+                                            clipped.ctypes.data_as(_u32p)))
+    return out, int(clipped[0])
+
+
+def decode_unpack(total, L, frac_bits, clip, pack, count=1):
+    """final_sum of packed rows (SA_ServiceAgent.py:538-540, 605) as the L float32 means of `count`
+    contributors: (field - count ceil(clip 2^frac_bits)) / (count 2^frac_bits)."""
+    if pack not in (2, 4):
+        raise RuntimeError("pack must be 2 or 4")
+    total = np.ascontiguousarray(total, dtype=np.uint32)
+    if total.shape != (-(-L // pack),):
+        raise RuntimeError("vector length error")
+    out = np.empty(L, np.float32)
+    _check(_lib.flm_decode_unpack(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip), int(pack),
+                                  int(count), out.ctypes.data_as(_f32p)))
+    return out
+
+
 class VectorStore:
     """The server's VECTOR bodies on the GPU(s) from arrival to final_sum (flm_store_*): hand each
     body to add() in receiveMessage (:205-210), call partial() in report_process (:346-350) and
@@ -442,6 +494,17 @@ class VectorStore:
         out = np.empty(self.L, np.float32)
         self._check(_lib.flm_store_unmask_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
                                               int(frac_bits), int(count), out.ctypes.data_as(_f32p)))
+        return out
+
+    def unmask_unpack_f32(self, seeds, signs, L_params, frac_bits, clip, pack, count=1):
+        """unmask() of a store of packed rows (L = ceil(L_params / pack)), decoded on the GPU(s) before the copy
+        to the host: the L_params float32 means of `count` contributors (:538-540, :605, and the codec of
+        client_encode_pack_mask)."""
+        sd, sg, K = _seed_arrays(seeds, signs)
+        out = np.empty(int(L_params), np.float32)
+        self._check(_lib.flm_store_unmask_unpack_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
+                                                     int(L_params), int(frac_bits), float(clip), int(pack), int(count),
+                                                     out.ctypes.data_as(_f32p)))
         return out
 
     def reset(self):

@@ -131,6 +131,10 @@ static void check_round_lists() {
             for (size_t K : {size_t(0), size_t(3)})
                 for (int opt = 0; opt < 4; ++opt) {
                     through_bounce(client_encode_mask_args(N, K, L, opt & 1, opt & 2));
+                    for (int pack : {2, 4}) {
+                        through_bounce(client_encode_pack_mask_args(N, K, L, packed_words(L, pack), opt & 1, opt & 2));
+                        if (!opt) through_bounce(decode_unpack_args(L, packed_words(L, pack)));
+                    }
                     if (opt < 2) through_bounce(client_mask_args(N, K, L, opt & 1));
                     if (opt < 2) through_bounce(aggregate_unmask_args(K, L, opt & 1));
                     if (opt) continue;
@@ -192,6 +196,24 @@ static void check_round_rules() {
     CHECK(codec_error(16, 0.5f, 65536, &range) && range);                             // 2^31
     CHECK(!codec_error(4, 1.01f, 126322567, &range) && codec_error(4, 1.01f, 126322568, &range) && range);  // m = 17
     CHECK(!codec_error(30, 1.9999999f, 1, &range) && codec_error(30, 2.0f, 1, &range) && range);  // m alone past 2^31 - 1
+    // the packed codec: pack, then the unpacked rule's refusals, then n 2B <= 2^W - 1 at its edges
+    uint32_t B = 0;
+    for (int pack : {0, 1, 3, 8, -2}) CHECK(packed_codec_error(7, 1.0f, pack, 1, &range, &B) && !range);
+    CHECK(packed_codec_error(31, 1.0f, 2, 1, &range, &B) && !range && packed_codec_error(7, 0.0f, 2, 1, &range, &B) && !range);
+    CHECK(packed_codec_error(7, 1.0f, 2, 0, &range, &B) && !range);
+    CHECK(!packed_codec_error(7, 1.0f, 2, 255, &range, &B) && !range && B == 128);
+    CHECK(packed_codec_error(7, 1.0f, 2, 256, &range, &B) && range);
+    CHECK(!packed_codec_error(4, 1.0f, 2, 2047, &range, &B) && B == 16 && packed_codec_error(4, 1.0f, 2, 2048, &range, &B) && range);
+    CHECK(!packed_codec_error(2, 1.0f, 4, 31, &range, &B) && B == 4 && packed_codec_error(2, 1.0f, 4, 32, &range, &B) && range);
+    CHECK(!packed_codec_error(0, 1.0f, 4, 127, &range, &B) && B == 1 && packed_codec_error(0, 1.0f, 4, 128, &range, &B) && range);
+    CHECK(!packed_codec_error(6, 1.9f, 4, 1, &range, &B) && B == 122);                 // 244 <= 255
+    CHECK(packed_codec_error(7, 1.0f, 4, 1, &range, &B) && range);                      // 2B = 256 alone past 2^8 - 1
+    CHECK(packed_codec_error(30, 2.0f, 2, 1, &range, &B) && range);                     // the unpacked rule's refusal first
+    CHECK(packed_words(1, 2) == 1 && packed_words(2, 2) == 1 && packed_words(3, 2) == 2 && packed_words(5, 4) == 2 &&
+          packed_words(0, 4) == 0);
+    const ArgList pe = client_encode_pack_mask_args(3, 7, 5, 2, false, true), pd = decode_unpack_args(5, 2);
+    CHECK(pe.n == 5 && pe.a[0].width == 20 && pe.a[3].width == 8 && pe.a[3].is_out && pe.a[3].in_place && !pe.a[2].present);
+    CHECK(pd.n == 2 && pd.a[0].width == 8 && pd.a[1].width == 20 && pd.a[1].is_out);
     CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
     CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));
     CHECK(!slot_range_error(0, 1ull << 36) && slot_range_error(16, 1ull << 36) && slot_range_error(1ull << 36, 1) &&
