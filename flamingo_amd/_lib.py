@@ -53,6 +53,13 @@ SIGNATURES = {
                                                _vp, _vp, _sz, _vp, _vp]),
     "flm_decode_unpack": (_int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, ctypes.c_int64, _f32p]),
     "flm_decode_unpack_dev": (_int, [_vp, _vp, _sz, _int, ctypes.c_float, _int, ctypes.c_int64, _vp, _vp]),
+    "flm_codec_check_noise": (_int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64, _u64]),
+    "flm_client_encode_noise_mask": (_int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _int, _u8p,
+                                            _int, _u8p, _u32p, _u32p]),
+    "flm_client_encode_noise_mask_dev": (_int, [_vp, _vp, _sz, _int, _i64p, _vp, _i8p, _sz, _int, ctypes.c_float, _int,
+                                                _vp, _int, _vp, _vp, _sz, _vp, _vp]),
+    "flm_decode_unpack_noise": (_int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _f32p]),
+    "flm_decode_unpack_noise_dev": (_int, [_vp, _vp, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _vp, _vp]),
     "flm_prg_expand_dev": (_int, [_vp, _vp, _int, _sz, _u64, _vp, _sz, _vp]),
     "flm_check_signs": (_int, [_vp, ctypes.POINTER(_int)]),
     "flm_last_plan": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
@@ -119,6 +126,8 @@ SIGNATURES = {
     "flm_store_unmask": (_int, [_vp, _u8p, _i8p, _int, _u32p]),
     "flm_store_unmask_f32": (_int, [_vp, _u8p, _i8p, _int, _int, ctypes.c_int64, _f32p]),
     "flm_store_unmask_unpack_f32": (_int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, ctypes.c_int64, _f32p]),
+    "flm_store_unmask_unpack_noise_f32": (_int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
+                                                 ctypes.c_int64, _f32p]),
     "flm_store_unmask_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "flm_store_reset": (_int, [_vp]),
     "flm_host_alloc": (_vp, [_sz]),

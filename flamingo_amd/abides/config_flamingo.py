@@ -78,6 +78,11 @@ def parse(argv):
     # rounding or, with ",sr", stochastic rounding; ",pack2" or ",pack4": that many parameters per ring word (the
     # packed codec: n 2 ceil(CLIP 2^F) must fit 16 or 8 bits, so pack4 serves small cohorts only); off by default
     ap.add_argument("--float_inputs", default=None, metavar="F,CLIP[,sr][,pack2|pack4]")
+    # distributed differential privacy: every client adds a share of binomial noise, BITS fair coins per parameter
+    # (even, 2..1024), to its quantised update inside the masking kernel (protocol.configure(dp_noise=...)); needs
+    # --float_inputs, and headroom for n (ceil(CLIP 2^F) + BITS / 2); turning BITS into an (epsilon, delta) is the
+    # caller's business; off by default
+    ap.add_argument("--dp_noise", type=int, default=0, metavar="BITS")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -164,7 +169,8 @@ def _run(args):
                     check_signatures=True if args.check_signatures else None,
                     gpu_verify=True if args.gpu_verify else None,
                     authenticate_shares=True if args.authenticate_shares else None,
-                    dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs))
+                    dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs),
+                    dp_noise=args.dp_noise)
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -226,8 +232,14 @@ def _run(args):
         if it in server.means:      # float inputs: the decoded mean against the mean of the clients' own floats
             exact = np.mean([np.asarray(agents[i].input_vector, np.float64) for i in server.online_ids[it]], axis=0)
             packed = f", {param.codec_pack()} per word" if param.codec_pack() > 1 else ""
+            diff = server.means[it].astype(np.float64) - exact
+            noised = ""
+            if param.codec_noise_bits():    # the sum of |U| binomial shares: variance |U| b / 4, over (|U| 2^f)^2
+                b, f = param.codec_noise_bits(), param.codec()[0]
+                noised = (f", noise of {b} coins: standard deviation of the difference {float(np.std(diff)):.3e}, "
+                          f"expected sqrt(|U| b) / (2 |U| 2^f) = {np.sqrt(u * b) / (2.0 * u * 2.0 ** f):.3e}")
             print(f"    iteration {it}: float inputs {param.codec()}{packed}: largest |final_mean - mean of the clients' floats| = "
-                  f"{float(np.max(np.abs(server.means[it].astype(np.float64) - exact))):.3e}, "
+                  f"{float(np.max(np.abs(diff))):.3e}{noised}, "
                   f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped")
     print()
     results["server"] = server

@@ -95,6 +95,7 @@ class SA_ClientAgent(Agent):
         self.input_vector = None     # None -> all ones (:304); with float inputs: a synthetic float32 update
         self.clipped = 0             # float inputs: elements of the last update that were clipped
         self.dither_seed = None      # float inputs, stochastic rounding: the last iteration's dither seed
+        self.noise_seed = None       # float inputs with --dp_noise: the last iteration's noise seed
         pki = param.pki(num_clients)
         self.secret_key = pki.client_sk[id]
         self.public_key = pki.client_pk[id]
@@ -239,7 +240,14 @@ class SA_ClientAgent(Agent):
             dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
                 if rounding == "stochastic" else None
             seg = np.array([0, len(seeds)], np.int64)
-            if param.codec_pack() == 1:
+            noise_bits = param.codec_noise_bits()
+            if noise_bits:   # distributed DP: the noise seed is drawn after every other draw, the dither seed included
+                self.noise_seed = bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))
+                vec, clipped = param.engine().client_encode_noise_mask(seg, seeds, signs, self.vector_len, x, frac_bits,
+                                                                       clip, param.codec_pack(), dither=dither,
+                                                                       noise_bits=noise_bits, noise=[self.noise_seed],
+                                                                       return_clipped=True)
+            elif param.codec_pack() == 1:
                 vec, clipped = param.engine().client_encode_mask(seg, seeds, signs, self.vector_len, x, frac_bits, clip,
                                                                  dither=dither, return_clipped=True)
             else:   # packed: the body is param.ring_len() words, the masks with it

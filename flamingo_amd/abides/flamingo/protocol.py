@@ -70,20 +70,28 @@ _codec = None                           # configure(codec=(frac_bits, clip, "nea
 # the store, the masks and the sums are ring_len() = ceil(vector_len / pack) words; vector_len stays the
 # parameter count and final_mean's length
 _codec_pack: int = 1
+# Distributed differential privacy (config_flamingo's --dp_noise BITS): every client adds a share of binomial
+# noise, BITS fair coins per parameter, to its quantised update inside the masking kernel
+# (MaskEngine.client_encode_noise_mask); only the sum of the shares appears in what the server unmasks.  It needs
+# the float inputs.  Off by default, so a run sends what it always sent and draws what it always drew.
+_dp_noise: int = 0
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
-              authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None):
+              authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None,
+              dp_noise: int | None = None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
     "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
-    many parameters into a ring word, False turns them off, None leaves them as they are."""
+    many parameters into a ring word, False turns them off, None leaves them as they are.  dp_noise: the coin
+    flips per parameter of every client's binomial noise share (even, 2..1024; 0 turns it off, None leaves it as
+    it is); it needs the float inputs, and turning those off turns it off."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack
+    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise
     if codec is not None:
         if codec is False:
-            _codec, _codec_pack = None, 1
+            _codec, _codec_pack, _dp_noise = None, 1, 0
         else:
             f, c, mode = codec[:3]
             pack = int(codec[3]) if len(codec) == 4 else 1
@@ -94,6 +102,13 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
             if pack not in (1, 2, 4):
                 raise ValueError("codec pack must be 1, 2 or 4")
             _codec, _codec_pack = (int(f), float(c), mode), pack
+    if dp_noise is not None:
+        b = int(dp_noise)
+        if b < 0 or b > 1024 or b % 2:
+            raise ValueError("dp_noise must be even and in 0..1024")
+        if b and _codec is None:
+            raise ValueError("dp_noise needs the float inputs (codec=...)")
+        _dp_noise = b
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -267,6 +282,11 @@ def codec():
 def codec_pack() -> int:
     """Parameters per ring word of the float inputs: 1 (also when they are off), 2 or 4."""
     return _codec_pack if _codec is not None else 1
+
+
+def codec_noise_bits() -> int:
+    """Coin flips per parameter of every client's binomial noise share: 0 when off (or the float inputs are)."""
+    return _dp_noise if _codec is not None else 0
 
 
 def ring_len() -> int:

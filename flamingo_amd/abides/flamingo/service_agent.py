@@ -84,7 +84,10 @@ class SA_ServiceAgent(Agent):
             # n updates of magnitude up to clip must fit the 32-bit ring: refuse the run, never wrap (FLM_ERANGE)
             # (packed: no field of the sum may carry into its neighbour, n 2 ceil(clip 2^f) <= 2^(32/pack) - 1)
             n = max(1, len(users) or num_clients)
-            if param.codec_pack() == 1:
+            if param.codec_noise_bits():   # ... and every client's noise share, in the worst case
+                param.engine().codec_check(param.codec()[0], param.codec()[1], n, pack=param.codec_pack(),
+                                           noise_bits=param.codec_noise_bits(), L=param.vector_len)
+            elif param.codec_pack() == 1:
                 param.engine().codec_check(param.codec()[0], param.codec()[1], n)
             else:
                 param.engine().codec_check(param.codec()[0], param.codec()[1], n, pack=param.codec_pack())
@@ -340,6 +343,9 @@ class SA_ServiceAgent(Agent):
             self.final_sum = st.unmask(seeds, signs)
             if codec is not None and pack == 1:   # float inputs: the same sum, decoded on the GPU(s) as the mean over U
                 self.final_mean = st.unmask_f32(seeds, signs, codec[0], count)
+            elif codec is not None and param.codec_noise_bits():   # packed, noised: the bias carries noise_bits / 2
+                self.final_mean = st.unmask_unpack_f32(seeds, signs, self.vector_len, codec[0], codec[1], pack, count,
+                                                       noise_bits=param.codec_noise_bits())
             elif codec is not None:               # packed: every device unpacks its word shard into its floats
                 self.final_mean = st.unmask_unpack_f32(seeds, signs, self.vector_len, codec[0], codec[1], pack, count)
         else:
@@ -356,6 +362,9 @@ class SA_ServiceAgent(Agent):
                          + (f", {gpu:.3f} ms GPU" if gpu is not None else ""))
         if codec is not None and self.final_mean is None and pack == 1:
             self.final_mean = param.engine().decode_sum(self.final_sum, codec[0], count)
+        elif codec is not None and self.final_mean is None and param.codec_noise_bits():
+            self.final_mean = param.engine().decode_unpack(self.final_sum, self.vector_len, codec[0], codec[1], pack, count,
+                                                           noise_bits=param.codec_noise_bits())
         elif codec is not None and self.final_mean is None:
             self.final_mean = param.engine().decode_unpack(self.final_sum, self.vector_len, codec[0], codec[1], pack, count)
         if codec is not None:

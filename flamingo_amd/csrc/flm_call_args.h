@@ -102,6 +102,39 @@ inline const char *packed_codec_error(int frac_bits, float clip, int pack, int64
                      : nullptr;
 }
 
+// The codec with distributed-DP binomial noise: every client adds Z in [-b/2, b/2], b = noise_bits even in
+// 0..1024 (0: off, the rules above alone), pack = 1, 2 or 4.  First the refusals of the rule above for that pack,
+// then the worst case in integers with B_n = B + b/2: unpacked n B_n <= 2^31 - 1, packed n 2 B_n <= 2^W - 1
+// (FLM_ERANGE), and for a row of L_params > 0 parameters ceil(b / 32) ceil(L_params / 16) <= 2^32 blocks of the
+// noise stream, whose block counter has no high word (FLM_ERANGE).  *bias: B, the codec's own; *bias_n: B_n.
+inline const char *noise_codec_error(int frac_bits, float clip, int pack, int noise_bits, int64_t n, uint64_t L_params,
+                                     bool *range, uint32_t *bias, uint32_t *bias_n) {
+    *range = false;
+    if (pack != 1 && pack != 2 && pack != 4) return "pack must be 1, 2 or 4";
+    if (noise_bits < 0 || noise_bits > 1024 || noise_bits % 2) return "noise_bits must be even and in 0..1024";
+    uint32_t B32 = 0;
+    if (const char *why = pack == 1 ? codec_error(frac_bits, clip, n, range)
+                                    : packed_codec_error(frac_bits, clip, pack, n, range, &B32))
+        return why;
+    const uint64_t B = (uint64_t)std::ceil((double)clip * std::ldexp(1.0, frac_bits));  // <= 2^31 - 1: the rule passed
+    const uint64_t Bn = B + (uint64_t)noise_bits / 2;
+    if (bias) *bias = (uint32_t)B;
+    if (bias_n) *bias_n = (uint32_t)Bn;
+    if (noise_bits == 0) return nullptr;
+    const uint64_t top = pack == 1 ? 2147483647ull : (uint64_t(1) << (32 / pack)) - 1;
+    const uint64_t each = pack == 1 ? Bn : 2 * Bn;
+    if (each > top || (uint64_t)n > top / each) {
+        *range = true;
+        return "that many contributors of magnitude up to ceil(clip 2^frac_bits) + noise_bits / 2 have no headroom";
+    }
+    const uint64_t draws = ((uint64_t)noise_bits + 31) / 32, blocks = L_params / 16 + (L_params % 16 ? 1 : 0);
+    if (blocks > (uint64_t(1) << 32) / draws) {  // draws blocks <= 2^32, without overflow
+        *range = true;
+        return "the noise stream of a row that long ends beyond 2^32 blocks (its block counter has no high word)";
+    }
+    return nullptr;
+}
+
 // words of a row of L parameters
 constexpr size_t packed_words(size_t L, int pack) { return (L + (size_t)pack - 1) / (size_t)pack; }
 
@@ -339,6 +372,13 @@ inline ArgList client_encode_pack_mask_args(size_t N, size_t K, size_t L, size_t
     return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
              arg_in(N * 32, bytes_in, dither), in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))),
              arg_out(N * 4, bytes_out, clipped)}, 5};
+}
+// x, seeds, dither, noise, out, clipped: the packed call's list with the clients' N x 32 noise seeds, which
+// travel in ec_scal (pack = 1: Lw = L)
+inline ArgList client_encode_noise_mask_args(size_t N, size_t K, size_t L, size_t Lw, bool dither, bool clipped) {
+    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
+             arg_in(N * 32, bytes_in, dither), arg_in(N * 32, ec_scal),
+             in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))), arg_out(N * 4, bytes_out, clipped)}, 6};
 }
 // sum (Lw words), out (L floats)
 inline ArgList decode_unpack_args(size_t L, size_t Lw) {

@@ -57,6 +57,12 @@ hipError_t launch_encode_pack_mask(const float *d_x, uint64_t x_pitch, int N, co
                                    const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
                                    int pack, uint32_t bias, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
                                    hipStream_t stream);
+// The same with the client's binomial noise share (encode_noise_mask_kernel): pack = 1, 2 or 4; noise_bits even in
+// 2..1024; d_noise N x 32 bytes; bias = ceil(clip 2^frac_bits), the codec's own (ignored at pack = 1).
+hipError_t launch_encode_noise_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                                    const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, int noise_bits,
+                                    uint64_t L, int frac_bits, float clip, int pack, uint32_t bias, uint32_t *d_out,
+                                    uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream);
 // d_out[pack l' + j] = float32(float64(field j of d_sum[l'] - count_bias) / denom) for the L parameters; d_out is
 // not d_sum; both 16-byte aligned
 hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int64_t count_bias, double denom, float *d_out,

@@ -1152,6 +1152,177 @@ __global__ __launch_bounds__(256) void encode_pack_mask_kernel(const float *__re
     }
 }
 
+// ------------------------------------------------------------ distributed-DP noise inside the encode-mask kernels
+// The binomial mechanism (tests/dp_cases.py): b = noise_bits fair coins per parameter and
+// client, m = ceil(b / 32) draws, r = b mod 32.  Draw d of parameter l is word 16 (m (l / 16) + d) + l % 16 of
+// PRG(noise_i), the last draw ANDed with 2^r - 1 when r != 0; Z[l] = sum_d popcount(draw d) - b / 2; q' = q + Z.
+// Unpacked the ring word is uint32(q'); packed the field is q' + B + b / 2 = q + B + sum_d popcount(draw d).
+
+// One noise block: ChaCha block `blk` of the client's noise stream holds one draw for the 16 parameters par..par + 15.
+// Unpacked, their popcounts go straight into the accumulator; packed, P of them make a word of the wave's own LDS
+// region (Q: the 4 / P quads of this parameter block), which no other wave and no other lane touches.
+template <int P>
+__device__ __forceinline__ void noise_block_add(const uint8_t *__restrict__ key, uint32_t blk, uint32_t draw_mask,
+                                                uint64_t par, uint64_t L, uint32_t (&m)[16], u32x4 *Q) {
+    uint32_t z[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) z[j] = 0u;
+    chacha_raw_add(key, blk, kAbcd, z);
+    if constexpr (P == 1) {
+        // parameters past L are never stored, so their noise needs no predicate here
+#pragma unroll
+        for (int j = 0; j < 16; ++j) m[j] = __popc(z[j] & draw_mask) + m[j];  // one v_bcnt_u32_b32 each
+    } else {
+        constexpr int W = 32 / P;
+        // a stored word's upper fields may lie past L: those parameters get no noise
+        const uint32_t have = par < L ? (uint32_t)(L - par < 16 ? L - par : 16) : 0u;
+        uint32_t e[16 / P];
+#pragma unroll
+        for (int q = 0; q < 16 / P; ++q) {
+            e[q] = 0u;
+#pragma unroll
+            for (int jj = 0; jj < P; ++jj) {
+                const int j = P * q + jj;
+                e[q] += ((uint32_t)j < have ? (uint32_t)__popc(z[j] & draw_mask) : 0u) << (W * jj);
+            }
+        }
+        if constexpr (P == 4) {
+            Q[0] += u32x4{e[0], e[1], e[2], e[3]};
+        } else {
+            Q[0] += u32x4{e[0], e[1], e[2], e[3]};
+            Q[1] += u32x4{e[4], e[5], e[6], e[7]};
+        }
+    }
+}
+
+// out[i][l'] = the noised word l' of x[i] + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l']
+// encode_mask_kernel (P = 1) and encode_pack_mask_kernel (P = 2, 4) with the client's noise share added in
+// registers: the same grid of (client, 1024-word tile) workgroups, lane t of every wave owns ChaCha block t of the
+// tile, the four partials meet in LDS and the tile is stored once.  A lane's 16 P parameters are P parameter
+// blocks of 16 and need `draws` noise blocks each: block draws (P (64 tile + t) + d) + dd of the noise stream is
+// draw dd of parameter block d.  A noise block only adds, so it is a unit like a seed, and any wave can run it:
+// the P draws noise units (unit u is draw u / P of parameter block u % P) and then the client's seeds form one
+// list that is dealt as encode_pack_mask_kernel deals its seeds round the encoding wave's E blocks: the first 3 E
+// go round ranks 1..3, the rest round all four from rank 0.  The loop over the list is rolled and its bound is
+// host-known; nothing loops on data.
+// Unpacked, everything adds into the accumulator registers and the encoding wave adds -b / 2 once per parameter
+// (`half`).  Packed, a wave's noise words and the encoding wave's packed words go to the wave's own LDS region
+// (zeroed first, indexed dynamically by the parameter block), the accumulator joins them at the end, and the
+// bias is B: the +b / 2 of the field bias B_n and the -b / 2 of Z cancel, so the popcounts add as they are.
+template <int P, bool STOCHASTIC>
+__global__ __launch_bounds__(256) void encode_noise_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
+                                                                const int64_t *__restrict__ seg,
+                                                                const uint8_t *__restrict__ seeds,
+                                                                const int8_t *__restrict__ signs,
+                                                                const uint8_t *__restrict__ dither,
+                                                                const uint8_t *__restrict__ noise, uint32_t draws,
+                                                                uint32_t last_mask, uint32_t half, uint64_t L,
+                                                                uint64_t Lw, uint32_t tiles, float clip, float scale,
+                                                                uint32_t bias, uint32_t *__restrict__ out,
+                                                                uint64_t out_pitch, uint32_t *__restrict__ clipped) {
+    static_assert(P == 1 || P == 2 || P == 4, "one, two or four fields per word");
+    constexpr int W = 32 / P;
+    constexpr int E = STOCHASTIC ? P : 1;
+    __shared__ u32x4 lds[4 * 256];  // 16 KiB: one 4 KiB region per wave
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
+    const uint32_t ctr = tile * 64u + (uint32_t)lane;
+    const uint64_t par0 = (uint64_t)P * ((uint64_t)tile * 1024u + 16u * (uint64_t)lane);  // the lane's first parameter
+    const int64_t k_lo = seg[i];
+    const int64_t n_noise = (int64_t)P * (int64_t)draws, n_units = n_noise + (seg[i + 1] - k_lo);
+
+    u32x4 *R = lds + w * 256 + 4 * lane;  // the lane's 16 words of its wave's partial
+    if constexpr (P > 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) R[j] = u32x4{0u, 0u, 0u, 0u};
+    }
+    uint32_t m[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m[j] = 0u;
+    uint32_t nneg = 0;
+    const int rank = 3 - w;
+#pragma unroll 1
+    for (int64_t u = rank ? rank - 1 : 3 * E; u < n_units; u += (u + 3 < 3 * E ? 3 : 4)) {
+        if (u < n_noise) {
+            const uint32_t d = (uint32_t)u % (uint32_t)P, dd = (uint32_t)u / (uint32_t)P;
+            // draws ceil(L / 16) <= 2^32 (the call's length rule): the counter of a parameter block the row has
+            // stays below 2^32; a block past L may wrap, and is predicated away or never stored
+            noise_block_add<P>(noise + 32 * (size_t)i, draws * ((uint32_t)P * ctr + d) + dd,
+                               dd + 1 == draws ? last_mask : 0xffffffffu, par0 + 16u * d, L, m, R + (4 / P) * d);
+        } else {
+            const int64_t k = k_lo + (u - n_noise);
+            const bool neg = signs[k] < 0;
+            nneg += neg ? 1u : 0u;
+            chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
+        }
+    }
+    if (rank == 0) {
+        const float *xr = x + (uint64_t)i * x_pitch;
+        uint32_t nclip = 0;
+        // one dither block's parameters per pass, the passes not unrolled, as in encode_pack_mask_kernel
+#pragma unroll 1
+        for (int d = 0; d < P; ++d) {
+            uint32_t r[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) r[j] = 0u;
+            if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, (uint32_t)P * ctr + (uint32_t)d, kAbcd, r);
+            uint32_t e[16 / P];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint64_t s = par0 + 16u * (uint32_t)d + 4u * j;
+                // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+                const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const uint32_t u0 = codec_field<STOCHASTIC>(s + 0 < L, v.x, clip, scale, r[4 * j + 0], bias, nclip);
+                const uint32_t u1 = codec_field<STOCHASTIC>(s + 1 < L, v.y, clip, scale, r[4 * j + 1], bias, nclip);
+                const uint32_t u2 = codec_field<STOCHASTIC>(s + 2 < L, v.z, clip, scale, r[4 * j + 2], bias, nclip);
+                const uint32_t u3 = codec_field<STOCHASTIC>(s + 3 < L, v.w, clip, scale, r[4 * j + 3], bias, nclip);
+                if constexpr (P == 1) {  // bias is 0: the words themselves, less b / 2 (words past L are not stored)
+                    m[4 * j + 0] += u0 - half;
+                    m[4 * j + 1] += u1 - half;
+                    m[4 * j + 2] += u2 - half;
+                    m[4 * j + 3] += u3 - half;
+                } else if constexpr (P == 4) {
+                    e[j] = u0 | (u1 << W) | (u2 << 2 * W) | (u3 << 3 * W);
+                } else {
+                    e[2 * j + 0] = u0 | (u1 << W);
+                    e[2 * j + 1] = u2 | (u3 << W);
+                }
+            }
+            if constexpr (P == 4) {
+                R[d] += u32x4{e[0], e[1], e[2], e[3]};
+            } else if constexpr (P == 2) {
+                R[2 * d + 0] += u32x4{e[0], e[1], e[2], e[3]};
+                R[2 * d + 1] += u32x4{e[4], e[5], e[6], e[7]};
+            }
+        }
+        if (clipped) {  // only this wave counts: its total is the workgroup's
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
+            if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
+        }
+    }
+
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const u32x4 a = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
+        if constexpr (P == 1) R[j] = a;
+        else R[j] += a;
+    }
+    __syncthreads();
+    const int p = threadIdx.x;  // quad p of the tile: 1 KiB contiguous per wave store
+    const u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p];
+    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
+    uint32_t *dst = out + (uint64_t)i * out_pitch + slot;
+    if (slot + 3 < Lw) {
+        *reinterpret_cast<u32x4 *>(dst) = acc;
+    } else {
+        if (slot + 0 < Lw) dst[0] = acc.x;
+        if (slot + 1 < Lw) dst[1] = acc.y;
+        if (slot + 2 < Lw) dst[2] = acc.z;
+    }
+}
+
 // One field of a summed word as the mean of `count` contributors; cb = count B.
 template <int P>
 __device__ __forceinline__ float unpack_field(uint32_t S, int j, int64_t cb, double denom) {
@@ -1249,6 +1420,48 @@ hipError_t launch_encode_pack_mask(const float *d_x, uint64_t x_pitch, int N, co
     else
         launch_encode_pack<4>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
                               L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+    return hipGetLastError();
+}
+
+template <int P>
+static void launch_encode_noise(bool stochastic, unsigned groups, hipStream_t stream, const float *d_x, uint64_t x_pitch,
+                                const int64_t *d_seg, const uint8_t *d_seeds, const int8_t *d_signs, const uint8_t *d_dither,
+                                const uint8_t *d_noise, uint32_t draws, uint32_t last_mask, uint32_t half, uint64_t L,
+                                uint64_t Lw, uint32_t tiles, float clip, float scale, uint32_t bias, uint32_t *d_out,
+                                uint64_t out_pitch, uint32_t *d_clipped) {
+    if (stochastic)
+        hipLaunchKernelGGL((encode_noise_mask_kernel<P, true>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
+                           d_seeds, d_signs, d_dither, d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias,
+                           d_out, out_pitch, d_clipped);
+    else
+        hipLaunchKernelGGL((encode_noise_mask_kernel<P, false>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
+                           d_seeds, d_signs, d_dither, d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias,
+                           d_out, out_pitch, d_clipped);
+}
+
+hipError_t launch_encode_noise_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                                    const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, int noise_bits,
+                                    uint64_t L, int frac_bits, float clip, int pack, uint32_t bias, uint32_t *d_out,
+                                    uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream) {
+    if (pack != 1 && pack != 2 && pack != 4) return hipErrorInvalidValue;
+    if (!d_noise || noise_bits < 2 || noise_bits > 1024 || noise_bits % 2) return hipErrorInvalidValue;
+    const uint64_t Lw = (L + (uint64_t)pack - 1) / (uint64_t)pack;
+    const uint64_t groups = encode_mask_groups(N, Lw);
+    if (groups == 0) return hipSuccess;
+    if (groups > 0x7fffffffull || frac_bits < 0 || frac_bits > 30) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)((Lw + 1023) / 1024);
+    const float scale = (float)(1u << frac_bits);
+    const uint32_t draws = (uint32_t)(noise_bits + 31) / 32, r = (uint32_t)noise_bits % 32;
+    const uint32_t last_mask = r ? (1u << r) - 1u : 0xffffffffu, half = (uint32_t)noise_bits / 2;
+    if (pack == 1)
+        launch_encode_noise<1>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
+                               d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, 0u, d_out, out_pitch, d_clipped);
+    else if (pack == 2)
+        launch_encode_noise<2>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
+                               d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+    else
+        launch_encode_noise<4>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
+                               d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
     return hipGetLastError();
 }
 

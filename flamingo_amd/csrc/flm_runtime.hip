@@ -292,6 +292,12 @@ int check_packed_codec(flm_ctx *ctx, int frac_bits, float clip, int pack, int64_
     const char *why = flm::rt::packed_codec_error(frac_bits, clip, pack, n, &headroom, bias);
     return refuse(ctx, why, headroom ? FLM_ERANGE : FLM_EINVAL);
 }
+int check_noise_codec(flm_ctx *ctx, int frac_bits, float clip, int pack, int noise_bits, int64_t n, uint64_t L_params,
+                      uint32_t *bias, uint32_t *bias_n) {
+    bool range = false;
+    const char *why = flm::rt::noise_codec_error(frac_bits, clip, pack, noise_bits, n, L_params, &range, bias, bias_n);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
 int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
                          size_t mask_hi, uint64_t prg_slot0, const uint32_t *d_out) {
     bool range = false;
@@ -1057,7 +1063,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4}"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1404,6 +1410,109 @@ int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int fra
     if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
     FLM_ON_DEVICE(ctx);
     FLM_HIP(ctx, flm::launch_decode_unpack(d_sum, L, pack, count * (int64_t)bias, (double)count * std::ldexp(1.0, frac_bits),
+                                           d_out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- distributed-DP binomial noise drawn inside the encode-mask kernels (flm_call_args.h has the rule)
+
+int flm_codec_check_noise(int frac_bits, float clip, int pack, int noise_bits, int64_t n_clients, uint64_t L_params) {
+    return check_noise_codec(nullptr, frac_bits, clip, pack, noise_bits, n_clients, L_params, nullptr, nullptr);
+}
+
+int flm_client_encode_noise_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                 const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
+                                 int noise_bits, const uint8_t *noise, uint32_t *out, uint32_t *clipped) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, 1, L, nullptr, nullptr)) return rc;
+    if (noise_bits == 0)  // off: the calls there were, byte for byte
+        return pack == 1 ? flm_client_encode_mask(ctx, x, N, seg, seeds, signs, L, frac_bits, clip, dither, out, clipped)
+                         : flm_client_encode_pack_mask(ctx, x, N, seg, seeds, signs, L, frac_bits, clip, pack, dither, out,
+                                                       clipped);
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (!noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
+    if (N == 0 || L == 0) return 0;
+    int64_t K = 0;
+    if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::client_encode_noise_mask_args(N, K, L, flm::rt::packed_words(L, pack), dither, clipped),
+               {x, seeds, dither, noise, out, clipped});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_client_encode_noise_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs,
+                                                  L, frac_bits, clip, pack, hc.dev<uint8_t>(2), noise_bits,
+                                                  hc.dev<uint8_t>(3), hc.dev<uint32_t>(4), hc.pitch(4) / 4,
+                                                  hc.dev<uint32_t>(5), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_client_encode_noise_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                                     const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
+                                     int pack, const uint8_t *d_dither, int noise_bits, const uint8_t *d_noise,
+                                     uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint32_t bias = 0;
+    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, 1, L, &bias, nullptr)) return rc;
+    if (noise_bits == 0)  // off: the calls there were, byte for byte
+        return pack == 1 ? flm_client_encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, frac_bits, clip, d_dither,
+                                                      d_out, out_pitch, d_clipped, stream)
+                         : flm_client_encode_pack_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, frac_bits, clip, pack,
+                                                           d_dither, d_out, out_pitch, d_clipped, stream);
+    if (!d_noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
+    if (N <= 0 || L == 0) return 0;
+    const size_t Lw = flm::rt::packed_words(L, pack);
+    int64_t K = 0;
+    if (int rc = refuse(ctx, flm::rt::client_args_error(d_x && d_out, N, seg, d_seeds, signs, &K))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, Lw))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;  // the dither stream is indexed by parameter
+    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, Lw)))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+    FLM_ON_DEVICE(ctx);
+    Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
+    if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
+    hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
+    if (e == hipSuccess)
+        e = flm::launch_encode_noise_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
+                                          reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, d_noise, noise_bits, L,
+                                          frac_bits, clip, pack, bias, d_out, out_pitch, d_clipped, s);
+    if (int rc = stage_done(ctx, up, s, 0)) return rc;
+    FLM_HIP(ctx, e);
+    return 0;
+}
+
+int flm_decode_unpack_noise(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int noise_bits,
+                            int64_t count, float *out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
+    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, count, 0, nullptr, nullptr)) return rc;
+    if (L == 0) return 0;
+    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::decode_unpack_args(L, flm::rt::packed_words(L, pack)), {sum, out});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_decode_unpack_noise_dev(ctx, hc.dev<uint32_t>(0), L, frac_bits, clip, pack, noise_bits, count,
+                                             hc.dev<float>(1), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_decode_unpack_noise_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
+                                int noise_bits, int64_t count, float *d_out, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
+    uint32_t bias_n = 0;
+    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, count, 0, nullptr, &bias_n)) return rc;
+    if (L == 0) return 0;
+    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
+    FLM_ON_DEVICE(ctx);
+    // decode_unpack_kernel as it is: only the bias changes, B_n = B + noise_bits / 2 in B's place
+    FLM_HIP(ctx, flm::launch_decode_unpack(d_sum, L, pack, count * (int64_t)bias_n, (double)count * std::ldexp(1.0, frac_bits),
                                            d_out, static_cast<hipStream_t>(stream)));
     return 0;
 }

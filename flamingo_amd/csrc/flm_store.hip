@@ -365,6 +365,7 @@ struct StoreDecode {
     int pack = 1;
     float clip = 0.0f;
     size_t L_params = 0;
+    int noise_bits = 0;  // the clients' binomial noise: the packed decode's bias is B + noise_bits / 2
 };
 
 // flm_store_unmask, and flm_store_unmask_f32 when count > 0: then every device decodes its shard in place
@@ -441,7 +442,9 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
                 FLM_SHIP(st, hipMalloc(&k.fout, want));
                 k.fout_cap = want;
             }
-            if (int rc = flm_decode_unpack_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, count, k.fout, s))
+            if (int rc = dec.noise_bits ? flm_decode_unpack_noise_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack,
+                                                                     dec.noise_bits, count, k.fout, s)
+                                        : flm_decode_unpack_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, count, k.fout, s))
                 return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
             FLM_SHIP(st, hipMemcpyAsync(st->hfout + P * k.lo, k.fout, np * sizeof(float), hipMemcpyDeviceToHost, s));
             continue;
@@ -486,6 +489,22 @@ int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_
         return sfail(st, FLM_EINVAL, "the store's length must be ceil(L_params / pack)");
     StoreDecode dec;
     dec.frac_bits = frac_bits, dec.count = count, dec.pack = pack, dec.clip = clip, dec.L_params = L_params;
+    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
+}
+
+int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                      int frac_bits, float clip, int pack, int noise_bits, int64_t count, float *out) {
+    if (noise_bits == 0)  // off: the call there was
+        return flm_store_unmask_unpack_f32(st, seeds, signs, K, L_params, frac_bits, clip, pack, count, out);
+    bool range = false;
+    if (pack == 1) return sfail(st, FLM_EINVAL, "pack must be 2 or 4");
+    if (const char *why = flm::rt::noise_codec_error(frac_bits, clip, pack, noise_bits, count, 0, &range, nullptr, nullptr))
+        return sfail(st, range ? FLM_ERANGE : FLM_EINVAL, why);
+    if (st && st->L != flm::rt::packed_words(L_params, pack))
+        return sfail(st, FLM_EINVAL, "the store's length must be ceil(L_params / pack)");
+    StoreDecode dec;
+    dec.frac_bits = frac_bits, dec.count = count, dec.pack = pack, dec.clip = clip, dec.L_params = L_params;
+    dec.noise_bits = noise_bits;
     return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
 }
 

@@ -232,6 +232,71 @@ int flm_decode_unpack(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits
 int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
                           int64_t count, float *d_out, void *stream);
 
+/* ------------------------------------- distributed-DP noise in the codec */
+
+/* Distributed differential privacy by the binomial mechanism (Agarwal et al., "cpSGD", NeurIPS 2018):
+ * every client adds a small share of integer noise to its quantised update before masking, so only
+ * the sum of the shares ever appears in what the server unmasks.  The reference's learning example
+ * does the local half on the host (agent/examples/crypto/PPFL_ClientAgent.py:219-221, 274-285: Laplace
+ * noise added to the weights before secure aggregation); here the share is drawn inside the
+ * encode-mask kernel (SA_ClientAgent.py:300-324), so the noised word exists only in registers.
+ *   noise_bits b: fair coin flips per parameter per client; 0 = off, else even, 2 <= b <= 1024.
+ *     m = ceil(b / 32) draws, r = b mod 32.
+ *   noise: one 32-byte seed per client, N x 32 bytes; secret and fresh per iteration, like the dither
+ *     seed.  The stream is PRG(noise_i), the PRG of every mask and of the dither.
+ *   draw d < m of parameter l: w(l, d) = PRG(noise_i)[16 * (m * (l / 16) + d) + l % 16]; if r != 0 the
+ *     last draw (d = m - 1) is ANDed with 2^r - 1.  Block-interleaved: ChaCha block m * beta + d gives
+ *     draw d of all 16 parameters of parameter block beta.  Indexed by parameter, not by ring word, in
+ *     every pack mode, as the dither is.
+ *   Z_i[l] = sum_d popcount(w(l, d)) - b / 2: in [-b / 2, b / 2], mean 0, variance b / 4.
+ *   q' = q + Z, q the codec's encode in either rounding.  pack = 1: the ring word is uint32(q').
+ *     pack = 2, 4: the field is u = q' + B_n, B_n = B + b / 2, B = ceil(c * 2^f), so u is in [0, 2 B_n].
+ *     Parameters >= L get no noise: their fields hold 0, they are not counted as clipped and never
+ *     stored.  The clipped count is that of the same call without noise.
+ *   decode: pack = 1: flm_decode_sum as it is (the noise has zero mean); packed: the packed decode with
+ *     B_n in B's place.
+ * Headroom, worst case, in exact integers, FLM_ERANGE outside it: pack = 1: n * B_n <= 2^31 - 1; packed:
+ * n * 2 * B_n <= 2^W - 1, W = 32 / pack.  (f = 4, c = 1, P = 2, b = 30): B_n = 31, n <= 1057; (2, 1, 4, 2):
+ * B_n = 5, n <= 25; (7, 1, 2) with n = 255 has no room for any noise.  The bound is worst case, every coin
+ * of every client on one side; a probabilistic bound is out of scope.  Length: m * ceil(L / 16) <= 2^32,
+ * because the noise stream's block counter has no high word; else FLM_ERANGE.
+ * The decoded mean over |U| contributors carries noise of standard deviation
+ * sqrt(|U| * b) / (2 * |U| * 2^f); a dropped client's share is simply absent.  Converting b to an
+ * (epsilon, delta) is the caller's business.
+ *
+ * flm_codec_check_noise (SA_ClientAgent.py:300-324; PPFL_ClientAgent.py:219-221, 274-285): pack 1, 2 or
+ * 4; FLM_EINVAL for any other pack and for noise_bits odd, negative or > 1024, and the refusals of
+ * flm_codec_check (pack = 1) or flm_codec_check_packed; FLM_ERANGE outside the headroom, and, when
+ * L_params > 0, outside the length rule.  No context, no device.  noise_bits = 0: those checks alone. */
+int flm_codec_check_noise(int frac_bits, float clip, int pack, int noise_bits, int64_t n_clients, uint64_t L_params);
+
+/* Client masking of float input with the client's noise share (SA_ClientAgent.py:300-324;
+ * agent/examples/crypto/PPFL_ClientAgent.py:219-221, 274-285): flm_client_encode_pack_mask's arguments,
+ * pack 1 (rows of L words, as flm_client_encode_mask), 2 or 4, and noise_bits with the N x 32 bytes of
+ * `noise`.  noise_bits = 0 runs flm_client_encode_mask or flm_client_encode_pack_mask, `noise` is
+ * ignored and the result is theirs bit for bit; noise_bits > 0 with `noise` NULL is FLM_EINVAL, refused
+ * before anything is launched.  The rule above with n = 1 and L. */
+int flm_client_encode_noise_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                 const int8_t *signs, size_t L, int frac_bits, float clip, int pack,
+                                 const uint8_t *dither, int noise_bits, const uint8_t *noise, uint32_t *out,
+                                 uint32_t *clipped);
+/* The same on device buffers (SA_ClientAgent.py:300-324; PPFL_ClientAgent.py:219-221, 274-285), enqueued
+ * on `stream`; nothing is synchronised, seg and signs are staged through the slot pool.  Pitches and
+ * alignment as flm_client_encode_pack_mask_dev's; d_noise: N x 32 bytes on the device. */
+int flm_client_encode_noise_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                                     const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits,
+                                     float clip, int pack, const uint8_t *d_dither, int noise_bits,
+                                     const uint8_t *d_noise, uint32_t *d_out, size_t out_pitch,
+                                     uint32_t *d_clipped, void *stream);
+/* flm_decode_unpack of noised packed rows (SA_ClientAgent.py:300-324 and PPFL_ClientAgent.py:219-221,
+ * 274-285 made the input; SA_ServiceAgent.py:538-540, 605 the sum): pack 2 or 4, the bias count * B_n.
+ * The headroom rule above with n = count. */
+int flm_decode_unpack_noise(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack,
+                            int noise_bits, int64_t count, float *out);
+/* The same on device buffers (SA_ClientAgent.py:300-324; PPFL_ClientAgent.py:219-221, 274-285). */
+int flm_decode_unpack_noise_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
+                                int noise_bits, int64_t count, float *d_out, void *stream);
+
 /* Device-resident PRG expansion: d_out[k*pitch + l] = PRG(seed k)[slot0 + l]. */
 int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, uint64_t slot0,
                        uint32_t *d_out, size_t pitch, void *stream);
@@ -608,6 +673,13 @@ int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *sign
  * out[0..L_params) is the mean of `count` contributors.  The packed headroom rule with n = count. */
 int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
                                 int frac_bits, float clip, int pack, int64_t count, float *out);
+/* flm_store_unmask_unpack_f32 of noised packed rows (SA_ClientAgent.py:300-324 and
+ * agent/examples/crypto/PPFL_ClientAgent.py:219-221, 274-285 made the input): the bias is
+ * count * (B + noise_bits / 2); the noised headroom rule with n = count.  noise_bits = 0 is
+ * flm_store_unmask_unpack_f32. */
+int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K,
+                                      size_t L_params, int frac_bits, float clip, int pack, int noise_bits,
+                                      int64_t count, float *out);
 /* Device time (ms, rank 0's stream) of the last flm_store_unmask, from its seed upload to the end of
  * its copy of final_sum to the host: the part of the call's wall time the GPU accounts for. */
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms);

@@ -61,6 +61,12 @@ for _name, _res, _args in (
         ("flm_decode_unpack", _int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, ctypes.c_int64, _f32p]),
         ("flm_store_unmask_unpack_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, ctypes.c_int64,
                                                _f32p]),
+        ("flm_codec_check_noise", _int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64, ctypes.c_uint64]),
+        ("flm_client_encode_noise_mask", _int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _int, _u8p,
+                                                _int, _u8p, _u32p, _u32p]),
+        ("flm_decode_unpack_noise", _int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _f32p]),
+        ("flm_store_unmask_unpack_noise_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
+                                                     ctypes.c_int64, _f32p]),
         ("flm_hash_to_curve", _int, [_vp, _u8p, _u32p, _int, _u8p, _u32p]),
         ("flm_hash_to_curve_decimal", _int, [_vp, ctypes.c_uint32, _int, _u8p, _u32p])):
     _f = getattr(_lib, _name)
@@ -422,18 +428,63 @@ def client_encode_pack_mask(seeds, signs, L, x, frac_bits, clip, pack, dither=No
     return out, int(clipped[0])
 
 
-def decode_unpack(total, L, frac_bits, clip, pack, count=1):
+def decode_unpack(total, L, frac_bits, clip, pack, count=1, noise_bits=0):
     """final_sum of packed rows (SA_ServiceAgent.py:538-540, 605) as the L float32 means of `count`
-    contributors: (field - count ceil(clip 2^frac_bits)) / (count 2^frac_bits)."""
+    contributors: (field - count ceil(clip 2^frac_bits)) / (count 2^frac_bits).  noise_bits > 0: rows of
+    client_encode_noise_mask, whose bias is ceil(clip 2^frac_bits) + noise_bits / 2."""
     if pack not in (2, 4):
         raise RuntimeError("pack must be 2 or 4")
     total = np.ascontiguousarray(total, dtype=np.uint32)
     if total.shape != (-(-L // pack),):
         raise RuntimeError("vector length error")
     out = np.empty(L, np.float32)
+    if noise_bits != 0:
+        _check(_lib.flm_decode_unpack_noise(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip),
+                                            int(pack), int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
+        return out
     _check(_lib.flm_decode_unpack(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip), int(pack),
                                   int(count), out.ctypes.data_as(_f32p)))
     return out
+
+
+def codec_check_noise(frac_bits, clip, pack, noise_bits, n_clients, L=0):
+    """Raise unless n_clients float updates of magnitude <= clip, each with its share of binomial noise
+    (noise_bits fair coins per parameter: at most noise_bits / 2 either way), fit the ring at `pack` (1, 2 or 4)
+    parameters per word, in the worst case: n (ceil(clip 2^frac_bits) + noise_bits / 2) <= 2^31 - 1, packed twice
+    that <= 2^(32 / pack) - 1; with L > 0 also ceil(noise_bits / 32) ceil(L / 16) <= 2^32.  The server's check at
+    set-up, with the real n."""
+    _check(_lib.flm_codec_check_noise(int(frac_bits), float(clip), int(pack), int(noise_bits), int(n_clients), int(L)))
+
+
+def client_encode_noise_mask(seeds, signs, L, x, frac_bits, clip, pack=1, dither=None, noise_bits=0, noise=None):
+    """client_encode_mask (pack 1) or client_encode_pack_mask (2, 4) with the client's share of distributed-DP
+    noise drawn inside the masking kernel ("replace it with model weights", SA_ClientAgent.py:300-324; the local
+    noise of agent/examples/crypto/PPFL_ClientAgent.py:219-221, 274-285): every parameter's quantised value gets
+    (heads of noise_bits fair coins of PRG(noise)) - noise_bits / 2.  noise: 32 secret bytes, fresh per iteration.
+    Turning noise_bits into an (epsilon, delta) is the caller's business.  Returns (uint32 words, clipped elements)."""
+    seg = np.array([0, len(seeds)], np.int64)
+    sd, sg, K = _seed_arrays(seeds, signs)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.shape != (L,):
+        raise RuntimeError("vector length error")
+    if pack not in (1, 2, 4):
+        raise RuntimeError("pack must be 1, 2 or 4")
+    keep = []
+    ptrs = []
+    for name, v in (("dither", dither), ("noise", noise)):
+        if v is None:
+            ptrs.append(None)
+            continue
+        if len(v) != 32:
+            raise RuntimeError("the %s seed must be 32 bytes" % name)
+        keep.append(np.frombuffer(bytes(v), np.uint8).copy())
+        ptrs.append(keep[-1].ctypes.data_as(_u8p))
+    out, clipped = np.empty(-(-L // pack), np.uint32), np.zeros(1, np.uint32)
+    _check(_lib.flm_client_encode_noise_mask(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p),
+                                             sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), L, int(frac_bits),
+                                             float(clip), int(pack), ptrs[0], int(noise_bits), ptrs[1],
+                                             out.ctypes.data_as(_u32p), clipped.ctypes.data_as(_u32p)))
+    return out, int(clipped[0])
 
 
 class VectorStore:
@@ -496,12 +547,17 @@ class VectorStore:
                                               int(frac_bits), int(count), out.ctypes.data_as(_f32p)))
         return out
 
-    def unmask_unpack_f32(self, seeds, signs, L_params, frac_bits, clip, pack, count=1):
+    def unmask_unpack_f32(self, seeds, signs, L_params, frac_bits, clip, pack, count=1, noise_bits=0):
         """unmask() of a store of packed rows (L = ceil(L_params / pack)), decoded on the GPU(s) before the copy
         to the host: the L_params float32 means of `count` contributors (:538-540, :605, and the codec of
-        client_encode_pack_mask)."""
+        client_encode_pack_mask; noise_bits > 0: of client_encode_noise_mask)."""
         sd, sg, K = _seed_arrays(seeds, signs)
         out = np.empty(int(L_params), np.float32)
+        if noise_bits != 0:
+            self._check(_lib.flm_store_unmask_unpack_noise_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
+                                                               int(L_params), int(frac_bits), float(clip), int(pack),
+                                                               int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
+            return out
         self._check(_lib.flm_store_unmask_unpack_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
                                                      int(L_params), int(frac_bits), float(clip), int(pack), int(count),
                                                      out.ctypes.data_as(_f32p)))

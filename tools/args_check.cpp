@@ -135,6 +135,8 @@ static void check_round_lists() {
                         through_bounce(client_encode_pack_mask_args(N, K, L, packed_words(L, pack), opt & 1, opt & 2));
                         if (!opt) through_bounce(decode_unpack_args(L, packed_words(L, pack)));
                     }
+                    for (int pack : {1, 2, 4})
+                        through_bounce(client_encode_noise_mask_args(N, K, L, packed_words(L, pack), opt & 1, opt & 2));
                     if (opt < 2) through_bounce(client_mask_args(N, K, L, opt & 1));
                     if (opt < 2) through_bounce(aggregate_unmask_args(K, L, opt & 1));
                     if (opt) continue;
@@ -214,6 +216,22 @@ static void check_round_rules() {
     const ArgList pe = client_encode_pack_mask_args(3, 7, 5, 2, false, true), pd = decode_unpack_args(5, 2);
     CHECK(pe.n == 5 && pe.a[0].width == 20 && pe.a[3].width == 8 && pe.a[3].is_out && pe.a[3].in_place && !pe.a[2].present);
     CHECK(pd.n == 2 && pd.a[0].width == 8 && pd.a[1].width == 20 && pd.a[1].is_out);
+    // the noised codec: pack and noise_bits, then the rule of that pack, then the worst case with B_n = B + b / 2
+    uint32_t Bn = 0;
+    for (int b : {-2, 1, 31, 1026}) CHECK(noise_codec_error(4, 1.0f, 2, b, 1, 0, &range, &B, &Bn) && !range);
+    for (int pack : {0, 3, 8}) CHECK(noise_codec_error(4, 1.0f, pack, 2, 1, 0, &range, &B, &Bn) && !range);
+    CHECK(!noise_codec_error(4, 1.0f, 2, 30, 1057, 0, &range, &B, &Bn) && B == 16 && Bn == 31);
+    CHECK(noise_codec_error(4, 1.0f, 2, 30, 1058, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_codec_error(2, 1.0f, 4, 2, 25, 0, &range, &B, &Bn) && Bn == 5 && noise_codec_error(2, 1.0f, 4, 2, 26, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_codec_error(7, 1.0f, 2, 0, 255, 0, &range, &B, &Bn) && noise_codec_error(7, 1.0f, 2, 2, 255, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_codec_error(16, 4.0f, 1, 1024, 8176, 0, &range, &B, &Bn) && Bn == 262656);  // 8176 * 262656 <= 2^31 - 1
+    CHECK(noise_codec_error(16, 4.0f, 1, 1024, 8177, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_codec_error(16, 4.0f, 1, 0, 8177, 0, &range, &B, &Bn));                     // without noise: 8191 fit
+    CHECK(!noise_codec_error(4, 1.0f, 1, 64, 1, 1ull << 35, &range, &B, &Bn));              // 2 * 2^31 blocks
+    CHECK(noise_codec_error(4, 1.0f, 1, 64, 1, (1ull << 35) + 1, &range, &B, &Bn) && range);
+    CHECK(!noise_codec_error(4, 1.0f, 1, 0, 1, ~0ull, &range, &B, &Bn));                    // no noise: no length rule
+    const ArgList ne = client_encode_noise_mask_args(3, 7, 5, 2, false, true);
+    CHECK(ne.n == 6 && ne.a[3].present && ne.a[3].width == 96 && !ne.a[2].present && ne.a[4].is_out && ne.a[4].width == 8);
     CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
     CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));
     CHECK(!slot_range_error(0, 1ull << 36) && slot_range_error(16, 1ull << 36) && slot_range_error(1ull << 36, 1) &&
