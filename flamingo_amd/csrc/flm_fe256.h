@@ -294,7 +294,17 @@ struct FeField {
 // Pornin, "Optimized Binary GCD for Modular Inversion" (eprint 2020/972), Algorithm 2, with
 // k - 1 = 30 inner steps per outer step so the update factors fit int32: 18 outer steps, i.e.
 // 540 >= 2 * 256 - 1 inner steps, the algorithm's bound (tools/bingcd_model.py runs exactly this
-// schedule in Python: it matches Fermat on 20k random and edge inputs, the worst needing all 18).
+// schedule in Python and traces it).  Random inputs reach a = 0 after 12 to 14 outer steps; all 18
+// are needed by 2^255 and a handful of c << k, k in 243..255 (mod p: 13 << 252, 71 << 249,
+// 923 << 246, ...; mod n: 21 << 251, 31 << 251, 57 << 250, ...).  The result v is final once
+// b == 1, at least one inner step earlier: every known input has it after 17 outer steps, so the
+// 18th is margin (the known inputs tell 16 steps from 18, none tells 17).  The two negation
+// branches below fire when the approximations order a and b wrongly (tied 34-bit top windows): the
+// family m - c 2^j + off reaches them on purpose, mod n at outer step 1, mod p also at steps 3 to 9;
+// mod p about 1 random input in 20,000 takes one as well.  A structured search (c << k,
+// m - (c << k), m - c 2^j + off and their inverses, ~24k inputs per modulus) found no input that
+// needs a 19th step: a search, not a proof.  tests/inv_cases.py lists these inputs;
+// tests/test_inv_edges_gpu.py runs them through this code.
 // An outer step runs 30 binary-GCD steps on 64-bit approximations of a and b (the low 30 bits
 // exact, above them the top 34 bits of the longer one's window), then applies the 2 x 2 update
 // matrix to the 256-bit a, b and to the Bezout coefficients u, v mod p (with a Montgomery
