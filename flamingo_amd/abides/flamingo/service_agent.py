@@ -84,13 +84,12 @@ class SA_ServiceAgent(Agent):
             # n updates of magnitude up to clip must fit the 32-bit ring: refuse the run, never wrap (FLM_ERANGE)
             # (packed: no field of the sum may carry into its neighbour, n 2 ceil(clip 2^f) <= 2^(32/pack) - 1)
             n = max(1, len(users) or num_clients)
-            if param.codec_noise_bits():   # ... and every client's noise share, in the worst case
-                param.engine().codec_check(param.codec()[0], param.codec()[1], n, pack=param.codec_pack(),
-                                           noise_bits=param.codec_noise_bits(), L=param.vector_len)
-            elif param.codec_pack() == 1:
-                param.engine().codec_check(param.codec()[0], param.codec()[1], n)
-            else:
-                param.engine().codec_check(param.codec()[0], param.codec()[1], n, pack=param.codec_pack())
+            # ... and every client's noise share, in the worst case.  One rule on the C side; pack and noise_bits
+            # are named only when on, so an engine that offers the plain codec alone still serves a plain run
+            kw = {"pack": param.codec_pack()} if param.codec_pack() != 1 else {}
+            if param.codec_noise_bits():
+                kw.update(noise_bits=param.codec_noise_bits(), L=param.vector_len)
+            param.engine().codec_check(param.codec()[0], param.codec()[1], n, **kw)
         self.online_counts = {}      # iteration -> |U|
         self.pairs_per_iteration = {}  # iteration -> D dropout pairs recovered
         self.aggProcessingMap = {0: self.initialize, 1: self.report, 2: self.forward_signatures,
@@ -336,18 +335,13 @@ class SA_ServiceAgent(Agent):
         # K masks over its own slot shard of the device-resident S, then the one copy to the host
         t0 = pd.Timestamp("now")
         st = self.store()
-        codec, pack = param.codec(), param.codec_pack()
+        codec = param.codec()
         count = max(1, len(self.user_vectors))
         self.final_mean = None
         if getattr(st, "has_partial", True):
             self.final_sum = st.unmask(seeds, signs)
-            if codec is not None and pack == 1:   # float inputs: the same sum, decoded on the GPU(s) as the mean over U
-                self.final_mean = st.unmask_f32(seeds, signs, codec[0], count)
-            elif codec is not None and param.codec_noise_bits():   # packed, noised: the bias carries noise_bits / 2
-                self.final_mean = st.unmask_unpack_f32(seeds, signs, self.vector_len, codec[0], codec[1], pack, count,
-                                                       noise_bits=param.codec_noise_bits())
-            elif codec is not None:               # packed: every device unpacks its word shard into its floats
-                self.final_mean = st.unmask_unpack_f32(seeds, signs, self.vector_len, codec[0], codec[1], pack, count)
+            if codec is not None:   # float inputs: the same sum, decoded on the GPU(s) as the mean over U
+                self.final_mean = self._mean(count, st, "unmask_f32", "unmask_unpack_f32", seeds, signs)
         else:
             # no report this iteration: the reference-style assigned partial sum (vec_sum_partial
             # setter, :540/:605) is the S the masks are added to, on the GPU
@@ -360,13 +354,8 @@ class SA_ServiceAgent(Agent):
             rec["reconstruction_unmask_gpu"] = gpu
         self.agent_print(f"reconstruction unmask: {len(seeds)} masks over S on the GPU(s) + D2H, {ms:.3f} ms wall"
                          + (f", {gpu:.3f} ms GPU" if gpu is not None else ""))
-        if codec is not None and self.final_mean is None and pack == 1:
-            self.final_mean = param.engine().decode_sum(self.final_sum, codec[0], count)
-        elif codec is not None and self.final_mean is None and param.codec_noise_bits():
-            self.final_mean = param.engine().decode_unpack(self.final_sum, self.vector_len, codec[0], codec[1], pack, count,
-                                                           noise_bits=param.codec_noise_bits())
-        elif codec is not None and self.final_mean is None:
-            self.final_mean = param.engine().decode_unpack(self.final_sum, self.vector_len, codec[0], codec[1], pack, count)
+        if codec is not None and self.final_mean is None:
+            self.final_mean = self._mean(count, param.engine(), "decode_sum", "decode_unpack", self.final_sum)
         if codec is not None:
             self.means[self.current_iteration] = self.final_mean
             self.online_ids[self.current_iteration] = sorted(self.user_vectors)
@@ -376,6 +365,16 @@ class SA_ServiceAgent(Agent):
         self.agent_print("final sum:", self.final_sum)
 
     # ----------------------------------------------------------------- util
+    def _mean(self, count, on, unpacked, packed, *head):
+        """The final sum as the mean over `count` clients, by a method of `on` (the store, or the engine for a sum on
+        the host): unpacked(*head, frac_bits, count) at pack 1 (in place), else packed(*head, L, frac_bits, clip, pack,
+        count), every device unpacking its word shard into its floats; with noise the bias carries noise_bits / 2."""
+        (frac_bits, clip), pack, noise_bits = param.codec()[:2], param.codec_pack(), param.codec_noise_bits()
+        if pack == 1:
+            return getattr(on, unpacked)(*head, frac_bits, count)
+        kw = {"noise_bits": noise_bits} if noise_bits else {}
+        return getattr(on, packed)(*head, self.vector_len, frac_bits, clip, pack, count, **kw)
+
     def recordTime(self, startTime, categoryName):
         self.elapsed_time[categoryName] += pd.Timestamp("now") - startTime
 

@@ -73,65 +73,43 @@ inline const char *frac_bits_error(int frac_bits) {
     return frac_bits < 0 || frac_bits > 30 ? "frac_bits outside 0..30" : nullptr;
 }
 
-// The codec's parameter and headroom rule: n ceil(clip 2^f) <= 2^31 - 1.  clip 2^f is exact in double (a float
-// times a power of two), so is its ceiling, and the product is compared in integers.  *headroom: the
-// parameters are fine and the sum is what can wrap (FLM_ERANGE).
-inline const char *codec_error(int frac_bits, float clip, int64_t n, bool *headroom) {
-    *headroom = false;
+// The codec's one rule.  pack = 1, 2 or 4 fields of W = 32 / pack bits per ring word (unpacked_ok: whether the
+// entry point admits pack = 1), each client adding binomial noise Z in [-b/2, b/2], b = noise_bits even in 0..1024
+// (0: off).  B = ceil(clip 2^f): clip 2^f is exact in double (a float times a power of two), so is its ceiling,
+// and every product is compared in integers.  Headroom for n contributors (FLM_ERANGE, *range set):
+//   n B <= 2^31 - 1, whatever the pack;
+//   packed, fields hold q + B in [0, 2B]: n 2B <= 2^W - 1, so that no field of the sum carries into its neighbour;
+//   with noise, B_n = B + b/2 in B's place in the rule of that pack;
+//   with noise and a row of L_params > 0 parameters: ceil(b / 32) ceil(L_params / 16) <= 2^32 blocks of the noise
+//   stream, whose block counter has no high word.
+// *bias: B, the codec's own; *bias_n: B_n (either may be NULL).
+inline const char *codec_error(int frac_bits, float clip, int pack, bool unpacked_ok, int noise_bits, int64_t n,
+                               uint64_t L_params, bool *range, uint32_t *bias = nullptr, uint32_t *bias_n = nullptr) {
+    *range = false;
+    if (pack != 2 && pack != 4 && !(unpacked_ok && pack == 1)) return unpacked_ok ? "pack must be 1, 2 or 4" : "pack must be 2 or 4";
+    if (noise_bits < 0 || noise_bits > 1024 || noise_bits % 2) return "noise_bits must be even and in 0..1024";
     if (const char *why = frac_bits_error(frac_bits)) return why;
     if (!(clip > 0.0f) || !std::isfinite(clip)) return "clip must be finite and positive";
     if (n < 1) return "a count of contributors must be at least 1";
-    const double m = std::ceil((double)clip * std::ldexp(1.0, frac_bits));
-    *headroom = m > 2147483647.0 || (uint64_t)n > 2147483647ull / (uint64_t)m;
-    return *headroom ? "that many contributors of magnitude up to ceil(clip 2^frac_bits) can wrap the 32-bit sum" : nullptr;
-}
-
-// The packed codec's rule: pack = 2 or 4 fields of W = 32 / pack bits per ring word (pack = 1 is the unpacked
-// calls' job), each holding q + B in [0, 2B], B = ceil(clip 2^f) as above.  Headroom for n contributors:
-// n 2B <= 2^W - 1, in integers, so that no field of the sum carries into its neighbour (FLM_ERANGE).
-// *bias: B, when the rule passes.
-inline const char *packed_codec_error(int frac_bits, float clip, int pack, int64_t n, bool *headroom, uint32_t *bias) {
-    *headroom = false;
-    if (pack != 2 && pack != 4) return "pack must be 2 or 4";
-    if (const char *why = codec_error(frac_bits, clip, n, headroom)) return why;
-    const uint64_t B = (uint64_t)std::ceil((double)clip * std::ldexp(1.0, frac_bits));  // >= 1: clip > 0
-    const uint64_t field_max = (uint64_t(1) << (32 / pack)) - 1;
-    *headroom = 2 * B > field_max || (uint64_t)n > field_max / (2 * B);
-    if (bias) *bias = (uint32_t)B;
-    return *headroom ? "that many contributors of fields up to 2 ceil(clip 2^frac_bits) can carry out of a packed field"
-                     : nullptr;
-}
-
-// The codec with distributed-DP binomial noise: every client adds Z in [-b/2, b/2], b = noise_bits even in
-// 0..1024 (0: off, the rules above alone), pack = 1, 2 or 4.  First the refusals of the rule above for that pack,
-// then the worst case in integers with B_n = B + b/2: unpacked n B_n <= 2^31 - 1, packed n 2 B_n <= 2^W - 1
-// (FLM_ERANGE), and for a row of L_params > 0 parameters ceil(b / 32) ceil(L_params / 16) <= 2^32 blocks of the
-// noise stream, whose block counter has no high word (FLM_ERANGE).  *bias: B, the codec's own; *bias_n: B_n.
-inline const char *noise_codec_error(int frac_bits, float clip, int pack, int noise_bits, int64_t n, uint64_t L_params,
-                                     bool *range, uint32_t *bias, uint32_t *bias_n) {
-    *range = false;
-    if (pack != 1 && pack != 2 && pack != 4) return "pack must be 1, 2 or 4";
-    if (noise_bits < 0 || noise_bits > 1024 || noise_bits % 2) return "noise_bits must be even and in 0..1024";
-    uint32_t B32 = 0;
-    if (const char *why = pack == 1 ? codec_error(frac_bits, clip, n, range)
-                                    : packed_codec_error(frac_bits, clip, pack, n, range, &B32))
-        return why;
-    const uint64_t B = (uint64_t)std::ceil((double)clip * std::ldexp(1.0, frac_bits));  // <= 2^31 - 1: the rule passed
-    const uint64_t Bn = B + (uint64_t)noise_bits / 2;
+    *range = true;  // from here on the parameters are fine and the sum is what can wrap
+    const double m = std::ceil((double)clip * std::ldexp(1.0, frac_bits));  // >= 1: clip > 0
+    if (m > 2147483647.0 || (uint64_t)n > 2147483647ull / (uint64_t)m)
+        return "that many contributors of magnitude up to ceil(clip 2^frac_bits) can wrap the 32-bit sum";
+    const uint64_t B = (uint64_t)m, Bn = B + (uint64_t)noise_bits / 2;
+    const uint64_t top = pack == 1 ? 2147483647ull : (uint64_t(1) << (32 / pack)) - 1;
+    if (pack > 1 && (2 * B > top || (uint64_t)n > top / (2 * B)))
+        return "that many contributors of fields up to 2 ceil(clip 2^frac_bits) can carry out of a packed field";
     if (bias) *bias = (uint32_t)B;
     if (bias_n) *bias_n = (uint32_t)Bn;
-    if (noise_bits == 0) return nullptr;
-    const uint64_t top = pack == 1 ? 2147483647ull : (uint64_t(1) << (32 / pack)) - 1;
-    const uint64_t each = pack == 1 ? Bn : 2 * Bn;
-    if (each > top || (uint64_t)n > top / each) {
-        *range = true;
-        return "that many contributors of magnitude up to ceil(clip 2^frac_bits) + noise_bits / 2 have no headroom";
+    if (noise_bits != 0) {
+        const uint64_t each = pack == 1 ? Bn : 2 * Bn;
+        if (each > top || (uint64_t)n > top / each)
+            return "that many contributors of magnitude up to ceil(clip 2^frac_bits) + noise_bits / 2 have no headroom";
+        const uint64_t draws = ((uint64_t)noise_bits + 31) / 32, blocks = L_params / 16 + (L_params % 16 ? 1 : 0);
+        if (blocks > (uint64_t(1) << 32) / draws)  // draws blocks <= 2^32, without overflow
+            return "the noise stream of a row that long ends beyond 2^32 blocks (its block counter has no high word)";
     }
-    const uint64_t draws = ((uint64_t)noise_bits + 31) / 32, blocks = L_params / 16 + (L_params % 16 ? 1 : 0);
-    if (blocks > (uint64_t(1) << 32) / draws) {  // draws blocks <= 2^32, without overflow
-        *range = true;
-        return "the noise stream of a row that long ends beyond 2^32 blocks (its block counter has no high word)";
-    }
+    *range = false;
     return nullptr;
 }
 
@@ -358,29 +336,15 @@ inline ArgList client_mask_args(size_t N, size_t K, size_t L, bool x) {
     return {{in_place(pitched(arg_in(L * 4, rows, x), N, host_row_pitch(L))), arg_in(K * 32, seeds), arg_in(K, signs),
              in_place(pitched(arg_out(L * 4, out), N, host_row_pitch(L)))}, 4};
 }
-// x, seeds, dither, out, clipped (the signs stay on the host); x and out in place as flm_client_mask's
-inline ArgList client_encode_mask_args(size_t N, size_t K, size_t L, bool dither, bool clipped) {
+// flm_client_encode_mask, _pack_mask, _noise_mask: x (L floats a row), seeds, dither, noise, out (Lw =
+// packed_words(L, pack) words a row), clipped; the signs stay on the host.  x and out in place as flm_client_mask's,
+// each at a pitch of its own; the clients' N x 32 noise seeds, when they travel, in ec_scal.
+inline ArgList client_encode_mask_args(size_t N, size_t K, size_t L, size_t Lw, bool dither, bool noise, bool clipped) {
     return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
-             arg_in(N * 32, bytes_in, dither), in_place(pitched(arg_out(L * 4, out), N, host_row_pitch(L))),
-             arg_out(N * 4, bytes_out, clipped)}, 5};
-}
-// sum, out
-inline ArgList decode_sum_args(size_t L) { return {{in_place(arg_in(L * 4, rows)), in_place(arg_out(L * 4, out))}, 2}; }
-// x (L floats a row), seeds, dither, out (Lw = packed_words(L, pack) words a row), clipped; x and out in place as
-// above, each at a pitch of its own
-inline ArgList client_encode_pack_mask_args(size_t N, size_t K, size_t L, size_t Lw, bool dither, bool clipped) {
-    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
-             arg_in(N * 32, bytes_in, dither), in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))),
-             arg_out(N * 4, bytes_out, clipped)}, 5};
-}
-// x, seeds, dither, noise, out, clipped: the packed call's list with the clients' N x 32 noise seeds, which
-// travel in ec_scal (pack = 1: Lw = L)
-inline ArgList client_encode_noise_mask_args(size_t N, size_t K, size_t L, size_t Lw, bool dither, bool clipped) {
-    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
-             arg_in(N * 32, bytes_in, dither), arg_in(N * 32, ec_scal),
+             arg_in(N * 32, bytes_in, dither), arg_in(N * 32, ec_scal, noise),
              in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))), arg_out(N * 4, bytes_out, clipped)}, 6};
 }
-// sum (Lw words), out (L floats)
+// sum (Lw words), out (L floats); Lw = L: the unpacked decode, which may then run in place
 inline ArgList decode_unpack_args(size_t L, size_t Lw) {
     return {{in_place(arg_in(Lw * 4, rows)), in_place(arg_out(L * 4, out))}, 2};
 }

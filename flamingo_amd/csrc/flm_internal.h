@@ -41,28 +41,27 @@ hipError_t launch_small_round(int B, const uint32_t *d_rows, uint64_t pitch, int
 hipError_t launch_small_client_mask(const uint32_t *d_x, uint64_t pitch, int N, const int64_t *d_seg,
                                    const uint8_t *d_seeds, const int8_t *d_signs, uint64_t L, uint32_t bias,
                                    uint32_t *d_out, hipStream_t stream);
-// Fixed-point codec (encode_mask_kernel, decode_sum_kernel).  d_out[i][l] = encode(d_x[i][l]) + client i's masks, one
-// workgroup per (client, 1024-slot tile) of a one-dimensional grid (encode_mask_groups of them, at most 2^31 - 1);
-// d_dither N x 32 selects stochastic rounding, NULL nearest-even; d_clipped N words, zeroed by the caller, or NULL.
+// Fixed-point codec (encode_mask_kernel, decode_sum_kernel, decode_unpack_kernel).  The codec's parameters as the
+// rule of flm_call_args.h passed them: pack = 1, 2 or 4 parameters per ring word, noise_bits even in 0..1024 (0:
+// no binomial noise), bias = ceil(clip 2^frac_bits), the codec's own (ignored at pack = 1).
+struct CodecParams {
+    int frac_bits;
+    float clip;
+    int pack, noise_bits;
+    uint32_t bias;
+};
+// d_out[i][l'] = word l' of the encoded, packed and noised d_x[i] + client i's masks: L counts parameters, d_out rows
+// hold ceil(L / pack) words, one workgroup per (client, 1024-word tile) of a one-dimensional grid
+// (encode_mask_groups(N, ceil(L / pack)) of them, at most 2^31 - 1).  d_x rows are read 16 bytes at a time up to
+// round_up(L, 4) floats; d_dither N x 32 selects stochastic rounding, NULL nearest-even; d_noise N x 32 bytes, read
+// when noise_bits > 0; d_clipped N words, zeroed by the caller, or NULL.
 uint64_t encode_mask_groups(int N, uint64_t L);
 hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
-                              const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
-                              uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream);
+                              const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, uint64_t L,
+                              const CodecParams &c, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
+                              hipStream_t stream);
 // d_out[l] = float32(float64(int32(d_sum[l])) / denom), l < n; d_out may be d_sum; both 16-byte aligned
 hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, float *d_out, hipStream_t stream);
-// Packed codec (encode_pack_mask_kernel, decode_unpack_kernel): pack = 2 or 4 parameters per ring word, biased by
-// bias = ceil(clip 2^frac_bits).  L counts parameters; d_out rows hold ceil(L / pack) words; the grid is
-// encode_mask_groups(N, ceil(L / pack)).  d_x rows are read 16 bytes at a time up to round_up(L, 4) floats.
-hipError_t launch_encode_pack_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
-                                   const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
-                                   int pack, uint32_t bias, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
-                                   hipStream_t stream);
-// The same with the client's binomial noise share (encode_noise_mask_kernel): pack = 1, 2 or 4; noise_bits even in
-// 2..1024; d_noise N x 32 bytes; bias = ceil(clip 2^frac_bits), the codec's own (ignored at pack = 1).
-hipError_t launch_encode_noise_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
-                                    const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, int noise_bits,
-                                    uint64_t L, int frac_bits, float clip, int pack, uint32_t bias, uint32_t *d_out,
-                                    uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream);
 // d_out[pack l' + j] = float32(float64(field j of d_sum[l'] - count_bias) / denom) for the L parameters; d_out is
 // not d_sum; both 16-byte aligned
 hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int64_t count_bias, double denom, float *d_out,

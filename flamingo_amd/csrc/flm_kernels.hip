@@ -940,83 +940,6 @@ __device__ __forceinline__ uint32_t codec_encode(float x, float clip, float scal
     }
 }
 
-// out[i][l] = encode(x[i][l]) + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l]   (SA_ClientAgent.py:300-324)
-// Workgroup g = (client i, 1024-slot tile) = (g / tiles, g % tiles) of a one-dimensional grid; four waves.
-// Every wave's lane t owns ChaCha block t of the tile (slots 16t..16t+15).  Client i's seeds go round the four
-// waves; the last wave, which gets the fewest, also loads the lane's 16 floats (four 16-byte loads, the same block
-// layout), makes the dither block in stochastic mode, and adds the encoded words to its mask accumulator: they
-// exist only in registers.  The four accumulators meet in LDS and the tile is stored once, 16 bytes per thread.
-// Slots past L read as 0.0 (a predicate per element: the padding of a row may hold anything), encode to 0 and
-// are never counted as clipped or stored.  clipped[i] (zeroed by the call) gets one atomic add per workgroup.
-template <bool STOCHASTIC>
-__global__ __launch_bounds__(256) void encode_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
-                                                          const int64_t *__restrict__ seg,
-                                                          const uint8_t *__restrict__ seeds,
-                                                          const int8_t *__restrict__ signs,
-                                                          const uint8_t *__restrict__ dither, uint64_t L, uint32_t tiles,
-                                                          float clip, float scale, uint32_t *__restrict__ out,
-                                                          uint64_t out_pitch, uint32_t *__restrict__ clipped) {
-    __shared__ u32x4 lds[4 * 256];  // 16 KiB: one 4 KiB region per wave
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
-    const uint64_t slot0 = (uint64_t)tile * 1024u + 16u * (uint64_t)lane;
-    const uint32_t ctr = tile * 64u + (uint32_t)lane;
-    const int64_t k_lo = seg[i], k_hi = seg[i + 1];
-
-    uint32_t m[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m[j] = 0u;
-    uint32_t nneg = 0;
-    // seed u of the client runs on the wave of rank (u + 1) % 4; rank 0 (wave 3) has the encoding as its unit 0
-    const int rank = 3 - w;
-    for (int64_t k = k_lo + ((rank + 3) & 3); k < k_hi; k += 4) {
-        const bool neg = signs[k] < 0;
-        nneg += neg ? 1u : 0u;
-        chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
-    }
-    if (rank == 0) {
-        uint32_t r[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) r[j] = 0u;
-        if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, ctr, kAbcd, r);
-        const float *xr = x + (uint64_t)i * x_pitch;
-        uint32_t nclip = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t s = slot0 + 4u * j;
-            // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
-            const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
-            m[4 * j + 0] += codec_encode<STOCHASTIC>(s + 0 < L ? v.x : 0.0f, clip, scale, r[4 * j + 0], nclip);
-            m[4 * j + 1] += codec_encode<STOCHASTIC>(s + 1 < L ? v.y : 0.0f, clip, scale, r[4 * j + 1], nclip);
-            m[4 * j + 2] += codec_encode<STOCHASTIC>(s + 2 < L ? v.z : 0.0f, clip, scale, r[4 * j + 2], nclip);
-            m[4 * j + 3] += codec_encode<STOCHASTIC>(s + 3 < L ? v.w : 0.0f, clip, scale, r[4 * j + 3], nclip);
-        }
-        if (clipped) {  // only this wave counts: its total is the workgroup's
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
-            if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
-        }
-    }
-
-    u32x4 *R = lds + w * 256 + 4 * lane;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        R[j] = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
-    __syncthreads();
-    const int p = threadIdx.x;  // quad p of the tile: 1 KiB contiguous per wave store
-    const u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p];
-    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
-    uint32_t *dst = out + (uint64_t)i * out_pitch + slot;
-    if (slot + 3 < L) {
-        *reinterpret_cast<u32x4 *>(dst) = acc;
-    } else {
-        if (slot + 0 < L) dst[0] = acc.x;
-        if (slot + 1 < L) dst[1] = acc.y;
-        if (slot + 2 < L) dst[2] = acc.z;
-    }
-}
-
 // out[l] = float32(float64(int32(sum[l])) / denom), denom = count 2^f (SA_ServiceAgent.py:538-540, 605: the
 // final sum, as a mean).  16-byte loads and stores; a thread reads its quad before it writes it, so out may be
 // sum.  HBM-bound: the double division hides under the stream.
@@ -1048,108 +971,6 @@ __device__ __forceinline__ uint32_t codec_field(bool have, float v, float clip, 
                                                 uint32_t &nclip) {
     const uint32_t q = codec_encode<STOCHASTIC>(have ? v : 0.0f, clip, scale, r, nclip);
     return have ? q + bias : 0u;
-}
-
-// out[i][l'] = pack(encode(x[i][P l' .. P l' + P - 1])) + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l']
-// encode_mask_kernel over Lw = ceil(L / P) ring words: the same grid of (client, 1024-word tile) workgroups, lane t
-// of every wave owns ChaCha block t of the tile, the four accumulators meet in LDS and the tile is stored once.
-// The encoding wave (rank 0) reads the lane's 16 P consecutive floats, one dither block's worth (16 parameters,
-// 16 / P words) at a time: in stochastic mode block P (64 tile + t) + d of the client's dither stream, which is
-// indexed by parameter.  So that wave carries E = P blocks of its own in stochastic mode (about one in nearest
-// mode: the encoding is a fraction of a block), and the seeds are dealt to even that out: the first 3 E go round
-// ranks 1..3, the rest round all four from rank 0.  E = 1 is encode_mask_kernel's order.
-template <int P, bool STOCHASTIC>
-__global__ __launch_bounds__(256) void encode_pack_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
-                                                               const int64_t *__restrict__ seg,
-                                                               const uint8_t *__restrict__ seeds,
-                                                               const int8_t *__restrict__ signs,
-                                                               const uint8_t *__restrict__ dither, uint64_t L,
-                                                               uint64_t Lw, uint32_t tiles, float clip, float scale,
-                                                               uint32_t bias, uint32_t *__restrict__ out,
-                                                               uint64_t out_pitch, uint32_t *__restrict__ clipped) {
-    static_assert(P == 2 || P == 4, "two or four fields per word");
-    constexpr int W = 32 / P;
-    constexpr int E = STOCHASTIC ? P : 1;
-    __shared__ u32x4 lds[5 * 256];  // 20 KiB: one 4 KiB region per wave, and one for the packed words
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
-    const uint32_t ctr = tile * 64u + (uint32_t)lane;
-    const int64_t k_lo = seg[i], n_k = seg[i + 1] - k_lo;
-
-    uint32_t m[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m[j] = 0u;
-    uint32_t nneg = 0;
-    const int rank = 3 - w;
-    for (int64_t u = rank ? rank - 1 : 3 * E; u < n_k; u += (u + 3 < 3 * E ? 3 : 4)) {
-        const int64_t k = k_lo + u;
-        const bool neg = signs[k] < 0;
-        nneg += neg ? 1u : 0u;
-        chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
-    }
-    if (rank == 0) {
-        const float *xr = x + (uint64_t)i * x_pitch;
-        const uint64_t par0 = (uint64_t)P * ((uint64_t)tile * 1024u + 16u * (uint64_t)lane);  // the lane's first parameter
-        uint32_t nclip = 0;
-        // One dither block's parameters per pass, and the passes not unrolled: the block's 16 / P packed words go to
-        // the lane's place in a fifth LDS region (a quad or two), so no pass indexes the accumulator registers and
-        // the footprint stays that of one ChaCha block beside m.
-        u32x4 *E4 = lds + 4 * 256 + 4 * lane;
-#pragma unroll 1
-        for (int d = 0; d < P; ++d) {
-            uint32_t r[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) r[j] = 0u;
-            // parameters below 2^36 (the call's range rule): the dither block counter stays below 2^32
-            if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, (uint32_t)P * ctr + (uint32_t)d, kAbcd, r);
-            uint32_t e[16 / P];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint64_t s = par0 + 16u * (uint32_t)d + 4u * j;
-                // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
-                const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const uint32_t u0 = codec_field<STOCHASTIC>(s + 0 < L, v.x, clip, scale, r[4 * j + 0], bias, nclip);
-                const uint32_t u1 = codec_field<STOCHASTIC>(s + 1 < L, v.y, clip, scale, r[4 * j + 1], bias, nclip);
-                const uint32_t u2 = codec_field<STOCHASTIC>(s + 2 < L, v.z, clip, scale, r[4 * j + 2], bias, nclip);
-                const uint32_t u3 = codec_field<STOCHASTIC>(s + 3 < L, v.w, clip, scale, r[4 * j + 3], bias, nclip);
-                if constexpr (P == 4) {
-                    e[j] = u0 | (u1 << W) | (u2 << 2 * W) | (u3 << 3 * W);
-                } else {
-                    e[2 * j + 0] = u0 | (u1 << W);
-                    e[2 * j + 1] = u2 | (u3 << W);
-                }
-            }
-            if constexpr (P == 4) {
-                E4[d] = u32x4{e[0], e[1], e[2], e[3]};
-            } else {
-                E4[2 * d + 0] = u32x4{e[0], e[1], e[2], e[3]};
-                E4[2 * d + 1] = u32x4{e[4], e[5], e[6], e[7]};
-            }
-        }
-        if (clipped) {  // only this wave counts: its total is the workgroup's
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
-            if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
-        }
-    }
-
-    u32x4 *R = lds + w * 256 + 4 * lane;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        R[j] = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
-    __syncthreads();
-    const int p = threadIdx.x;  // quad p of the tile: 1 KiB contiguous per wave store
-    const u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p] + lds[1024 + p];
-    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
-    uint32_t *dst = out + (uint64_t)i * out_pitch + slot;
-    if (slot + 3 < Lw) {
-        *reinterpret_cast<u32x4 *>(dst) = acc;
-    } else {
-        if (slot + 0 < Lw) dst[0] = acc.x;
-        if (slot + 1 < Lw) dst[1] = acc.y;
-        if (slot + 2 < Lw) dst[2] = acc.z;
-    }
 }
 
 // ------------------------------------------------------------ distributed-DP noise inside the encode-mask kernels
@@ -1195,45 +1016,115 @@ __device__ __forceinline__ void noise_block_add(const uint8_t *__restrict__ key,
     }
 }
 
-// out[i][l'] = the noised word l' of x[i] + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l']
-// encode_mask_kernel (P = 1) and encode_pack_mask_kernel (P = 2, 4) with the client's noise share added in
-// registers: the same grid of (client, 1024-word tile) workgroups, lane t of every wave owns ChaCha block t of the
-// tile, the four partials meet in LDS and the tile is stored once.  A lane's 16 P parameters are P parameter
-// blocks of 16 and need `draws` noise blocks each: block draws (P (64 tile + t) + d) + dd of the noise stream is
-// draw dd of parameter block d.  A noise block only adds, so it is a unit like a seed, and any wave can run it:
-// the P draws noise units (unit u is draw u / P of parameter block u % P) and then the client's seeds form one
-// list that is dealt as encode_pack_mask_kernel deals its seeds round the encoding wave's E blocks: the first 3 E
-// go round ranks 1..3, the rest round all four from rank 0.  The loop over the list is rolled and its bound is
-// host-known; nothing loops on data.
-// Unpacked, everything adds into the accumulator registers and the encoding wave adds -b / 2 once per parameter
-// (`half`).  Packed, a wave's noise words and the encoding wave's packed words go to the wave's own LDS region
-// (zeroed first, indexed dynamically by the parameter block), the accumulator joins them at the end, and the
-// bias is B: the +b / 2 of the field bias B_n and the -b / 2 of Z cancel, so the popcounts add as they are.
-template <int P, bool STOCHASTIC>
-__global__ __launch_bounds__(256) void encode_noise_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
-                                                                const int64_t *__restrict__ seg,
-                                                                const uint8_t *__restrict__ seeds,
-                                                                const int8_t *__restrict__ signs,
-                                                                const uint8_t *__restrict__ dither,
-                                                                const uint8_t *__restrict__ noise, uint32_t draws,
-                                                                uint32_t last_mask, uint32_t half, uint64_t L,
-                                                                uint64_t Lw, uint32_t tiles, float clip, float scale,
-                                                                uint32_t bias, uint32_t *__restrict__ out,
-                                                                uint64_t out_pitch, uint32_t *__restrict__ clipped) {
+// ------------------------------------------------------------ the encode-mask kernel
+// The parts of encode_mask_kernel below that stand on their own.
+
+// The dealing of a client's unit list (unit = one ChaCha block per lane) over the four waves, rank = 3 - wave: the
+// encoding wave (rank 0) carries E blocks of its own, so the first 3 E units go round ranks 1..3 and the rest round
+// all four from rank 0.  E = 1: unit u runs on rank (u + 1) % 4, a step of 4 throughout.
+template <int E>
+__device__ __forceinline__ int64_t first_unit(int rank) { return rank ? rank - 1 : 3 * E; }
+template <int E>
+__device__ __forceinline__ int64_t next_unit(int64_t u) { return u + (u + 3 < 3 * E ? 3 : 4); }
+
+// Waves per SIMD pinned, floor and ceiling, to those of the kernel an instantiation replaced: the stochastic ones
+// without noise (7 at P = 1, 6 packed).  Left alone the allocator took 81 VGPRs at P = 4, one past the step to 6
+// waves, or at P = 1 aimed at 8 waves with 63 and ran slower.  0: left alone (1 to 8); those match unasked.
+template <int P, bool STOCHASTIC, bool NOISE>
+constexpr int kEncodeWaves = STOCHASTIC && !NOISE ? (P == 1 ? 7 : 6) : 0;
+
+// clipped[i] (zeroed by the call) gets one atomic add per workgroup: only the encoding wave counts, so its
+// total is the workgroup's
+__device__ __forceinline__ void clipped_add(uint32_t *clipped, uint32_t i, uint32_t nclip, int lane) {
+    if (!clipped) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
+    if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
+}
+
+// The four waves' partials meet in LDS and the tile is stored once: R, the lane's 16 words of its wave's region,
+// takes the accumulator (ADD: on top of the words already there), then thread p sums quad p of the REGIONS regions
+// (the waves' four, and a fifth where the packed words have one) and stores it, 16 bytes a thread (1 KiB
+// contiguous per wave), word by word across the row's end at Lw.
+template <bool ADD, int REGIONS>
+__device__ __forceinline__ void tile_meet_store(const u32x4 *lds, u32x4 *R, const uint32_t (&m)[16], uint32_t nneg,
+                                                uint32_t *row, uint32_t tile, uint64_t Lw) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const u32x4 a = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
+        if constexpr (ADD) R[j] += a;
+        else R[j] = a;
+    }
+    __syncthreads();
+    const int p = threadIdx.x;
+    u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p];
+    if constexpr (REGIONS == 5) acc += lds[1024 + p];
+    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
+    uint32_t *dst = row + slot;
+    if (slot + 3 < Lw) {
+        *reinterpret_cast<u32x4 *>(dst) = acc;
+    } else {
+        if (slot + 0 < Lw) dst[0] = acc.x;
+        if (slot + 1 < Lw) dst[1] = acc.y;
+        if (slot + 2 < Lw) dst[2] = acc.z;
+    }
+}
+
+// out[i][l'] = word l' of x[i] (encoded, packed P to a word, noised) + sum_{k in [seg[i], seg[i+1])} signs[k] PRG(seeds[k])[l']
+// (SA_ClientAgent.py:300-324), over Lw = ceil(L / P) ring words a row.
+// Workgroup g = (client i, 1024-word tile) = (g / tiles, g % tiles) of a one-dimensional grid; four waves.  Every
+// wave's lane t owns ChaCha block t of the tile (words 16t..16t+15) and keeps a 16-word accumulator in registers.
+// The units: a unit adds one ChaCha block per lane, and any wave can run it.  With NOISE the P draws noise units
+// come first (unit u is draw u / P of parameter block u % P: block draws (P (64 tile + t) + d) + dd of the noise
+// stream is draw dd of parameter block d of the lane's P), then the client's seeds; first_unit / next_unit deal the
+// list.  The loop over the two kinds of unit is rolled (the seeds-only loop is left to the compiler, as it was) and
+// its bound is host-known; nothing loops on data.
+// The encoding: rank 0 reads the lane's 16 P consecutive floats, one parameter block (one dither block's worth: in
+// stochastic mode block P (64 tile + t) + d of the client's dither stream, which is indexed by parameter) per pass,
+// the passes not unrolled, so that the footprint stays that of one ChaCha block beside the accumulator.  That is
+// E = P blocks of its own in stochastic mode and about one in nearest mode.  Parameters past L read as 0.0 (a
+// predicate per element: the padding of a row may hold anything), encode to a zero field and are never counted as
+// clipped or stored.  The pass is written in the kernel, not in a helper: behind a function boundary the same text
+// took 83 to 96 VGPRs at P = 4 stochastic, here 77 to 81 (profiles/codec_unify_resources.txt).
+// The meet: the four partials meet in LDS (one 4 KiB region per wave) and the tile is stored once.
+// P = 1: everything adds into the accumulator registers; bias is 0, and with NOISE the encoding wave adds -b / 2
+// once per parameter (`half`).  P > 1: packed words go to LDS, indexed dynamically by the parameter block, so that
+// no pass indexes the accumulator registers.  With NOISE every wave has some (its noise units'): they and the
+// encoding wave's add into the wave's own region, zeroed first, and the accumulator joins them at the meet; the
+// bias is B: the +b / 2 of the field bias B_n and the -b / 2 of Z cancel, so the popcounts add as they are.  Without
+// noise only the encoding wave has any and stores them to a fifth region (20 KiB), with no zeroing and no
+// read-modify-write: with the own region there too, the packed legs without noise measured up to 1.1 % slower
+// than the kernel they replace.
+// NOISE = false: the unit list is the seeds alone; noise, draws, last_mask and half are not read; at P = 1 the
+// encoding wave calls codec_encode itself.  No instantiation spills.
+template <int P, bool STOCHASTIC, bool NOISE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kEncodeWaves<P, STOCHASTIC, NOISE> ? kEncodeWaves<P, STOCHASTIC, NOISE> : 1,
+                                                                         kEncodeWaves<P, STOCHASTIC, NOISE> ? kEncodeWaves<P, STOCHASTIC, NOISE> : 8)))
+void encode_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
+                                                          const int64_t *__restrict__ seg,
+                                                          const uint8_t *__restrict__ seeds,
+                                                          const int8_t *__restrict__ signs,
+                                                          const uint8_t *__restrict__ dither,
+                                                          const uint8_t *__restrict__ noise, uint32_t draws,
+                                                          uint32_t last_mask, uint32_t half, uint64_t L, uint64_t Lw,
+                                                          uint32_t tiles, float clip, float scale, uint32_t bias,
+                                                          uint32_t *__restrict__ out, uint64_t out_pitch,
+                                                          uint32_t *__restrict__ clipped) {
     static_assert(P == 1 || P == 2 || P == 4, "one, two or four fields per word");
-    constexpr int W = 32 / P;
     constexpr int E = STOCHASTIC ? P : 1;
-    __shared__ u32x4 lds[4 * 256];  // 16 KiB: one 4 KiB region per wave
+    constexpr bool OWN = P > 1 && NOISE;    // packed words add into the wave's own region ...
+    constexpr bool FIFTH = P > 1 && !NOISE;  // ... or, only the encoding wave having any, are stored to a fifth
+    __shared__ u32x4 lds[(FIFTH ? 5 : 4) * 256];  // one 4 KiB region per wave (16 KiB), and the fifth
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
     const uint32_t ctr = tile * 64u + (uint32_t)lane;
     const uint64_t par0 = (uint64_t)P * ((uint64_t)tile * 1024u + 16u * (uint64_t)lane);  // the lane's first parameter
     const int64_t k_lo = seg[i];
-    const int64_t n_noise = (int64_t)P * (int64_t)draws, n_units = n_noise + (seg[i + 1] - k_lo);
+    const int64_t n_noise = NOISE ? (int64_t)P * (int64_t)draws : 0, n_units = n_noise + (seg[i + 1] - k_lo);
 
     u32x4 *R = lds + w * 256 + 4 * lane;  // the lane's 16 words of its wave's partial
-    if constexpr (P > 1) {
+    if constexpr (OWN) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) R[j] = u32x4{0u, 0u, 0u, 0u};
     }
@@ -1242,16 +1133,27 @@ __global__ __launch_bounds__(256) void encode_noise_mask_kernel(const float *__r
     for (int j = 0; j < 16; ++j) m[j] = 0u;
     uint32_t nneg = 0;
     const int rank = 3 - w;
+    // The seed's four lines stand in both loops: through a lambda or a helper the allocator gave the stochastic
+    // instantiations 16 VGPRs fewer and they ran 1.5 to 2.4 % slower.
+    if constexpr (NOISE) {  // two bodies in the loop: kept rolled
 #pragma unroll 1
-    for (int64_t u = rank ? rank - 1 : 3 * E; u < n_units; u += (u + 3 < 3 * E ? 3 : 4)) {
-        if (u < n_noise) {
-            const uint32_t d = (uint32_t)u % (uint32_t)P, dd = (uint32_t)u / (uint32_t)P;
-            // draws ceil(L / 16) <= 2^32 (the call's length rule): the counter of a parameter block the row has
-            // stays below 2^32; a block past L may wrap, and is predicated away or never stored
-            noise_block_add<P>(noise + 32 * (size_t)i, draws * ((uint32_t)P * ctr + d) + dd,
-                               dd + 1 == draws ? last_mask : 0xffffffffu, par0 + 16u * d, L, m, R + (4 / P) * d);
-        } else {
+        for (int64_t u = first_unit<E>(rank); u < n_units; u = next_unit<E>(u)) {
+            if (u < n_noise) {
+                const uint32_t d = (uint32_t)u % (uint32_t)P, dd = (uint32_t)u / (uint32_t)P;
+                // draws ceil(L / 16) <= 2^32 (the call's length rule): the counter of a parameter block the row has
+                // stays below 2^32; a block past L may wrap, and is predicated away or never stored
+                noise_block_add<P>(noise + 32 * (size_t)i, draws * ((uint32_t)P * ctr + d) + dd,
+                                   dd + 1 == draws ? last_mask : 0xffffffffu, par0 + 16u * d, L, m, R + (4 / P) * d);
+                continue;
+            }
             const int64_t k = k_lo + (u - n_noise);
+            const bool neg = signs[k] < 0;
+            nneg += neg ? 1u : 0u;
+            chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
+        }
+    } else {
+        for (int64_t u = first_unit<E>(rank); u < n_units; u = E == 1 ? u + 4 : next_unit<E>(u)) {  // E = 1: said outright
+            const int64_t k = k_lo + u;
             const bool neg = signs[k] < 0;
             nneg += neg ? 1u : 0u;
             chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
@@ -1260,12 +1162,13 @@ __global__ __launch_bounds__(256) void encode_noise_mask_kernel(const float *__r
     if (rank == 0) {
         const float *xr = x + (uint64_t)i * x_pitch;
         uint32_t nclip = 0;
-        // one dither block's parameters per pass, the passes not unrolled, as in encode_pack_mask_kernel
 #pragma unroll 1
         for (int d = 0; d < P; ++d) {
+            constexpr int W = 32 / P;
             uint32_t r[16];
 #pragma unroll
             for (int j = 0; j < 16; ++j) r[j] = 0u;
+            // parameters below 2^36 (the call's range rule): the dither block counter stays below 2^32
             if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, (uint32_t)P * ctr + (uint32_t)d, kAbcd, r);
             uint32_t e[16 / P];
 #pragma unroll
@@ -1273,6 +1176,13 @@ __global__ __launch_bounds__(256) void encode_noise_mask_kernel(const float *__r
                 const uint64_t s = par0 + 16u * (uint32_t)d + 4u * j;
                 // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
                 const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (P == 1 && !NOISE) {  // the words themselves: 0.0 past L encodes to 0, and is not stored
+                    m[4 * j + 0] += codec_encode<STOCHASTIC>(s + 0 < L ? v.x : 0.0f, clip, scale, r[4 * j + 0], nclip);
+                    m[4 * j + 1] += codec_encode<STOCHASTIC>(s + 1 < L ? v.y : 0.0f, clip, scale, r[4 * j + 1], nclip);
+                    m[4 * j + 2] += codec_encode<STOCHASTIC>(s + 2 < L ? v.z : 0.0f, clip, scale, r[4 * j + 2], nclip);
+                    m[4 * j + 3] += codec_encode<STOCHASTIC>(s + 3 < L ? v.w : 0.0f, clip, scale, r[4 * j + 3], nclip);
+                    continue;
+                }
                 const uint32_t u0 = codec_field<STOCHASTIC>(s + 0 < L, v.x, clip, scale, r[4 * j + 0], bias, nclip);
                 const uint32_t u1 = codec_field<STOCHASTIC>(s + 1 < L, v.y, clip, scale, r[4 * j + 1], bias, nclip);
                 const uint32_t u2 = codec_field<STOCHASTIC>(s + 2 < L, v.z, clip, scale, r[4 * j + 2], bias, nclip);
@@ -1289,38 +1199,18 @@ __global__ __launch_bounds__(256) void encode_noise_mask_kernel(const float *__r
                     e[2 * j + 1] = u2 | (u3 << W);
                 }
             }
-            if constexpr (P == 4) {
-                R[d] += u32x4{e[0], e[1], e[2], e[3]};
-            } else if constexpr (P == 2) {
-                R[2 * d + 0] += u32x4{e[0], e[1], e[2], e[3]};
-                R[2 * d + 1] += u32x4{e[4], e[5], e[6], e[7]};
+            if constexpr (OWN) {
+                R[(4 / P) * d] += u32x4{e[0], e[1], e[2], e[3]};
+                if constexpr (P == 2) R[2 * d + 1] += u32x4{e[4], e[5], e[6], e[7]};
+            } else if constexpr (FIFTH) {
+                u32x4 *E4 = lds + 4 * 256 + 4 * lane;
+                E4[(4 / P) * d] = u32x4{e[0], e[1], e[2], e[3]};
+                if constexpr (P == 2) E4[2 * d + 1] = u32x4{e[4], e[5], e[6], e[7]};
             }
         }
-        if (clipped) {  // only this wave counts: its total is the workgroup's
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) nclip += __shfl_xor(nclip, off);
-            if (lane == 0 && nclip) atomicAdd(clipped + i, nclip);
-        }
+        clipped_add(clipped, i, nclip, lane);
     }
-
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const u32x4 a = u32x4{m[4 * j] + nneg, m[4 * j + 1] + nneg, m[4 * j + 2] + nneg, m[4 * j + 3] + nneg};
-        if constexpr (P == 1) R[j] = a;
-        else R[j] += a;
-    }
-    __syncthreads();
-    const int p = threadIdx.x;  // quad p of the tile: 1 KiB contiguous per wave store
-    const u32x4 acc = lds[p] + lds[256 + p] + lds[512 + p] + lds[768 + p];
-    const uint64_t slot = (uint64_t)tile * 1024u + 4u * (uint64_t)p;
-    uint32_t *dst = out + (uint64_t)i * out_pitch + slot;
-    if (slot + 3 < Lw) {
-        *reinterpret_cast<u32x4 *>(dst) = acc;
-    } else {
-        if (slot + 0 < Lw) dst[0] = acc.x;
-        if (slot + 1 < Lw) dst[1] = acc.y;
-        if (slot + 2 < Lw) dst[2] = acc.z;
-    }
+    tile_meet_store<OWN, FIFTH ? 5 : 4>(lds, R, m, nneg, out + (uint64_t)i * out_pitch, tile, Lw);
 }
 
 // One field of a summed word as the mean of `count` contributors; cb = count B.
@@ -1374,94 +1264,27 @@ __global__ __launch_bounds__(256) void decode_unpack_kernel(const uint32_t *__re
 uint64_t encode_mask_groups(int N, uint64_t L) { return (uint64_t)N * ((L + 1023) / 1024); }
 
 hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
-                              const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
-                              uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream) {
-    const uint64_t groups = encode_mask_groups(N, L);
-    if (groups == 0) return hipSuccess;
-    if (groups > 0x7fffffffull || frac_bits < 0 || frac_bits > 30) return hipErrorInvalidValue;
-    const uint32_t tiles = (uint32_t)((L + 1023) / 1024);
-    const float scale = (float)(1u << frac_bits);
-    if (d_dither)
-        hipLaunchKernelGGL(encode_mask_kernel<true>, dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
-                           d_seeds, d_signs, d_dither, L, tiles, clip, scale, d_out, out_pitch, d_clipped);
-    else
-        hipLaunchKernelGGL(encode_mask_kernel<false>, dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
-                           d_seeds, d_signs, d_dither, L, tiles, clip, scale, d_out, out_pitch, d_clipped);
-    return hipGetLastError();
-}
-
-template <int P>
-static void launch_encode_pack(bool stochastic, unsigned groups, hipStream_t stream, const float *d_x, uint64_t x_pitch,
-                               const int64_t *d_seg, const uint8_t *d_seeds, const int8_t *d_signs, const uint8_t *d_dither,
-                               uint64_t L, uint64_t Lw, uint32_t tiles, float clip, float scale, uint32_t bias,
-                               uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped) {
-    if (stochastic)
-        hipLaunchKernelGGL((encode_pack_mask_kernel<P, true>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
-                           d_seeds, d_signs, d_dither, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
-    else
-        hipLaunchKernelGGL((encode_pack_mask_kernel<P, false>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
-                           d_seeds, d_signs, d_dither, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
-}
-
-hipError_t launch_encode_pack_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
-                                   const int8_t *d_signs, const uint8_t *d_dither, uint64_t L, int frac_bits, float clip,
-                                   int pack, uint32_t bias, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
-                                   hipStream_t stream) {
-    if (pack != 2 && pack != 4) return hipErrorInvalidValue;
-    const uint64_t Lw = (L + (uint64_t)pack - 1) / (uint64_t)pack;
+                              const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, uint64_t L,
+                              const CodecParams &c, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
+                              hipStream_t stream) {
+    if (c.pack != 1 && c.pack != 2 && c.pack != 4) return hipErrorInvalidValue;
+    if (c.noise_bits < 0 || c.noise_bits > 1024 || c.noise_bits % 2 || (c.noise_bits && !d_noise)) return hipErrorInvalidValue;
+    const uint64_t Lw = (L + (uint64_t)c.pack - 1) / (uint64_t)c.pack;
     const uint64_t groups = encode_mask_groups(N, Lw);
     if (groups == 0) return hipSuccess;
-    if (groups > 0x7fffffffull || frac_bits < 0 || frac_bits > 30) return hipErrorInvalidValue;
+    if (groups > 0x7fffffffull || c.frac_bits < 0 || c.frac_bits > 30) return hipErrorInvalidValue;
     const uint32_t tiles = (uint32_t)((Lw + 1023) / 1024);
-    const float scale = (float)(1u << frac_bits);
-    if (pack == 2)
-        launch_encode_pack<2>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
-                              L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
-    else
-        launch_encode_pack<4>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
-                              L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
-    return hipGetLastError();
-}
-
-template <int P>
-static void launch_encode_noise(bool stochastic, unsigned groups, hipStream_t stream, const float *d_x, uint64_t x_pitch,
-                                const int64_t *d_seg, const uint8_t *d_seeds, const int8_t *d_signs, const uint8_t *d_dither,
-                                const uint8_t *d_noise, uint32_t draws, uint32_t last_mask, uint32_t half, uint64_t L,
-                                uint64_t Lw, uint32_t tiles, float clip, float scale, uint32_t bias, uint32_t *d_out,
-                                uint64_t out_pitch, uint32_t *d_clipped) {
-    if (stochastic)
-        hipLaunchKernelGGL((encode_noise_mask_kernel<P, true>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
-                           d_seeds, d_signs, d_dither, d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias,
-                           d_out, out_pitch, d_clipped);
-    else
-        hipLaunchKernelGGL((encode_noise_mask_kernel<P, false>), dim3(groups), dim3(256), 0, stream, d_x, x_pitch, d_seg,
-                           d_seeds, d_signs, d_dither, d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias,
-                           d_out, out_pitch, d_clipped);
-}
-
-hipError_t launch_encode_noise_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
-                                    const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, int noise_bits,
-                                    uint64_t L, int frac_bits, float clip, int pack, uint32_t bias, uint32_t *d_out,
-                                    uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream) {
-    if (pack != 1 && pack != 2 && pack != 4) return hipErrorInvalidValue;
-    if (!d_noise || noise_bits < 2 || noise_bits > 1024 || noise_bits % 2) return hipErrorInvalidValue;
-    const uint64_t Lw = (L + (uint64_t)pack - 1) / (uint64_t)pack;
-    const uint64_t groups = encode_mask_groups(N, Lw);
-    if (groups == 0) return hipSuccess;
-    if (groups > 0x7fffffffull || frac_bits < 0 || frac_bits > 30) return hipErrorInvalidValue;
-    const uint32_t tiles = (uint32_t)((Lw + 1023) / 1024);
-    const float scale = (float)(1u << frac_bits);
-    const uint32_t draws = (uint32_t)(noise_bits + 31) / 32, r = (uint32_t)noise_bits % 32;
-    const uint32_t last_mask = r ? (1u << r) - 1u : 0xffffffffu, half = (uint32_t)noise_bits / 2;
-    if (pack == 1)
-        launch_encode_noise<1>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
-                               d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, 0u, d_out, out_pitch, d_clipped);
-    else if (pack == 2)
-        launch_encode_noise<2>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
-                               d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
-    else
-        launch_encode_noise<4>(d_dither != nullptr, (unsigned)groups, stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither,
-                               d_noise, draws, last_mask, half, L, Lw, tiles, clip, scale, bias, d_out, out_pitch, d_clipped);
+    const float scale = (float)(1u << c.frac_bits);
+    const uint32_t draws = (uint32_t)(c.noise_bits + 31) / 32, r = (uint32_t)c.noise_bits % 32;
+    const uint32_t last_mask = r ? (1u << r) - 1u : 0xffffffffu, half = (uint32_t)c.noise_bits / 2;
+    // [pack / 2][stochastic][noise]: pack is 1, 2 or 4 (refused above otherwise), so pack / 2 is 0, 1 or 2
+#define FLM_E(P) {{encode_mask_kernel<P, false, false>, encode_mask_kernel<P, false, true>}, \
+                  {encode_mask_kernel<P, true, false>, encode_mask_kernel<P, true, true>}}
+    static constexpr decltype(&encode_mask_kernel<1, false, false>) kernels[3][2][2] = {FLM_E(1), FLM_E(2), FLM_E(4)};
+#undef FLM_E
+    hipLaunchKernelGGL(kernels[c.pack / 2][d_dither != nullptr][c.noise_bits != 0], dim3((unsigned)groups), dim3(256), 0,
+                       stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither, d_noise, draws, last_mask, half, L, Lw, tiles,
+                       c.clip, scale, c.pack == 1 ? 0u : c.bias, d_out, out_pitch, d_clipped);
     return hipGetLastError();
 }
 

@@ -282,20 +282,11 @@ int refuse(flm_ctx *ctx, const char *why, int code = FLM_EINVAL) { return why ? 
 int check_range(flm_ctx *ctx, uint64_t slot0, uint64_t n) {
     return refuse(ctx, flm::rt::slot_range_error(slot0, n), FLM_ERANGE);
 }
-int check_codec(flm_ctx *ctx, int frac_bits, float clip, int64_t n) {
-    bool headroom = false;
-    const char *why = flm::rt::codec_error(frac_bits, clip, n, &headroom);
-    return refuse(ctx, why, headroom ? FLM_ERANGE : FLM_EINVAL);
-}
-int check_packed_codec(flm_ctx *ctx, int frac_bits, float clip, int pack, int64_t n, uint32_t *bias) {
-    bool headroom = false;
-    const char *why = flm::rt::packed_codec_error(frac_bits, clip, pack, n, &headroom, bias);
-    return refuse(ctx, why, headroom ? FLM_ERANGE : FLM_EINVAL);
-}
-int check_noise_codec(flm_ctx *ctx, int frac_bits, float clip, int pack, int noise_bits, int64_t n, uint64_t L_params,
-                      uint32_t *bias, uint32_t *bias_n) {
+// c's frac_bits, clip, pack and noise_bits against the codec's rule for n contributors; fills c.bias, and *bias_n
+int check_codec(flm_ctx *ctx, flm::CodecParams &c, bool unpacked_ok, int64_t n, uint64_t L_params, uint32_t *bias_n = nullptr) {
     bool range = false;
-    const char *why = flm::rt::noise_codec_error(frac_bits, clip, pack, noise_bits, n, L_params, &range, bias, bias_n);
+    const char *why = flm::rt::codec_error(c.frac_bits, c.clip, c.pack, unpacked_ok, c.noise_bits, n, L_params, &range,
+                                           &c.bias, bias_n);
     return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
 }
 int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
@@ -1250,43 +1241,27 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
     return run_rows_jobs(ctx, d_x, pitch, N, seg, signs, d_seeds, (int)K, 1u, L, 0, d_out, s);
 }
 
-int flm_codec_check(int frac_bits, float clip, int64_t n_clients) { return check_codec(nullptr, frac_bits, clip, n_clients); }
+// ---- the fixed-point codec: float rows in, ring rows of ceil(L / pack) words out, and the mean of a sum back
+// (flm_call_args.h has the rule).  One body per call shape; an entry point fixes its pack and noise_bits and whether
+// it admits pack = 1 (the packed calls do not: pack = 1 is the unpacked calls' job).
 
-int flm_client_encode_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
-                           const int8_t *signs, size_t L, int frac_bits, float clip, const uint8_t *dither,
-                           uint32_t *out, uint32_t *clipped) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    if (int rc = check_codec(ctx, frac_bits, clip, 1)) return rc;
-    if (N == 0 || L == 0) return 0;
-    int64_t K = 0;
-    if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
-    if (int rc = check_range(ctx, 0, L)) return rc;
-    FLM_ON_DEVICE(ctx);
-    HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::client_encode_mask_args(N, K, L, dither, clipped), {x, seeds, dither, out, clipped});
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_client_encode_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs, L,
-                                            frac_bits, clip, hc.dev<uint8_t>(2), hc.dev<uint32_t>(3), hc.pitch(3) / 4,
-                                            hc.dev<uint32_t>(4), ctx->stream))
-        return rc;
-    return hc.finish();
-}
+namespace {
 
-int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
-                               const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
-                               const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
-                               void *stream) {
+int encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg, const uint8_t *d_seeds,
+                    const int8_t *signs, size_t L, flm::CodecParams c, bool unpacked_ok, const uint8_t *d_dither,
+                    const uint8_t *d_noise, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped, void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = check_codec(ctx, frac_bits, clip, 1)) return rc;
+    if (int rc = check_codec(ctx, c, unpacked_ok, 1, L)) return rc;
+    if (c.noise_bits && !d_noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
     if (N <= 0 || L == 0) return 0;
+    const size_t Lw = flm::rt::packed_words(L, c.pack);
     int64_t K = 0;
     if (int rc = refuse(ctx, flm::rt::client_args_error(d_x && d_out, N, seg, d_seeds, signs, &K))) return rc;
     if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, Lw))) return rc;
     if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
-    if (int rc = check_range(ctx, 0, L)) return rc;
-    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, L)))) return rc;
+    if (int rc = check_range(ctx, 0, L)) return rc;  // the dither stream is indexed by parameter
+    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, Lw)))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
     Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
@@ -1294,227 +1269,155 @@ int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, i
     hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
     if (e == hipSuccess)
         e = flm::launch_encode_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
-                                    reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, L, frac_bits, clip, d_out,
-                                    out_pitch, d_clipped, s);
+                                    reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, d_noise, L, c, d_out, out_pitch,
+                                    d_clipped, s);
     if (int rc = stage_done(ctx, up, s, 0)) return rc;
     FLM_HIP(ctx, e);
     return 0;
 }
 
-int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, int64_t count, float *out) {
+// the codec before N < 0 (the plain and packed entry points refuse a negative N first, themselves); the noise
+// seeds are wanted, and travel, only when noise_bits > 0
+int encode_mask_host(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds, const int8_t *signs,
+                     size_t L, flm::CodecParams c, bool unpacked_ok, const uint8_t *dither, const uint8_t *noise,
+                     uint32_t *out, uint32_t *clipped) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = refuse(ctx, flm::rt::decode_error(frac_bits, count))) return rc;
-    if (L == 0) return 0;
-    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    FLM_ON_DEVICE(ctx);
-    HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::decode_sum_args(L), {sum, out});
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_decode_sum_dev(ctx, hc.dev<uint32_t>(0), L, frac_bits, count, hc.dev<float>(1), ctx->stream)) return rc;
-    return hc.finish();
-}
-
-int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, int64_t count, float *d_out,
-                       void *stream) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = refuse(ctx, flm::rt::decode_error(frac_bits, count))) return rc;
-    if (L == 0) return 0;
-    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
-    FLM_ON_DEVICE(ctx);
-    FLM_HIP(ctx, flm::launch_decode_sum(d_sum, L, (double)count * std::ldexp(1.0, frac_bits), d_out,
-                                        static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-// ---- the packed codec: pack parameters per ring word, rows of ceil(L / pack) words (flm_call_args.h has the rule)
-
-int flm_codec_check_packed(int frac_bits, float clip, int pack, int64_t n_clients) {
-    return check_packed_codec(nullptr, frac_bits, clip, pack, n_clients, nullptr);
-}
-
-int flm_client_encode_pack_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
-                                const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
-                                uint32_t *out, uint32_t *clipped) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_codec(ctx, c, unpacked_ok, 1, L)) return rc;
     if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, 1, nullptr)) return rc;
+    if (c.noise_bits && !noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
     if (N == 0 || L == 0) return 0;
     int64_t K = 0;
     if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
     if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::client_encode_pack_mask_args(N, K, L, flm::rt::packed_words(L, pack), dither, clipped),
-               {x, seeds, dither, out, clipped});
+    hc.declare(flm::rt::client_encode_mask_args(N, K, L, flm::rt::packed_words(L, c.pack), dither, c.noise_bits, clipped),
+               {x, seeds, dither, noise, out, clipped});
     if (int rc = hc.begin()) return rc;
-    if (int rc = flm_client_encode_pack_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs, L,
-                                                 frac_bits, clip, pack, hc.dev<uint8_t>(2), hc.dev<uint32_t>(3),
-                                                 hc.pitch(3) / 4, hc.dev<uint32_t>(4), ctx->stream))
+    if (int rc = encode_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs, L, c, unpacked_ok,
+                                 hc.dev<uint8_t>(2), hc.dev<uint8_t>(3), hc.dev<uint32_t>(4), hc.pitch(4) / 4,
+                                 hc.dev<uint32_t>(5), ctx->stream))
         return rc;
     return hc.finish();
 }
 
+// The decode's rule.  pack = 1 where admitted is flm_decode_sum, whose rule knows no clip; packed, the codec's rule
+// for `count` contributors, and *bias_n gets B_n = B + noise_bits / 2.
+int check_decode(flm_ctx *ctx, flm::CodecParams &c, bool unpacked_ok, int64_t count, uint32_t *bias_n) {
+    if (unpacked_ok && c.pack == 1) return refuse(ctx, flm::rt::decode_error(c.frac_bits, count));
+    return check_codec(ctx, c, unpacked_ok, count, 0, bias_n);
+}
+
+// Unpacked, the kernel may run in place.  Packed, the noise only changes the bias: count B_n in count B's place.
+int decode_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, flm::CodecParams c, bool unpacked_ok, int64_t count,
+               float *d_out, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint32_t bias_n = 0;
+    if (int rc = check_decode(ctx, c, unpacked_ok, count, &bias_n)) return rc;
+    if (L == 0) return 0;
+    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
+    FLM_ON_DEVICE(ctx);
+    const double denom = (double)count * std::ldexp(1.0, c.frac_bits);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FLM_HIP(ctx, c.pack == 1 ? flm::launch_decode_sum(d_sum, L, denom, d_out, s)
+                             : flm::launch_decode_unpack(d_sum, L, c.pack, count * (int64_t)bias_n, denom, d_out, s));
+    return 0;
+}
+
+int decode_host(flm_ctx *ctx, const uint32_t *sum, size_t L, flm::CodecParams c, bool unpacked_ok, int64_t count, float *out) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_decode(ctx, c, unpacked_ok, count, nullptr)) return rc;
+    if (L == 0) return 0;
+    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::decode_unpack_args(L, flm::rt::packed_words(L, c.pack)), {sum, out});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = decode_dev(ctx, hc.dev<uint32_t>(0), L, c, unpacked_ok, count, hc.dev<float>(1), ctx->stream)) return rc;
+    return hc.finish();
+}
+
+}  // namespace
+
+int flm_codec_check(int frac_bits, float clip, int64_t n_clients) {
+    flm::CodecParams c{frac_bits, clip, 1, 0, 0};
+    return check_codec(nullptr, c, true, n_clients, 0);
+}
+int flm_codec_check_packed(int frac_bits, float clip, int pack, int64_t n_clients) {
+    flm::CodecParams c{frac_bits, clip, pack, 0, 0};
+    return check_codec(nullptr, c, false, n_clients, 0);
+}
+int flm_codec_check_noise(int frac_bits, float clip, int pack, int noise_bits, int64_t n_clients, uint64_t L_params) {
+    flm::CodecParams c{frac_bits, clip, pack, noise_bits, 0};
+    return check_codec(nullptr, c, true, n_clients, L_params);
+}
+
+int flm_client_encode_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                           const int8_t *signs, size_t L, int frac_bits, float clip, const uint8_t *dither,
+                           uint32_t *out, uint32_t *clipped) {
+    if (ctx && N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, 1, 0, 0}, true, dither, nullptr, out, clipped);
+}
+int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                               const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
+                               const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
+                               void *stream) {
+    return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, 1, 0, 0}, true, d_dither, nullptr,
+                           d_out, out_pitch, d_clipped, stream);
+}
+int flm_client_encode_pack_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
+                                uint32_t *out, uint32_t *clipped) {
+    if (ctx && N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, 0, 0}, false, dither, nullptr, out, clipped);
+}
 int flm_client_encode_pack_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
                                     const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
                                     int pack, const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch,
                                     uint32_t *d_clipped, void *stream) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    uint32_t bias = 0;
-    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, 1, &bias)) return rc;
-    if (N <= 0 || L == 0) return 0;
-    const size_t Lw = flm::rt::packed_words(L, pack);
-    int64_t K = 0;
-    if (int rc = refuse(ctx, flm::rt::client_args_error(d_x && d_out, N, seg, d_seeds, signs, &K))) return rc;
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, Lw))) return rc;
-    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
-    if (int rc = check_range(ctx, 0, L)) return rc;  // the dither stream is indexed by parameter
-    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, Lw)))) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-    FLM_ON_DEVICE(ctx);
-    Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
-    if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
-    hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
-    if (e == hipSuccess)
-        e = flm::launch_encode_pack_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
-                                         reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, L, frac_bits, clip, pack,
-                                         bias, d_out, out_pitch, d_clipped, s);
-    if (int rc = stage_done(ctx, up, s, 0)) return rc;
-    FLM_HIP(ctx, e);
-    return 0;
+    return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, pack, 0, 0}, false, d_dither, nullptr,
+                           d_out, out_pitch, d_clipped, stream);
 }
-
-int flm_decode_unpack(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int64_t count,
-                      float *out) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, count, nullptr)) return rc;
-    if (L == 0) return 0;
-    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    FLM_ON_DEVICE(ctx);
-    HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::decode_unpack_args(L, flm::rt::packed_words(L, pack)), {sum, out});
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_decode_unpack_dev(ctx, hc.dev<uint32_t>(0), L, frac_bits, clip, pack, count, hc.dev<float>(1), ctx->stream))
-        return rc;
-    return hc.finish();
-}
-
-int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack, int64_t count,
-                          float *d_out, void *stream) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    uint32_t bias = 0;
-    if (int rc = check_packed_codec(ctx, frac_bits, clip, pack, count, &bias)) return rc;
-    if (L == 0) return 0;
-    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
-    FLM_ON_DEVICE(ctx);
-    FLM_HIP(ctx, flm::launch_decode_unpack(d_sum, L, pack, count * (int64_t)bias, (double)count * std::ldexp(1.0, frac_bits),
-                                           d_out, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-// ---- distributed-DP binomial noise drawn inside the encode-mask kernels (flm_call_args.h has the rule)
-
-int flm_codec_check_noise(int frac_bits, float clip, int pack, int noise_bits, int64_t n_clients, uint64_t L_params) {
-    return check_noise_codec(nullptr, frac_bits, clip, pack, noise_bits, n_clients, L_params, nullptr, nullptr);
-}
-
 int flm_client_encode_noise_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
                                  const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
                                  int noise_bits, const uint8_t *noise, uint32_t *out, uint32_t *clipped) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, 1, L, nullptr, nullptr)) return rc;
-    if (noise_bits == 0)  // off: the calls there were, byte for byte
-        return pack == 1 ? flm_client_encode_mask(ctx, x, N, seg, seeds, signs, L, frac_bits, clip, dither, out, clipped)
-                         : flm_client_encode_pack_mask(ctx, x, N, seg, seeds, signs, L, frac_bits, clip, pack, dither, out,
-                                                       clipped);
-    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    if (!noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
-    if (N == 0 || L == 0) return 0;
-    int64_t K = 0;
-    if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
-    if (int rc = check_range(ctx, 0, L)) return rc;
-    FLM_ON_DEVICE(ctx);
-    HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::client_encode_noise_mask_args(N, K, L, flm::rt::packed_words(L, pack), dither, clipped),
-               {x, seeds, dither, noise, out, clipped});
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_client_encode_noise_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs,
-                                                  L, frac_bits, clip, pack, hc.dev<uint8_t>(2), noise_bits,
-                                                  hc.dev<uint8_t>(3), hc.dev<uint32_t>(4), hc.pitch(4) / 4,
-                                                  hc.dev<uint32_t>(5), ctx->stream))
-        return rc;
-    return hc.finish();
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, noise_bits, 0}, true, dither, noise, out,
+                            clipped);
 }
-
 int flm_client_encode_noise_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
                                      const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
                                      int pack, const uint8_t *d_dither, int noise_bits, const uint8_t *d_noise,
                                      uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped, void *stream) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    uint32_t bias = 0;
-    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, 1, L, &bias, nullptr)) return rc;
-    if (noise_bits == 0)  // off: the calls there were, byte for byte
-        return pack == 1 ? flm_client_encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, frac_bits, clip, d_dither,
-                                                      d_out, out_pitch, d_clipped, stream)
-                         : flm_client_encode_pack_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, frac_bits, clip, pack,
-                                                           d_dither, d_out, out_pitch, d_clipped, stream);
-    if (!d_noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
-    if (N <= 0 || L == 0) return 0;
-    const size_t Lw = flm::rt::packed_words(L, pack);
-    int64_t K = 0;
-    if (int rc = refuse(ctx, flm::rt::client_args_error(d_x && d_out, N, seg, d_seeds, signs, &K))) return rc;
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, Lw))) return rc;
-    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
-    if (int rc = check_range(ctx, 0, L)) return rc;  // the dither stream is indexed by parameter
-    if (int rc = refuse(ctx, flm::rt::encode_mask_launch_error(flm::encode_mask_groups(N, Lw)))) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-    FLM_ON_DEVICE(ctx);
-    Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
-    if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
-    hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
-    if (e == hipSuccess)
-        e = flm::launch_encode_noise_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
-                                          reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, d_noise, noise_bits, L,
-                                          frac_bits, clip, pack, bias, d_out, out_pitch, d_clipped, s);
-    if (int rc = stage_done(ctx, up, s, 0)) return rc;
-    FLM_HIP(ctx, e);
-    return 0;
+    return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, pack, noise_bits, 0}, true, d_dither,
+                           d_noise, d_out, out_pitch, d_clipped, stream);
 }
 
+int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, int64_t count, float *out) {
+    return decode_host(ctx, sum, L, {frac_bits, 0.0f, 1, 0, 0}, true, count, out);
+}
+int flm_decode_sum_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, int64_t count, float *d_out,
+                       void *stream) {
+    return decode_dev(ctx, d_sum, L, {frac_bits, 0.0f, 1, 0, 0}, true, count, d_out, stream);
+}
+int flm_decode_unpack(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int64_t count,
+                      float *out) {
+    return decode_host(ctx, sum, L, {frac_bits, clip, pack, 0, 0}, false, count, out);
+}
+int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack, int64_t count,
+                          float *d_out, void *stream) {
+    return decode_dev(ctx, d_sum, L, {frac_bits, clip, pack, 0, 0}, false, count, d_out, stream);
+}
+// pack = 1 is refused here, as the packed calls refuse it; any other pack by the noise rule
 int flm_decode_unpack_noise(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int noise_bits,
                             int64_t count, float *out) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
-    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, count, 0, nullptr, nullptr)) return rc;
-    if (L == 0) return 0;
-    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    FLM_ON_DEVICE(ctx);
-    HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::decode_unpack_args(L, flm::rt::packed_words(L, pack)), {sum, out});
-    if (int rc = hc.begin()) return rc;
-    if (int rc = flm_decode_unpack_noise_dev(ctx, hc.dev<uint32_t>(0), L, frac_bits, clip, pack, noise_bits, count,
-                                             hc.dev<float>(1), ctx->stream))
-        return rc;
-    return hc.finish();
+    if (ctx && pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
+    return decode_host(ctx, sum, L, {frac_bits, clip, pack, noise_bits, 0}, true, count, out);
 }
-
 int flm_decode_unpack_noise_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
                                 int noise_bits, int64_t count, float *d_out, void *stream) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
-    uint32_t bias_n = 0;
-    if (int rc = check_noise_codec(ctx, frac_bits, clip, pack, noise_bits, count, 0, nullptr, &bias_n)) return rc;
-    if (L == 0) return 0;
-    if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
-    FLM_ON_DEVICE(ctx);
-    // decode_unpack_kernel as it is: only the bias changes, B_n = B + noise_bits / 2 in B's place
-    FLM_HIP(ctx, flm::launch_decode_unpack(d_sum, L, pack, count * (int64_t)bias_n, (double)count * std::ldexp(1.0, frac_bits),
-                                           d_out, static_cast<hipStream_t>(stream)));
-    return 0;
+    if (ctx && pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
+    return decode_dev(ctx, d_sum, L, {frac_bits, clip, pack, noise_bits, 0}, true, count, d_out, stream);
 }
 
 int flm_prg_expand(flm_ctx *ctx, const uint8_t *seeds, int K, size_t L, uint64_t slot0, uint32_t *out) {

@@ -442,9 +442,8 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
                 FLM_SHIP(st, hipMalloc(&k.fout, want));
                 k.fout_cap = want;
             }
-            if (int rc = dec.noise_bits ? flm_decode_unpack_noise_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack,
-                                                                     dec.noise_bits, count, k.fout, s)
-                                        : flm_decode_unpack_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, count, k.fout, s))
+            if (int rc = flm_decode_unpack_noise_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, dec.noise_bits, count,
+                                                     k.fout, s))
                 return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
             FLM_SHIP(st, hipMemcpyAsync(st->hfout + P * k.lo, k.fout, np * sizeof(float), hipMemcpyDeviceToHost, s));
             continue;
@@ -480,25 +479,11 @@ int flm_store_unmask_f32(flm_store *st, const uint8_t *seeds, const int8_t *sign
     return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
 }
 
-int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
-                                int frac_bits, float clip, int pack, int64_t count, float *out) {
-    bool headroom = false;
-    if (const char *why = flm::rt::packed_codec_error(frac_bits, clip, pack, count, &headroom, nullptr))
-        return sfail(st, headroom ? FLM_ERANGE : FLM_EINVAL, why);
-    if (st && st->L != flm::rt::packed_words(L_params, pack))
-        return sfail(st, FLM_EINVAL, "the store's length must be ceil(L_params / pack)");
-    StoreDecode dec;
-    dec.frac_bits = frac_bits, dec.count = count, dec.pack = pack, dec.clip = clip, dec.L_params = L_params;
-    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
-}
-
-int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
-                                      int frac_bits, float clip, int pack, int noise_bits, int64_t count, float *out) {
-    if (noise_bits == 0)  // off: the call there was
-        return flm_store_unmask_unpack_f32(st, seeds, signs, K, L_params, frac_bits, clip, pack, count, out);
+// the packed store's mean, with or without the clients' noise
+static int store_unmask_unpack(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params, int frac_bits,
+                               float clip, int pack, bool unpacked_ok, int noise_bits, int64_t count, float *out) {
     bool range = false;
-    if (pack == 1) return sfail(st, FLM_EINVAL, "pack must be 2 or 4");
-    if (const char *why = flm::rt::noise_codec_error(frac_bits, clip, pack, noise_bits, count, 0, &range, nullptr, nullptr))
+    if (const char *why = flm::rt::codec_error(frac_bits, clip, pack, unpacked_ok, noise_bits, count, 0, &range))
         return sfail(st, range ? FLM_ERANGE : FLM_EINVAL, why);
     if (st && st->L != flm::rt::packed_words(L_params, pack))
         return sfail(st, FLM_EINVAL, "the store's length must be ceil(L_params / pack)");
@@ -506,6 +491,19 @@ int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const
     dec.frac_bits = frac_bits, dec.count = count, dec.pack = pack, dec.clip = clip, dec.L_params = L_params;
     dec.noise_bits = noise_bits;
     return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
+}
+
+int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                int frac_bits, float clip, int pack, int64_t count, float *out) {
+    return store_unmask_unpack(st, seeds, signs, K, L_params, frac_bits, clip, pack, false, 0, count, out);
+}
+
+int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                      int frac_bits, float clip, int pack, int noise_bits, int64_t count, float *out) {
+    if (noise_bits == 0)  // off: the call there was, its refusals included
+        return flm_store_unmask_unpack_f32(st, seeds, signs, K, L_params, frac_bits, clip, pack, count, out);
+    if (pack == 1) return sfail(st, FLM_EINVAL, "pack must be 2 or 4");  // the packed calls' refusal; others by the noise rule
+    return store_unmask_unpack(st, seeds, signs, K, L_params, frac_bits, clip, pack, true, noise_bits, count, out);
 }
 
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms) {

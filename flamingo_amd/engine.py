@@ -280,16 +280,57 @@ class MaskEngine:
         packed codec's rule instead (flm_codec_check_packed: n * 2 ceil(clip * 2^frac_bits) <= 2^(32/pack) - 1).
         noise_bits > 0: the rule with every client's binomial noise share (flm_codec_check_noise: the worst case,
         ceil(clip * 2^frac_bits) + noise_bits / 2 in the bound's place, and for L > 0 parameters the noise
-        stream's length rule ceil(noise_bits / 32) * ceil(L / 16) <= 2^32)."""
-        if noise_bits != 0:
-            rc = self.lib.flm_codec_check_noise(int(frac_bits), float(clip), int(pack), int(noise_bits), int(n_clients), int(L))
-            self._check(rc, "flm_codec_check_noise")
-        elif pack == 1:
-            rc = self.lib.flm_codec_check(int(frac_bits), float(clip), int(n_clients))
-            self._check(rc, "flm_codec_check")
-        else:
-            rc = self.lib.flm_codec_check_packed(int(frac_bits), float(clip), int(pack), int(n_clients))
-            self._check(rc, "flm_codec_check_packed")
+        stream's length rule ceil(noise_bits / 32) * ceil(L / 16) <= 2^32).  flm_codec_check_noise is all three:
+        without noise it is the rule of the pack."""
+        rc = self.lib.flm_codec_check_noise(int(frac_bits), float(clip), int(pack), int(noise_bits), int(n_clients), int(L))
+        self._check(rc, "flm_codec_check_noise")
+
+    def _encode_mask(self, fn: str, codec, seg, seeds, signs, L: int, x, frac_bits: int, clip: float, pack: int, dither,
+                     noise, return_clipped: bool):
+        """The host form of the three encode calls.  codec(dither, noise): the arguments of `fn` between clip and
+        out, which is where the three differ."""
+        seg = np.ascontiguousarray(seg, dtype=np.int64)
+        N = seg.shape[0] - 1
+        seeds = _seeds_array(seeds)
+        signs = _signs_array(signs, seeds.shape[0])
+        if seg[-1] != seeds.shape[0]:
+            raise RuntimeError("seg[-1] must equal the number of seeds")
+        if x is None:
+            raise RuntimeError("x is required")
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.shape != (N, L):
+            raise RuntimeError("x must be (N, L)")
+        ptrs = []
+        for name, s in (("dither", dither), ("noise", noise)):
+            if s is not None:
+                s = _seeds_array(s)
+                if s.shape[0] != N:
+                    raise RuntimeError(f"one 32-byte {name} seed per client")
+            ptrs.append(p_u8(s) if s is not None else None)
+        out = np.empty((N, -(-L // pack) if pack > 0 else 0), dtype=np.uint32)
+        clipped = np.zeros(N, dtype=np.uint32)
+        rc = getattr(self.lib, fn)(self.ctx, p_f32(x), N, p_i64(seg), p_u8(seeds), p_i8(signs), L, int(frac_bits),
+                                   float(clip), *codec(*ptrs), p_u32(out), p_u32(clipped) if return_clipped else None)
+        self._check(rc, fn)
+        return (out, clipped) if return_clipped else out
+
+    def client_encode_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float, dither=None,
+                           return_clipped: bool = False):
+        """y_i = encode(x_i) + sum_{k in seg i} signs[k]*PRG(seeds[k]) for float32 x (N, L); (N, L) uint32.
+
+        dither: N 32-byte seeds for stochastic rounding, None for nearest-even.  With
+        return_clipped, also the (N,) uint32 counts of elements that were NaN or beyond +-clip."""
+        return self._encode_mask("flm_client_encode_mask", lambda d, z: (d,), seg, seeds, signs, L, x, frac_bits, clip, 1,
+                                 dither, None, return_clipped)
+
+    def client_encode_pack_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float,
+                                pack: int, dither=None, return_clipped: bool = False):
+        """client_encode_mask with `pack` (2 or 4) parameters per ring word: float32 x (N, L) in,
+        (N, ceil(L / pack)) uint32 out; field j of word l' is encode(x[pack l' + j]) + ceil(clip 2^frac_bits).
+        The dither stream is indexed by parameter.  flm_client_encode_pack_mask."""
+        pack = int(pack)
+        return self._encode_mask("flm_client_encode_pack_mask", lambda d, z: (pack, d), seg, seeds, signs, L, x, frac_bits,
+                                 clip, pack, dither, None, return_clipped)
 
     def client_encode_noise_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float,
                                  pack: int = 1, dither=None, noise_bits: int = 0, noise=None,
@@ -299,118 +340,25 @@ class MaskEngine:
         noise_bits / 2 on each parameter's quantised value.  noise: N 32-byte seeds, secret and fresh per
         iteration.  noise_bits = 0: the calls without noise, bit for bit (noise is ignored).
         flm_client_encode_noise_mask."""
-        seg = np.ascontiguousarray(seg, dtype=np.int64)
-        N = seg.shape[0] - 1
-        seeds = _seeds_array(seeds)
-        signs = _signs_array(signs, seeds.shape[0])
-        if seg[-1] != seeds.shape[0]:
-            raise RuntimeError("seg[-1] must equal the number of seeds")
-        if x is None:
-            raise RuntimeError("x is required")
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        if x.shape != (N, L):
-            raise RuntimeError("x must be (N, L)")
-        dp = zp = None
-        if dither is not None:
-            dither = _seeds_array(dither)
-            if dither.shape[0] != N:
-                raise RuntimeError("one 32-byte dither seed per client")
-            dp = p_u8(dither)
-        if noise is not None:
-            noise = _seeds_array(noise)
-            if noise.shape[0] != N:
-                raise RuntimeError("one 32-byte noise seed per client")
-            zp = p_u8(noise)
         pack = int(pack)
-        out = np.empty((N, -(-L // pack) if pack > 0 else 0), dtype=np.uint32)
-        clipped = np.zeros(N, dtype=np.uint32)
-        rc = self.lib.flm_client_encode_noise_mask(self.ctx, p_f32(x), N, p_i64(seg), p_u8(seeds), p_i8(signs), L,
-                                                   int(frac_bits), float(clip), pack, dp, int(noise_bits), zp, p_u32(out),
-                                                   p_u32(clipped) if return_clipped else None)
-        self._check(rc, "flm_client_encode_noise_mask")
-        return (out, clipped) if return_clipped else out
-
-    def client_encode_pack_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float,
-                                pack: int, dither=None, return_clipped: bool = False):
-        """client_encode_mask with `pack` (2 or 4) parameters per ring word: float32 x (N, L) in,
-        (N, ceil(L / pack)) uint32 out; field j of word l' is encode(x[pack l' + j]) + ceil(clip 2^frac_bits).
-        The dither stream is indexed by parameter.  flm_client_encode_pack_mask."""
-        seg = np.ascontiguousarray(seg, dtype=np.int64)
-        N = seg.shape[0] - 1
-        seeds = _seeds_array(seeds)
-        signs = _signs_array(signs, seeds.shape[0])
-        if seg[-1] != seeds.shape[0]:
-            raise RuntimeError("seg[-1] must equal the number of seeds")
-        if x is None:
-            raise RuntimeError("x is required")
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        if x.shape != (N, L):
-            raise RuntimeError("x must be (N, L)")
-        dp = None
-        if dither is not None:
-            dither = _seeds_array(dither)
-            if dither.shape[0] != N:
-                raise RuntimeError("one 32-byte dither seed per client")
-            dp = p_u8(dither)
-        pack = int(pack)
-        out = np.empty((N, -(-L // pack) if pack > 0 else 0), dtype=np.uint32)
-        clipped = np.zeros(N, dtype=np.uint32)
-        rc = self.lib.flm_client_encode_pack_mask(self.ctx, p_f32(x), N, p_i64(seg), p_u8(seeds), p_i8(signs), L,
-                                                  int(frac_bits), float(clip), pack, dp, p_u32(out),
-                                                  p_u32(clipped) if return_clipped else None)
-        self._check(rc, "flm_client_encode_pack_mask")
-        return (out, clipped) if return_clipped else out
+        return self._encode_mask("flm_client_encode_noise_mask", lambda d, z: (pack, d, int(noise_bits), z), seg, seeds,
+                                 signs, L, x, frac_bits, clip, pack, dither, noise, return_clipped)
 
     def decode_unpack(self, total: np.ndarray, L: int, frac_bits: int, clip: float, pack: int, count: int = 1,
                       noise_bits: int = 0) -> np.ndarray:
-        """The L float32 means of `count` contributors held in the ceil(L / pack) summed packed words `total`
-        (flm_decode_unpack): field - count ceil(clip 2^frac_bits), over count 2^frac_bits.  noise_bits > 0: rows of
-        client_encode_noise_mask, whose bias is ceil(clip 2^frac_bits) + noise_bits / 2 (flm_decode_unpack_noise)."""
+        """The L float32 means of `count` contributors held in the ceil(L / pack) summed packed words `total`:
+        field - count ceil(clip 2^frac_bits), over count 2^frac_bits.  noise_bits > 0: rows of
+        client_encode_noise_mask, whose bias is ceil(clip 2^frac_bits) + noise_bits / 2.  flm_decode_unpack_noise,
+        which without noise is flm_decode_unpack."""
         total = np.ascontiguousarray(total, dtype=np.uint32)
         pack = int(pack)
         if total.ndim != 1 or (pack > 0 and total.shape[0] != -(-L // pack)):
             raise RuntimeError("total must be a vector of ceil(L / pack) words")
         out = np.empty(L, dtype=np.float32)
-        if noise_bits != 0:
-            rc = self.lib.flm_decode_unpack_noise(self.ctx, p_u32(total), L, int(frac_bits), float(clip), pack,
-                                                  int(noise_bits), int(count), p_f32(out))
-            self._check(rc, "flm_decode_unpack_noise")
-            return out
-        rc = self.lib.flm_decode_unpack(self.ctx, p_u32(total), L, int(frac_bits), float(clip), pack, int(count),
-                                        p_f32(out))
-        self._check(rc, "flm_decode_unpack")
+        rc = self.lib.flm_decode_unpack_noise(self.ctx, p_u32(total), L, int(frac_bits), float(clip), pack,
+                                              int(noise_bits), int(count), p_f32(out))
+        self._check(rc, "flm_decode_unpack_noise")
         return out
-
-    def client_encode_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float, dither=None,
-                           return_clipped: bool = False):
-        """y_i = encode(x_i) + sum_{k in seg i} signs[k]*PRG(seeds[k]) for float32 x (N, L); (N, L) uint32.
-
-        dither: N 32-byte seeds for stochastic rounding, None for nearest-even.  With
-        return_clipped, also the (N,) uint32 counts of elements that were NaN or beyond +-clip."""
-        seg = np.ascontiguousarray(seg, dtype=np.int64)
-        N = seg.shape[0] - 1
-        seeds = _seeds_array(seeds)
-        signs = _signs_array(signs, seeds.shape[0])
-        if seg[-1] != seeds.shape[0]:
-            raise RuntimeError("seg[-1] must equal the number of seeds")
-        if x is None:
-            raise RuntimeError("x is required")
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        if x.shape != (N, L):
-            raise RuntimeError("x must be (N, L)")
-        dp = None
-        if dither is not None:
-            dither = _seeds_array(dither)
-            if dither.shape[0] != N:
-                raise RuntimeError("one 32-byte dither seed per client")
-            dp = p_u8(dither)
-        out = np.empty((N, L), dtype=np.uint32)
-        clipped = np.zeros(N, dtype=np.uint32)
-        rc = self.lib.flm_client_encode_mask(self.ctx, p_f32(x), N, p_i64(seg), p_u8(seeds), p_i8(signs), L,
-                                             int(frac_bits), float(clip), dp, p_u32(out),
-                                             p_u32(clipped) if return_clipped else None)
-        self._check(rc, "flm_client_encode_mask")
-        return (out, clipped) if return_clipped else out
 
     def decode_sum(self, total: np.ndarray, frac_bits: int, count: int = 1) -> np.ndarray:
         """float32(int32(total) / (count * 2^frac_bits)): the ring sum as the mean of `count` contributors."""
@@ -539,80 +487,11 @@ class MaskEngine:
         self._check(rc, "flm_client_mask_dev")
         return out
 
-    def client_encode_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float,
-                               dither_dev=None, clipped=None, stream=None):
-        """Device client_encode_mask: seg/signs host arrays; seeds_dev (K, 32) uint8, x (>= N, >= L) float32,
-        out (>= N, >= L) 32-bit, dither_dev (N, 32) uint8 or None, clipped (>= N,) 32-bit or None: CUDA
-        tensors, rows at their own strides.  Enqueued on `stream`; nothing is synchronised."""
+    def _encode_mask_dev(self, fn: str, codec, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float,
+                         pack: int, dither_dev, noise_dev, clipped, stream):
+        """The device form of the three encode calls; codec(dither, noise) as in _encode_mask, on device addresses."""
         import torch
         seg, signs, N, K = _client_seeds(seg, signs, seeds_dev)
-        for name, t in (("x", x), ("out", out)):
-            if t is None or t.dim() != 2 or t.shape[0] < N or t.shape[1] < L or t.element_size() != 4 or t.stride(1) != 1:
-                raise RuntimeError(f"{name} must be (>= {N}, >= {L}) 32-bit with unit column stride")
-        if x.dtype != torch.float32:
-            raise RuntimeError("x must be float32")
-        if dither_dev is not None and (tuple(dither_dev.shape) != (N, 32) or dither_dev.element_size() != 1
-                                       or not dither_dev.is_contiguous()):
-            raise RuntimeError(f"dither_dev must be a contiguous ({N}, 32) uint8 tensor")
-        if clipped is not None and (clipped.dim() != 1 or clipped.shape[0] < N or clipped.element_size() != 4
-                                    or not clipped.is_contiguous()):
-            raise RuntimeError(f"clipped must be a contiguous (>= {N},) 32-bit tensor")
-        rc = self.lib.flm_client_encode_mask_dev(
-            self.ctx, ctypes.c_void_p(x.data_ptr()), x.stride(0) if N > 1 else x.shape[1], N, p_i64(seg),
-            ctypes.c_void_p(seeds_dev.data_ptr() if K else 0), p_i8(signs), L, int(frac_bits), float(clip),
-            ctypes.c_void_p(dither_dev.data_ptr() if dither_dev is not None else 0), ctypes.c_void_p(out.data_ptr()),
-            out.stride(0) if N > 1 else out.shape[1], ctypes.c_void_p(clipped.data_ptr() if clipped is not None else 0),
-            self._stream_handle(stream))
-        self._check(rc, "flm_client_encode_mask_dev")
-        return out
-
-    def decode_sum_dev(self, total, out, L: int, frac_bits: int, count: int = 1, stream=None):
-        """out[:L] = decode(total[:L]) on CUDA tensors (32-bit in, float32 out); out may be a float32 view of total."""
-        import torch
-        if total.element_size() != 4 or total.numel() < L or out.dtype != torch.float32 or out.numel() < L \
-                or not total.is_contiguous() or not out.is_contiguous():
-            raise RuntimeError(f"total must hold >= {L} 32-bit words and out >= {L} float32, both contiguous")
-        rc = self.lib.flm_decode_sum_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), int(count),
-                                         ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
-        self._check(rc, "flm_decode_sum_dev")
-        return out
-
-    def client_encode_pack_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float, pack: int,
-                                    dither_dev=None, clipped=None, stream=None):
-        """Device client_encode_pack_mask: as client_encode_mask_dev, with x (>= N, >= L) float32 and out
-        (>= N, >= ceil(L / pack)) 32-bit.  Enqueued on `stream`; nothing is synchronised."""
-        import torch
-        seg, signs, N, K = _client_seeds(seg, signs, seeds_dev)
-        pack = int(pack)
-        Lw = -(-L // pack) if pack > 0 else L
-        for name, t, n in (("x", x, L), ("out", out, Lw)):
-            if t is None or t.dim() != 2 or t.shape[0] < N or t.shape[1] < n or t.element_size() != 4 or t.stride(1) != 1:
-                raise RuntimeError(f"{name} must be (>= {N}, >= {n}) 32-bit with unit column stride")
-        if x.dtype != torch.float32:
-            raise RuntimeError("x must be float32")
-        if dither_dev is not None and (tuple(dither_dev.shape) != (N, 32) or dither_dev.element_size() != 1
-                                       or not dither_dev.is_contiguous()):
-            raise RuntimeError(f"dither_dev must be a contiguous ({N}, 32) uint8 tensor")
-        if clipped is not None and (clipped.dim() != 1 or clipped.shape[0] < N or clipped.element_size() != 4
-                                    or not clipped.is_contiguous()):
-            raise RuntimeError(f"clipped must be a contiguous (>= {N},) 32-bit tensor")
-        rc = self.lib.flm_client_encode_pack_mask_dev(
-            self.ctx, ctypes.c_void_p(x.data_ptr()), x.stride(0) if N > 1 else x.shape[1], N, p_i64(seg),
-            ctypes.c_void_p(seeds_dev.data_ptr() if K else 0), p_i8(signs), L, int(frac_bits), float(clip), pack,
-            ctypes.c_void_p(dither_dev.data_ptr() if dither_dev is not None else 0), ctypes.c_void_p(out.data_ptr()),
-            out.stride(0) if N > 1 else out.shape[1], ctypes.c_void_p(clipped.data_ptr() if clipped is not None else 0),
-            self._stream_handle(stream))
-        self._check(rc, "flm_client_encode_pack_mask_dev")
-        return out
-
-    def client_encode_noise_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float,
-                                     pack: int = 1, dither_dev=None, noise_bits: int = 0, noise_dev=None, clipped=None,
-                                     stream=None):
-        """Device client_encode_noise_mask: as client_encode_pack_mask_dev (pack 1, 2 or 4), with noise_dev a
-        contiguous (N, 32) uint8 tensor of the clients' noise seeds.  Enqueued on `stream`; nothing is synchronised."""
-        import torch
-        seg, signs, N, K = _client_seeds(seg, signs, seeds_dev)
-        pack = int(pack)
         Lw = -(-L // pack) if pack > 0 else L
         for name, t, n in (("x", x, L), ("out", out, Lw)):
             if t is None or t.dim() != 2 or t.shape[0] < N or t.shape[1] < n or t.element_size() != 4 or t.stride(1) != 1:
@@ -625,35 +504,66 @@ class MaskEngine:
         if clipped is not None and (clipped.dim() != 1 or clipped.shape[0] < N or clipped.element_size() != 4
                                     or not clipped.is_contiguous()):
             raise RuntimeError(f"clipped must be a contiguous (>= {N},) 32-bit tensor")
-        rc = self.lib.flm_client_encode_noise_mask_dev(
-            self.ctx, ctypes.c_void_p(x.data_ptr()), x.stride(0) if N > 1 else x.shape[1], N, p_i64(seg),
-            ctypes.c_void_p(seeds_dev.data_ptr() if K else 0), p_i8(signs), L, int(frac_bits), float(clip), pack,
-            ctypes.c_void_p(dither_dev.data_ptr() if dither_dev is not None else 0), int(noise_bits),
-            ctypes.c_void_p(noise_dev.data_ptr() if noise_dev is not None else 0), ctypes.c_void_p(out.data_ptr()),
-            out.stride(0) if N > 1 else out.shape[1], ctypes.c_void_p(clipped.data_ptr() if clipped is not None else 0),
-            self._stream_handle(stream))
-        self._check(rc, "flm_client_encode_noise_mask_dev")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        rc = getattr(self.lib, fn)(
+            self.ctx, ptr(x), x.stride(0) if N > 1 else x.shape[1], N, p_i64(seg), ptr(seeds_dev if K else None), p_i8(signs),
+            L, int(frac_bits), float(clip), *codec(ptr(dither_dev), ptr(noise_dev)), ptr(out),
+            out.stride(0) if N > 1 else out.shape[1], ptr(clipped), self._stream_handle(stream))
+        self._check(rc, fn)
+        return out
+
+    def client_encode_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float,
+                               dither_dev=None, clipped=None, stream=None):
+        """Device client_encode_mask: seg/signs host arrays; seeds_dev (K, 32) uint8, x (>= N, >= L) float32,
+        out (>= N, >= L) 32-bit, dither_dev (N, 32) uint8 or None, clipped (>= N,) 32-bit or None: CUDA
+        tensors, rows at their own strides.  Enqueued on `stream`; nothing is synchronised."""
+        return self._encode_mask_dev("flm_client_encode_mask_dev", lambda d, z: (d,), seg, seeds_dev, signs, out, L, x,
+                                     frac_bits, clip, 1, dither_dev, None, clipped, stream)
+
+    def client_encode_pack_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float, pack: int,
+                                    dither_dev=None, clipped=None, stream=None):
+        """Device client_encode_pack_mask: as client_encode_mask_dev, with x (>= N, >= L) float32 and out
+        (>= N, >= ceil(L / pack)) 32-bit.  Enqueued on `stream`; nothing is synchronised."""
+        pack = int(pack)
+        return self._encode_mask_dev("flm_client_encode_pack_mask_dev", lambda d, z: (pack, d), seg, seeds_dev, signs, out,
+                                     L, x, frac_bits, clip, pack, dither_dev, None, clipped, stream)
+
+    def client_encode_noise_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float,
+                                     pack: int = 1, dither_dev=None, noise_bits: int = 0, noise_dev=None, clipped=None,
+                                     stream=None):
+        """Device client_encode_noise_mask: as client_encode_pack_mask_dev (pack 1, 2 or 4), with noise_dev a
+        contiguous (N, 32) uint8 tensor of the clients' noise seeds.  Enqueued on `stream`; nothing is synchronised."""
+        pack = int(pack)
+        return self._encode_mask_dev("flm_client_encode_noise_mask_dev", lambda d, z: (pack, d, int(noise_bits), z), seg,
+                                     seeds_dev, signs, out, L, x, frac_bits, clip, pack, dither_dev, noise_dev, clipped,
+                                     stream)
+
+    def decode_sum_dev(self, total, out, L: int, frac_bits: int, count: int = 1, stream=None):
+        """out[:L] = decode(total[:L]) on CUDA tensors (32-bit in, float32 out); out may be a float32 view of total."""
+        import torch
+        if total.element_size() != 4 or total.numel() < L or out.dtype != torch.float32 or out.numel() < L \
+                or not total.is_contiguous() or not out.is_contiguous():
+            raise RuntimeError(f"total must hold >= {L} 32-bit words and out >= {L} float32, both contiguous")
+        rc = self.lib.flm_decode_sum_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), int(count),
+                                         ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
+        self._check(rc, "flm_decode_sum_dev")
         return out
 
     def decode_unpack_dev(self, total, out, L: int, frac_bits: int, clip: float, pack: int, count: int = 1, stream=None,
                           noise_bits: int = 0):
         """out[:L] = the packed decode of total[:ceil(L / pack)] on CUDA tensors (32-bit in, float32 out, not views
-        of one another).  noise_bits > 0: rows of client_encode_noise_mask (flm_decode_unpack_noise_dev)."""
+        of one another).  noise_bits > 0: rows of client_encode_noise_mask.  flm_decode_unpack_noise_dev, which
+        without noise is flm_decode_unpack_dev."""
         import torch
         pack = int(pack)
         Lw = -(-L // pack) if pack > 0 else L
         if total.element_size() != 4 or total.numel() < Lw or out.dtype != torch.float32 or out.numel() < L \
                 or not total.is_contiguous() or not out.is_contiguous():
             raise RuntimeError(f"total must hold >= {Lw} 32-bit words and out >= {L} float32, both contiguous")
-        if noise_bits != 0:
-            rc = self.lib.flm_decode_unpack_noise_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits),
-                                                      float(clip), pack, int(noise_bits), int(count),
-                                                      ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
-            self._check(rc, "flm_decode_unpack_noise_dev")
-            return out
-        rc = self.lib.flm_decode_unpack_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), float(clip),
-                                            pack, int(count), ctypes.c_void_p(out.data_ptr()), self._stream_handle(stream))
-        self._check(rc, "flm_decode_unpack_dev")
+        rc = self.lib.flm_decode_unpack_noise_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), float(clip),
+                                                  pack, int(noise_bits), int(count), ctypes.c_void_p(out.data_ptr()),
+                                                  self._stream_handle(stream))
+        self._check(rc, "flm_decode_unpack_noise_dev")
         return out
 
     def prg_expand_dev(self, seeds_dev, out, L: int, slot0: int = 0, stream=None):

@@ -138,21 +138,16 @@ class VectorStore:
                           count: int = 1, noise_bits: int = 0) -> np.ndarray:
         """unmask() of a store of packed rows (its L is ceil(L_params / pack)): every device decodes its word
         shard into the floats it holds before the copy to the host; the L_params float32 means of `count`
-        contributors (flm_store_unmask_unpack_f32; the codec of client_encode_pack_mask).  noise_bits > 0: rows of
-        client_encode_noise_mask, decoded with their bias (flm_store_unmask_unpack_noise_f32)."""
+        contributors (the codec of client_encode_pack_mask).  noise_bits > 0: rows of client_encode_noise_mask,
+        decoded with their bias.  flm_store_unmask_unpack_noise_f32, which without noise is flm_store_unmask_unpack_f32."""
         from .engine import _seeds_array, _signs_array
         seeds = _seeds_array(seeds)
         signs = _signs_array(signs, seeds.shape[0])
         out = np.empty(int(L_params), np.float32)
-        if noise_bits != 0:
-            self._check(self.lib.flm_store_unmask_unpack_noise_f32(self.h, p_u8(seeds), p_i8(signs), seeds.shape[0],
-                                                                   int(L_params), int(frac_bits), float(clip), int(pack),
-                                                                   int(noise_bits), int(count), p_f32(out)),
-                        "flm_store_unmask_unpack_noise_f32")
-            return out
-        self._check(self.lib.flm_store_unmask_unpack_f32(self.h, p_u8(seeds), p_i8(signs), seeds.shape[0], int(L_params),
-                                                         int(frac_bits), float(clip), int(pack), int(count), p_f32(out)),
-                    "flm_store_unmask_unpack_f32")
+        self._check(self.lib.flm_store_unmask_unpack_noise_f32(self.h, p_u8(seeds), p_i8(signs), seeds.shape[0],
+                                                               int(L_params), int(frac_bits), float(clip), int(pack),
+                                                               int(noise_bits), int(count), p_f32(out)),
+                    "flm_store_unmask_unpack_noise_f32")
         return out
 
     def unmask_ms(self) -> float:

@@ -363,27 +363,36 @@ def codec_check(frac_bits, clip, n_clients):
     _check(_lib.flm_codec_check(int(frac_bits), float(clip), int(n_clients)))
 
 
-def client_encode_mask(seeds, signs, L, x, frac_bits, clip, dither=None):
-    """client_mask for a float32 update x ("For machine learning, replace it with model weights",
-    SA_ClientAgent.py:300-304): encode(x) + sum_k signs[k] * PRG(seeds[k]) with the fixed-point encoding
-    (clip to +-clip, frac_bits fractional bits; nearest-even, or stochastic with a 32-byte dither seed) fused
-    into the masking of SA_ClientAgent.py:304-324.  Returns (uint32[L], number of clipped elements)."""
+def _encode_mask(fn, codec, seeds, signs, L, x, frac_bits, clip, pack, dither=None, noise=None):
+    """One client's call of the encode entry point `fn`; codec(dither, noise): its arguments between clip and out,
+    which is where the three entry points differ.  Returns (uint32[ceil(L / pack)], number of clipped elements)."""
     seg = np.array([0, len(seeds)], np.int64)
     sd, sg, K = _seed_arrays(seeds, signs)
     x = np.ascontiguousarray(x, dtype=np.float32)
     if x.shape != (L,):
         raise RuntimeError("vector length error")
-    dp = None
-    if dither is not None:
-        if len(dither) != 32:
-            raise RuntimeError("the dither seed must be 32 bytes")
-        d = np.frombuffer(bytes(dither), np.uint8).copy()
-        dp = d.ctypes.data_as(_u8p)
-    out, clipped = np.empty(L, np.uint32), np.zeros(1, np.uint32)
-    _check(_lib.flm_client_encode_mask(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p),
-                                       sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), L, int(frac_bits), float(clip),
-                                       dp, out.ctypes.data_as(_u32p), clipped.ctypes.data_as(_u32p)))
+    keep, ptrs = [], []
+    for name, v in (("dither", dither), ("noise", noise)):
+        if v is None:
+            ptrs.append(None)
+            continue
+        if len(v) != 32:
+            raise RuntimeError("the %s seed must be 32 bytes" % name)
+        keep.append(np.frombuffer(bytes(v), np.uint8).copy())
+        ptrs.append(keep[-1].ctypes.data_as(_u8p))
+    out, clipped = np.empty(-(-L // pack), np.uint32), np.zeros(1, np.uint32)
+    _check(fn(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p), sd.ctypes.data_as(_u8p),
+              sg.ctypes.data_as(_i8p), L, int(frac_bits), float(clip), *codec(*ptrs), out.ctypes.data_as(_u32p),
+              clipped.ctypes.data_as(_u32p)))
     return out, int(clipped[0])
+
+
+def client_encode_mask(seeds, signs, L, x, frac_bits, clip, dither=None):
+    """client_mask for a float32 update x ("For machine learning, replace it with model weights",
+    SA_ClientAgent.py:300-304): encode(x) + sum_k signs[k] * PRG(seeds[k]) with the fixed-point encoding
+    (clip to +-clip, frac_bits fractional bits; nearest-even, or stochastic with a 32-byte dither seed) fused
+    into the masking of SA_ClientAgent.py:304-324.  Returns (uint32[L], number of clipped elements)."""
+    return _encode_mask(_lib.flm_client_encode_mask, lambda d, z: (d,), seeds, signs, L, x, frac_bits, clip, 1, dither)
 
 
 def decode_sum(total, frac_bits, count=1):
@@ -407,25 +416,10 @@ def client_encode_pack_mask(seeds, signs, L, x, frac_bits, clip, pack, dither=No
     """client_encode_mask with `pack` parameters per ring word ("replace it with model weights",
     SA_ClientAgent.py:300-304, masked as :304-324): the VECTOR body is ceil(L / pack) words, field j of word l'
     holding encode(x[pack l' + j]) + ceil(clip 2^frac_bits).  Returns (uint32[ceil(L / pack)], clipped elements)."""
-    seg = np.array([0, len(seeds)], np.int64)
-    sd, sg, K = _seed_arrays(seeds, signs)
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    if x.shape != (L,):
-        raise RuntimeError("vector length error")
     if pack not in (2, 4):
         raise RuntimeError("pack must be 2 or 4")
-    dp = None
-    if dither is not None:
-        if len(dither) != 32:
-            raise RuntimeError("the dither seed must be 32 bytes")
-        d = np.frombuffer(bytes(dither), np.uint8).copy()
-        dp = d.ctypes.data_as(_u8p)
-    out, clipped = np.empty(-(-L // pack), np.uint32), np.zeros(1, np.uint32)
-    _check(_lib.flm_client_encode_pack_mask(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p),
-                                            sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), L, int(frac_bits),
-                                            float(clip), int(pack), dp, out.ctypes.data_as(_u32p),
-                                            clipped.ctypes.data_as(_u32p)))
-    return out, int(clipped[0])
+    return _encode_mask(_lib.flm_client_encode_pack_mask, lambda d, z: (int(pack), d), seeds, signs, L, x, frac_bits, clip,
+                        pack, dither)
 
 
 def decode_unpack(total, L, frac_bits, clip, pack, count=1, noise_bits=0):
@@ -438,12 +432,8 @@ def decode_unpack(total, L, frac_bits, clip, pack, count=1, noise_bits=0):
     if total.shape != (-(-L // pack),):
         raise RuntimeError("vector length error")
     out = np.empty(L, np.float32)
-    if noise_bits != 0:
-        _check(_lib.flm_decode_unpack_noise(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip),
-                                            int(pack), int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
-        return out
-    _check(_lib.flm_decode_unpack(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip), int(pack),
-                                  int(count), out.ctypes.data_as(_f32p)))
+    _check(_lib.flm_decode_unpack_noise(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip),
+                                        int(pack), int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
     return out
 
 
@@ -462,29 +452,10 @@ def client_encode_noise_mask(seeds, signs, L, x, frac_bits, clip, pack=1, dither
     noise of agent/examples/crypto/PPFL_ClientAgent.py:219-221, 274-285): every parameter's quantised value gets
     (heads of noise_bits fair coins of PRG(noise)) - noise_bits / 2.  noise: 32 secret bytes, fresh per iteration.
     Turning noise_bits into an (epsilon, delta) is the caller's business.  Returns (uint32 words, clipped elements)."""
-    seg = np.array([0, len(seeds)], np.int64)
-    sd, sg, K = _seed_arrays(seeds, signs)
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    if x.shape != (L,):
-        raise RuntimeError("vector length error")
     if pack not in (1, 2, 4):
         raise RuntimeError("pack must be 1, 2 or 4")
-    keep = []
-    ptrs = []
-    for name, v in (("dither", dither), ("noise", noise)):
-        if v is None:
-            ptrs.append(None)
-            continue
-        if len(v) != 32:
-            raise RuntimeError("the %s seed must be 32 bytes" % name)
-        keep.append(np.frombuffer(bytes(v), np.uint8).copy())
-        ptrs.append(keep[-1].ctypes.data_as(_u8p))
-    out, clipped = np.empty(-(-L // pack), np.uint32), np.zeros(1, np.uint32)
-    _check(_lib.flm_client_encode_noise_mask(_context(), x.ctypes.data_as(_f32p), 1, seg.ctypes.data_as(_i64p),
-                                             sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), L, int(frac_bits),
-                                             float(clip), int(pack), ptrs[0], int(noise_bits), ptrs[1],
-                                             out.ctypes.data_as(_u32p), clipped.ctypes.data_as(_u32p)))
-    return out, int(clipped[0])
+    return _encode_mask(_lib.flm_client_encode_noise_mask, lambda d, z: (int(pack), d, int(noise_bits), z), seeds, signs, L,
+                        x, frac_bits, clip, pack, dither, noise)
 
 
 class VectorStore:
@@ -553,14 +524,9 @@ class VectorStore:
         client_encode_pack_mask; noise_bits > 0: of client_encode_noise_mask)."""
         sd, sg, K = _seed_arrays(seeds, signs)
         out = np.empty(int(L_params), np.float32)
-        if noise_bits != 0:
-            self._check(_lib.flm_store_unmask_unpack_noise_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
-                                                               int(L_params), int(frac_bits), float(clip), int(pack),
-                                                               int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
-            return out
-        self._check(_lib.flm_store_unmask_unpack_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
-                                                     int(L_params), int(frac_bits), float(clip), int(pack), int(count),
-                                                     out.ctypes.data_as(_f32p)))
+        self._check(_lib.flm_store_unmask_unpack_noise_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
+                                                           int(L_params), int(frac_bits), float(clip), int(pack),
+                                                           int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
         return out
 
     def reset(self):

@@ -1,6 +1,6 @@
 """The distributed-DP binomial noise of the float codec (include/flamingo_hip.h) restated in
 numpy on top of tests/codec_cases.py and tests/pack_cases.py, and the case lists of its tests.  No test functions:
-the premises are checked without a GPU by tests/test_dp_cpu.py, the kernels (encode_noise_mask_kernel and the
+the premises are checked without a GPU by tests/test_dp_cpu.py, the kernels (encode_mask_kernel with noise and the
 packed decode with the noised bias) bit for bit against them by tests/test_dp_gpu.py.
 
 * draws / noise_words / noise restate the mechanism: b = noise_bits fair coins per parameter and client,

@@ -1,6 +1,6 @@
 """The packed fixed-point codec (include/flamingo_hip.h) restated in numpy on top of
 tests/codec_cases.py, and the case lists of its tests.  No test functions: the premises of the lists are checked
-without a GPU by tests/test_pack_cpu.py, the kernels (encode_pack_mask_kernel, decode_unpack_kernel) bit for bit
+without a GPU by tests/test_pack_cpu.py, the kernels (encode_mask_kernel at P = 2, 4, decode_unpack_kernel) bit for bit
 against them by tests/test_pack_gpu.py.
 
 * bias / headroom_ok / encode_packed / decode_packed / masked_packed restate the codec: P = 2 or 4 fields of

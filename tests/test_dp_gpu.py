@@ -1,10 +1,12 @@
-"""encode_noise_mask_kernel and the noise-aware decodes, bit for bit against the numpy restatement of the binomial
+"""encode_mask_kernel's noise and the noise-aware decodes, bit for bit against the numpy restatement of the binomial
 noise (tests/dp_cases.py): one batch of four clients with 0, 1, 5 and 14 seeds at every width, every b of the case
-list, three lengths and both roundings, host and device forms with poisoned padding and guards; noise off is the
-existing calls byte for byte; the refusals; whole rounds through flm_aggregate_unmask and the noise-aware decode,
-also through the store; the reference-side binding."""
+list, three lengths and both roundings, host and device forms with poisoned padding and guards; one batch of 0
+through 17 seeds across the boundaries of the unit dealing; noise off is the existing calls byte for byte; the
+refusals; whole rounds through flm_aggregate_unmask and the noise-aware decode, also through the store; the
+reference-side binding."""
 from __future__ import annotations
 
+import functools
 import hashlib
 import importlib.util
 import os
@@ -65,6 +67,64 @@ def test_batch_matches_the_restatement(eng, P, f, c, b):
                 assert np.array_equal(o[:, :Lw], want), (L, pad)
                 assert np.all(o[:, Lw:] == POISON)                              # guard words untouched
                 assert np.array_equal(clt.cpu().numpy().view(np.uint32), want_cl)
+
+
+# ------------------------------------------------------------------ the dealing boundaries
+DEAL_CLIENTS = 18                                   # client i has i seeds, 0 through 17
+DEAL_BITS = (0, 32, 64)                             # 0, P and 2 P noise units in front of the seeds
+
+
+def _deal_params(P):
+    return (16, 4.0) if P == 1 else PC.pack_params(P)       # P = 4: (2, 1.0), the one pair its fields admit
+
+
+def _deal_cases():
+    return [(P, st, b) for P in (1, 2, 4) for st in (False, True) for b in DEAL_BITS
+            if D.headroom_ok(*_deal_params(P), P, b, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def _deal_batch(P):
+    """The inputs of one width, built once: L = 1024 P + 1 parameters are two word tiles, the second of one word,
+    whose upper fields (P > 1) lie past L."""
+    f, c = _deal_params(P)
+    L = 1024 * P + 1
+    rng = np.random.default_rng(4100 + P)
+    counts = np.arange(DEAL_CLIENTS)
+    seeds = rng.integers(0, 256, size=(int(counts.sum()), 32), dtype=np.uint8)
+    signs = rng.choice(np.array([-1, 1], np.int8), size=int(counts.sum()))
+    seg = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    xs = np.stack([K.random_row(L, c, 4200 + 50 * P + i, wild=True) for i in range(DEAL_CLIENTS)])
+    dithers = [hashlib.sha256(b"dp deal dither %d %d" % (P, i)).digest() for i in range(DEAL_CLIENTS)]
+    noises = [D.seed(4300 + 100 * P + i) for i in range(DEAL_CLIENTS)]
+    return f, c, L, xs, seg, seeds, signs, dithers, noises
+
+
+@pytest.mark.parametrize("P,stochastic,b", _deal_cases())
+def test_dealing_boundaries(eng, P, stochastic, b):
+    """The unit list is dealt in threes up to unit 3 E (E = P stochastic, 1 nearest: 3, 6 or 12) and in fours from
+    there, and with noise the P ceil(b / 32) noise units come first: with 0 through 17 seeds and b = 0, 32, 64 the
+    change of step falls inside the noise units, on the first seed and among the seeds, and every wave's share ends
+    before, on and after it.  Every word, the clipped counts and the guard words, against the restatement."""
+    import torch
+    f, c, L, xs, seg, seeds, signs, dithers, noises = _deal_batch(P)
+    N, Lw = DEAL_CLIENTS, -(-L // P)
+    assert Lw == 1025 and int(seg[-1]) == 153
+    d = dithers if stochastic else None
+    want, want_cl = D.batch_rows(xs, seg, seeds, signs, f, c, P, d, noises, b)
+    XP, OP = (L + 3) // 4 * 4 + 16, (Lw + 3) // 4 * 4 + 32
+    xp = np.full((N, XP), np.nan, np.float32)
+    xp[:, :L] = xs
+    out = torch.full((N, OP), POISON - (1 << 32), dtype=torch.int32, device="cuda")
+    clt = torch.full((N,), 77, dtype=torch.int32, device="cuda")
+    eng.client_encode_noise_mask_dev(seg, torch.from_numpy(seeds).cuda(), signs, out, L, torch.from_numpy(xp).cuda(), f, c, P,
+                                     dither_dev=torch.from_numpy(_u8(dithers)).cuda() if stochastic else None, noise_bits=b,
+                                     noise_dev=torch.from_numpy(_u8(noises)).cuda(), clipped=clt)
+    o = out.cpu().numpy().view(np.uint32)
+    bad = [i for i in range(N) if not np.array_equal(o[i, :Lw], want[i])]
+    assert not bad, ("clients (= seed counts) whose rows differ", bad)
+    assert np.all(o[:, Lw:] == POISON)                                      # guard words untouched
+    assert want_cl.sum() > 0 and np.array_equal(clt.cpu().numpy().view(np.uint32), want_cl)
 
 
 # ------------------------------------------------------------------ noise off

@@ -1,4 +1,4 @@
-"""encode_pack_mask_kernel and decode_unpack_kernel, bit for bit against the numpy restatement of the packed codec
+"""encode_mask_kernel at P = 2, 4 and decode_unpack_kernel, bit for bit against the numpy restatement of the packed codec
 (tests/pack_cases.py), for 2 and 4 parameters per ring word, nearest and stochastic: every row-tail, word-tail and
 tile shape, clients with 0..40 seeds mixed in one batch, the edge values in every field, the stochastic threshold
 parameters (the dither stream is indexed by parameter), pitched device rows with poisoned padding and guards, the

@@ -130,32 +130,41 @@ static void check_round_lists() {
         for (size_t N : {size_t(1), size_t(3)})
             for (size_t K : {size_t(0), size_t(3)})
                 for (int opt = 0; opt < 4; ++opt) {
-                    through_bounce(client_encode_mask_args(N, K, L, opt & 1, opt & 2));
+                    through_bounce(client_encode_mask_args(N, K, L, L, opt & 1, false, opt & 2));
                     for (int pack : {2, 4}) {
-                        through_bounce(client_encode_pack_mask_args(N, K, L, packed_words(L, pack), opt & 1, opt & 2));
+                        through_bounce(client_encode_mask_args(N, K, L, packed_words(L, pack), opt & 1, false, opt & 2));
                         if (!opt) through_bounce(decode_unpack_args(L, packed_words(L, pack)));
                     }
                     for (int pack : {1, 2, 4})
-                        through_bounce(client_encode_noise_mask_args(N, K, L, packed_words(L, pack), opt & 1, opt & 2));
+                        through_bounce(client_encode_mask_args(N, K, L, packed_words(L, pack), opt & 1, true, opt & 2));
                     if (opt < 2) through_bounce(client_mask_args(N, K, L, opt & 1));
                     if (opt < 2) through_bounce(aggregate_unmask_args(K, L, opt & 1));
                     if (opt) continue;
                     through_bounce(prg_expand_args(K, L));
                     through_bounce(mask_accumulate_args(K, L));
-                    through_bounce(decode_sum_args(L));
+                    through_bounce(decode_unpack_args(L, L));
                     through_bounce(chacha20_xor_args(L));
                 }
     // rows travel at the host forms' pitch; what is optional is exactly what the flags name
-    const ArgList m = client_mask_args(3, 7, 5, false), e = client_encode_mask_args(3, 7, 5, false, true);
+    const ArgList m = client_mask_args(3, 7, 5, false), e = client_encode_mask_args(3, 7, 5, 5, false, false, true);
     CHECK(host_row_pitch(1) == 256 && host_row_pitch(64) == 256 && host_row_pitch(65) == 512);
     CHECK(m.n == 4 && !m.a[0].present && m.a[3].is_out && m.a[3].in_place && m.a[3].rows == 3 && m.a[3].width == 20 &&
           m.a[3].h_pitch == 20 && m.a[3].d_pitch == 256 && m.a[1].width == 7 * 32 && m.a[2].width == 7);
-    CHECK(e.n == 5 && e.a[0].present && !e.a[2].present && e.a[4].present && e.a[4].is_out && e.a[4].width == 12);
+    CHECK(e.n == 6 && e.a[0].present && !e.a[2].present && !e.a[3].present && e.a[5].present && e.a[5].is_out && e.a[5].width == 12);
     const ArgList z = client_mask_args(3, 0, 5, true);  // K = 0: seeds and signs declared, no bytes
     CHECK(z.a[1].present && z.a[2].present && !z.a[1].width && !z.a[2].width);
     CHECK(!aggregate_unmask_args(3, 5, false).a[2].present && aggregate_unmask_args(3, 5, true).a[2].width == 20);
     const ArgList acc = mask_accumulate_args(3, 1025);  // the rows first, the seeds after
     CHECK(acc.a[0].slot == rows && acc.a[1].slot == out && acc.a[1].is_out && acc.a[2].slot == seeds && acc.a[3].slot == signs);
+}
+
+// The codec's one rule as the three families of entry points call it: unpacked, packed (pack = 1 not admitted), noised.
+static const char *unpacked_rule(int f, float clip, int64_t n, bool *range) { return codec_error(f, clip, 1, true, 0, n, 0, range); }
+static const char *packed_rule(int f, float clip, int pack, int64_t n, bool *range, uint32_t *B) {
+    return codec_error(f, clip, pack, false, 0, n, 0, range, B);
+}
+static const char *noise_rule(int f, float clip, int pack, int b, int64_t n, uint64_t L, bool *range, uint32_t *B, uint32_t *Bn) {
+    return codec_error(f, clip, pack, true, b, n, L, range, B, Bn);
 }
 
 // The round path's rules at their edges.
@@ -187,50 +196,51 @@ static void check_round_rules() {
     CHECK(std::strstr(align16_error({buf + 8}), "16-byte aligned"));
     // frac_bits 0, 30, 31; the clip; n ceil(clip 2^f) exactly 2^31 - 1 and one more
     bool range = true;
-    CHECK(!codec_error(0, 1.0f, 1, &range) && !range && !codec_error(30, 1.0f, 1, &range) && !range);
-    CHECK(codec_error(31, 1.0f, 1, &range) && !range && codec_error(-1, 1.0f, 1, &range) && !range);
-    CHECK(codec_error(16, 0.0f, 1, &range) && !range && codec_error(16, -1.0f, 1, &range) && !range);
-    CHECK(codec_error(16, INFINITY, 1, &range) && !range && codec_error(16, NAN, 1, &range) && !range);
-    CHECK(codec_error(16, 1.0f, 0, &range) && !range);
-    CHECK(!codec_error(0, 1.0f, 2147483647, &range) && !range);                       // n x 1 = 2^31 - 1
-    CHECK(codec_error(0, 1.0f, 2147483648ll, &range) && range);                       // ... and one more
-    CHECK(!codec_error(16, 0.5f, 65535, &range) && !range);                           // 65535 x 2^15 < 2^31 - 1
-    CHECK(codec_error(16, 0.5f, 65536, &range) && range);                             // 2^31
-    CHECK(!codec_error(4, 1.01f, 126322567, &range) && codec_error(4, 1.01f, 126322568, &range) && range);  // m = 17
-    CHECK(!codec_error(30, 1.9999999f, 1, &range) && codec_error(30, 2.0f, 1, &range) && range);  // m alone past 2^31 - 1
+    CHECK(!unpacked_rule(0, 1.0f, 1, &range) && !range && !unpacked_rule(30, 1.0f, 1, &range) && !range);
+    CHECK(unpacked_rule(31, 1.0f, 1, &range) && !range && unpacked_rule(-1, 1.0f, 1, &range) && !range);
+    CHECK(unpacked_rule(16, 0.0f, 1, &range) && !range && unpacked_rule(16, -1.0f, 1, &range) && !range);
+    CHECK(unpacked_rule(16, INFINITY, 1, &range) && !range && unpacked_rule(16, NAN, 1, &range) && !range);
+    CHECK(unpacked_rule(16, 1.0f, 0, &range) && !range);
+    CHECK(!unpacked_rule(0, 1.0f, 2147483647, &range) && !range);                       // n x 1 = 2^31 - 1
+    CHECK(unpacked_rule(0, 1.0f, 2147483648ll, &range) && range);                       // ... and one more
+    CHECK(!unpacked_rule(16, 0.5f, 65535, &range) && !range);                           // 65535 x 2^15 < 2^31 - 1
+    CHECK(unpacked_rule(16, 0.5f, 65536, &range) && range);                             // 2^31
+    CHECK(!unpacked_rule(4, 1.01f, 126322567, &range) && unpacked_rule(4, 1.01f, 126322568, &range) && range);  // m = 17
+    CHECK(!unpacked_rule(30, 1.9999999f, 1, &range) && unpacked_rule(30, 2.0f, 1, &range) && range);  // m alone past 2^31 - 1
     // the packed codec: pack, then the unpacked rule's refusals, then n 2B <= 2^W - 1 at its edges
     uint32_t B = 0;
-    for (int pack : {0, 1, 3, 8, -2}) CHECK(packed_codec_error(7, 1.0f, pack, 1, &range, &B) && !range);
-    CHECK(packed_codec_error(31, 1.0f, 2, 1, &range, &B) && !range && packed_codec_error(7, 0.0f, 2, 1, &range, &B) && !range);
-    CHECK(packed_codec_error(7, 1.0f, 2, 0, &range, &B) && !range);
-    CHECK(!packed_codec_error(7, 1.0f, 2, 255, &range, &B) && !range && B == 128);
-    CHECK(packed_codec_error(7, 1.0f, 2, 256, &range, &B) && range);
-    CHECK(!packed_codec_error(4, 1.0f, 2, 2047, &range, &B) && B == 16 && packed_codec_error(4, 1.0f, 2, 2048, &range, &B) && range);
-    CHECK(!packed_codec_error(2, 1.0f, 4, 31, &range, &B) && B == 4 && packed_codec_error(2, 1.0f, 4, 32, &range, &B) && range);
-    CHECK(!packed_codec_error(0, 1.0f, 4, 127, &range, &B) && B == 1 && packed_codec_error(0, 1.0f, 4, 128, &range, &B) && range);
-    CHECK(!packed_codec_error(6, 1.9f, 4, 1, &range, &B) && B == 122);                 // 244 <= 255
-    CHECK(packed_codec_error(7, 1.0f, 4, 1, &range, &B) && range);                      // 2B = 256 alone past 2^8 - 1
-    CHECK(packed_codec_error(30, 2.0f, 2, 1, &range, &B) && range);                     // the unpacked rule's refusal first
+    for (int pack : {0, 1, 3, 8, -2}) CHECK(packed_rule(7, 1.0f, pack, 1, &range, &B) && !range);
+    CHECK(packed_rule(31, 1.0f, 2, 1, &range, &B) && !range && packed_rule(7, 0.0f, 2, 1, &range, &B) && !range);
+    CHECK(packed_rule(7, 1.0f, 2, 0, &range, &B) && !range);
+    CHECK(!packed_rule(7, 1.0f, 2, 255, &range, &B) && !range && B == 128);
+    CHECK(packed_rule(7, 1.0f, 2, 256, &range, &B) && range);
+    CHECK(!packed_rule(4, 1.0f, 2, 2047, &range, &B) && B == 16 && packed_rule(4, 1.0f, 2, 2048, &range, &B) && range);
+    CHECK(!packed_rule(2, 1.0f, 4, 31, &range, &B) && B == 4 && packed_rule(2, 1.0f, 4, 32, &range, &B) && range);
+    CHECK(!packed_rule(0, 1.0f, 4, 127, &range, &B) && B == 1 && packed_rule(0, 1.0f, 4, 128, &range, &B) && range);
+    CHECK(!packed_rule(6, 1.9f, 4, 1, &range, &B) && B == 122);                 // 244 <= 255
+    CHECK(packed_rule(7, 1.0f, 4, 1, &range, &B) && range);                      // 2B = 256 alone past 2^8 - 1
+    CHECK(packed_rule(30, 2.0f, 2, 1, &range, &B) && range);                     // the unpacked rule's refusal first
     CHECK(packed_words(1, 2) == 1 && packed_words(2, 2) == 1 && packed_words(3, 2) == 2 && packed_words(5, 4) == 2 &&
           packed_words(0, 4) == 0);
-    const ArgList pe = client_encode_pack_mask_args(3, 7, 5, 2, false, true), pd = decode_unpack_args(5, 2);
-    CHECK(pe.n == 5 && pe.a[0].width == 20 && pe.a[3].width == 8 && pe.a[3].is_out && pe.a[3].in_place && !pe.a[2].present);
+    const ArgList pe = client_encode_mask_args(3, 7, 5, 2, false, false, true), pd = decode_unpack_args(5, 2);
+    CHECK(pe.n == 6 && pe.a[0].width == 20 && pe.a[4].width == 8 && pe.a[4].is_out && pe.a[4].in_place && !pe.a[2].present &&
+          !pe.a[3].present);
     CHECK(pd.n == 2 && pd.a[0].width == 8 && pd.a[1].width == 20 && pd.a[1].is_out);
     // the noised codec: pack and noise_bits, then the rule of that pack, then the worst case with B_n = B + b / 2
     uint32_t Bn = 0;
-    for (int b : {-2, 1, 31, 1026}) CHECK(noise_codec_error(4, 1.0f, 2, b, 1, 0, &range, &B, &Bn) && !range);
-    for (int pack : {0, 3, 8}) CHECK(noise_codec_error(4, 1.0f, pack, 2, 1, 0, &range, &B, &Bn) && !range);
-    CHECK(!noise_codec_error(4, 1.0f, 2, 30, 1057, 0, &range, &B, &Bn) && B == 16 && Bn == 31);
-    CHECK(noise_codec_error(4, 1.0f, 2, 30, 1058, 0, &range, &B, &Bn) && range);
-    CHECK(!noise_codec_error(2, 1.0f, 4, 2, 25, 0, &range, &B, &Bn) && Bn == 5 && noise_codec_error(2, 1.0f, 4, 2, 26, 0, &range, &B, &Bn) && range);
-    CHECK(!noise_codec_error(7, 1.0f, 2, 0, 255, 0, &range, &B, &Bn) && noise_codec_error(7, 1.0f, 2, 2, 255, 0, &range, &B, &Bn) && range);
-    CHECK(!noise_codec_error(16, 4.0f, 1, 1024, 8176, 0, &range, &B, &Bn) && Bn == 262656);  // 8176 * 262656 <= 2^31 - 1
-    CHECK(noise_codec_error(16, 4.0f, 1, 1024, 8177, 0, &range, &B, &Bn) && range);
-    CHECK(!noise_codec_error(16, 4.0f, 1, 0, 8177, 0, &range, &B, &Bn));                     // without noise: 8191 fit
-    CHECK(!noise_codec_error(4, 1.0f, 1, 64, 1, 1ull << 35, &range, &B, &Bn));              // 2 * 2^31 blocks
-    CHECK(noise_codec_error(4, 1.0f, 1, 64, 1, (1ull << 35) + 1, &range, &B, &Bn) && range);
-    CHECK(!noise_codec_error(4, 1.0f, 1, 0, 1, ~0ull, &range, &B, &Bn));                    // no noise: no length rule
-    const ArgList ne = client_encode_noise_mask_args(3, 7, 5, 2, false, true);
+    for (int b : {-2, 1, 31, 1026}) CHECK(noise_rule(4, 1.0f, 2, b, 1, 0, &range, &B, &Bn) && !range);
+    for (int pack : {0, 3, 8}) CHECK(noise_rule(4, 1.0f, pack, 2, 1, 0, &range, &B, &Bn) && !range);
+    CHECK(!noise_rule(4, 1.0f, 2, 30, 1057, 0, &range, &B, &Bn) && B == 16 && Bn == 31);
+    CHECK(noise_rule(4, 1.0f, 2, 30, 1058, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_rule(2, 1.0f, 4, 2, 25, 0, &range, &B, &Bn) && Bn == 5 && noise_rule(2, 1.0f, 4, 2, 26, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_rule(7, 1.0f, 2, 0, 255, 0, &range, &B, &Bn) && noise_rule(7, 1.0f, 2, 2, 255, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_rule(16, 4.0f, 1, 1024, 8176, 0, &range, &B, &Bn) && Bn == 262656);  // 8176 * 262656 <= 2^31 - 1
+    CHECK(noise_rule(16, 4.0f, 1, 1024, 8177, 0, &range, &B, &Bn) && range);
+    CHECK(!noise_rule(16, 4.0f, 1, 0, 8177, 0, &range, &B, &Bn));                     // without noise: 8191 fit
+    CHECK(!noise_rule(4, 1.0f, 1, 64, 1, 1ull << 35, &range, &B, &Bn));              // 2 * 2^31 blocks
+    CHECK(noise_rule(4, 1.0f, 1, 64, 1, (1ull << 35) + 1, &range, &B, &Bn) && range);
+    CHECK(!noise_rule(4, 1.0f, 1, 0, 1, ~0ull, &range, &B, &Bn));                    // no noise: no length rule
+    const ArgList ne = client_encode_mask_args(3, 7, 5, 2, false, true, true);
     CHECK(ne.n == 6 && ne.a[3].present && ne.a[3].width == 96 && !ne.a[2].present && ne.a[4].is_out && ne.a[4].width == 8);
     CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
     CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));

@@ -2,9 +2,9 @@
 
 Client-batch masking of float32 input at tools/pack_bench.py's shapes (c5: N = 1024 clients x 2^20 parameters,
 S = 25 seeds each; agent: N = 1), for b = 0, 32, 64, 256 noise bits and P = 1, 2, 4 parameters per ring word,
-nearest-even and stochastic, all through flm_client_encode_noise_mask_dev.  b = 0 dispatches the kernels there
-were (encode_mask_kernel, encode_pack_mask_kernel): the yardstick, timed in the same process.  b > 0 runs
-encode_noise_mask_kernel<P, STOCHASTIC>, which adds P ceil(b / 32) ChaCha blocks per word tile to the S seed blocks
+nearest-even and stochastic, all through flm_client_encode_noise_mask_dev.  b = 0 dispatches the instantiations
+without noise (encode_mask_kernel<P, STOCHASTIC, false>): the yardstick, timed in the same process.  b > 0 runs
+encode_mask_kernel<P, STOCHASTIC, true>, which adds P ceil(b / 32) ChaCha blocks per word tile to the S seed blocks
 and the E encoding blocks (E = P stochastic, 1 nearest: DESIGN.md section 5), so the block-count model of the ratio
 is (S + E + P m) / (S + E).  Parameters: (f, c) = (7, 1) for P = 1 and 2, (2, 1) for P = 4; P = 4 has no headroom
 for b = 256 at any (f, c) (2 (B + 128) > 255), so that leg is left out.
