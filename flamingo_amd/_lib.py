@@ -60,6 +60,9 @@ SIGNATURES = {
                                                 _vp, _int, _vp, _vp, _sz, _vp, _vp]),
     "flm_decode_unpack_noise": (_int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _f32p]),
     "flm_decode_unpack_noise_dev": (_int, [_vp, _vp, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _vp, _vp]),
+    "flm_rotate_check": (_int, [_u64, _int, ctypes.POINTER(_u64)]),
+    "flm_rotate_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _int, _vp, _sz, _vp, _vp]),
+    "flm_rotate": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, _int, _f32p, _u32p]),
     "flm_prg_expand_dev": (_int, [_vp, _vp, _int, _sz, _u64, _vp, _sz, _vp]),
     "flm_check_signs": (_int, [_vp, ctypes.POINTER(_int)]),
     "flm_last_plan": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),

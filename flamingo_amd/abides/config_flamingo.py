@@ -83,6 +83,11 @@ def parse(argv):
     # --float_inputs, and headroom for n (ceil(CLIP 2^F) + BITS / 2); turning BITS into an (epsilon, delta) is the
     # caller's business; off by default
     ap.add_argument("--dp_noise", type=int, default=0, metavar="BITS")
+    # every client rotates its float update by a randomised Hadamard transform in blocks of 2^LOG2BLOCK parameters
+    # (4..12) before the encode, under a public key per iteration, and the server rotates the decoded mean back
+    # (protocol.configure(rotate=...)): CLIP then bounds the rotated coordinates, about ||x||_2 / 2^(LOG2BLOCK / 2)
+    # per block where it had to cover the largest coordinate; needs --float_inputs; off by default
+    ap.add_argument("--rotate", type=int, default=0, metavar="LOG2BLOCK")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -170,7 +175,7 @@ def _run(args):
                     gpu_verify=True if args.gpu_verify else None,
                     authenticate_shares=True if args.authenticate_shares else None,
                     dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs),
-                    dp_noise=args.dp_noise)
+                    dp_noise=args.dp_noise, rotate=args.rotate)
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -238,9 +243,13 @@ def _run(args):
                 b, f = param.codec_noise_bits(), param.codec()[0]
                 noised = (f", noise of {b} coins: standard deviation of the difference {float(np.std(diff)):.3e}, "
                           f"expected sqrt(|U| b) / (2 |U| 2^f) = {np.sqrt(u * b) / (2.0 * u * 2.0 ** f):.3e}")
-            print(f"    iteration {it}: float inputs {param.codec()}{packed}: largest |final_mean - mean of the clients' floats| = "
+            rotated = nonfinite = ""
+            if param.rotate_bits():
+                rotated = f", rotated in blocks of 2^{param.rotate_bits()}"
+                nonfinite = f", {sum(agents[i].nonfinite for i in server.online_ids[it])} non-finite"
+            print(f"    iteration {it}: float inputs {param.codec()}{packed}{rotated}: largest |final_mean - mean of the clients' floats| = "
                   f"{float(np.max(np.abs(diff))):.3e}{noised}, "
-                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped")
+                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped{nonfinite}")
     print()
     results["server"] = server
     results["clients"] = agents[:n]

@@ -94,6 +94,8 @@ class SA_ClientAgent(Agent):
         self.offline_iterations = set(offline_iterations)
         self.input_vector = None     # None -> all ones (:304); with float inputs: a synthetic float32 update
         self.clipped = 0             # float inputs: elements of the last update that were clipped
+        self.nonfinite = 0           # ... and, with the rotation on, its non-finite elements (clipped then counts
+                                     # rotated coordinates)
         self.dither_seed = None      # float inputs, stochastic rounding: the last iteration's dither seed
         self.noise_seed = None       # float inputs with --dp_noise: the last iteration's noise seed
         pki = param.pki(num_clients)
@@ -235,23 +237,28 @@ class SA_ClientAgent(Agent):
             frac_bits, clip, rounding = codec
             if self.input_vector is None:
                 from ...synthetic import float_update
-                self.input_vector = float_update(self.id, self.vector_len, clip)
+                self.input_vector = float_update(self.id, self.vector_len, clip, param.rotate_bits())
             x = np.asarray(self.input_vector, np.float32)[None, :]
+            L = self.vector_len
+            if param.rotate_bits():   # the iteration's public rotation in front of the encode; the clip bounds its output
+                x, nonfinite = param.engine().rotate(x, param.rotation_key(self.current_iteration), param.rotate_bits(),
+                                                     return_nonfinite=True)
+                L, self.nonfinite = param.rotated_len(), int(nonfinite[0])
             dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
                 if rounding == "stochastic" else None
             seg = np.array([0, len(seeds)], np.int64)
             noise_bits = param.codec_noise_bits()
             if noise_bits:   # distributed DP: the noise seed is drawn after every other draw, the dither seed included
                 self.noise_seed = bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))
-                vec, clipped = param.engine().client_encode_noise_mask(seg, seeds, signs, self.vector_len, x, frac_bits,
+                vec, clipped = param.engine().client_encode_noise_mask(seg, seeds, signs, L, x, frac_bits,
                                                                        clip, param.codec_pack(), dither=dither,
                                                                        noise_bits=noise_bits, noise=[self.noise_seed],
                                                                        return_clipped=True)
             elif param.codec_pack() == 1:
-                vec, clipped = param.engine().client_encode_mask(seg, seeds, signs, self.vector_len, x, frac_bits, clip,
+                vec, clipped = param.engine().client_encode_mask(seg, seeds, signs, L, x, frac_bits, clip,
                                                                  dither=dither, return_clipped=True)
             else:   # packed: the body is param.ring_len() words, the masks with it
-                vec, clipped = param.engine().client_encode_pack_mask(seg, seeds, signs, self.vector_len, x, frac_bits,
+                vec, clipped = param.engine().client_encode_pack_mask(seg, seeds, signs, L, x, frac_bits,
                                                                       clip, param.codec_pack(), dither=dither,
                                                                       return_clipped=True)
             vec, self.clipped = vec[0], int(clipped[0])

@@ -75,23 +75,30 @@ _codec_pack: int = 1
 # (MaskEngine.client_encode_noise_mask); only the sum of the shares appears in what the server unmasks.  It needs
 # the float inputs.  Off by default, so a run sends what it always sent and draws what it always drew.
 _dp_noise: int = 0
+# Randomised block Hadamard rotation (config_flamingo's --rotate LOG2BLOCK): every client rotates its float update
+# in blocks of 2^LOG2BLOCK parameters under the iteration's public key before the encode (MaskEngine.rotate), the
+# server rotates the decoded mean back; the clip then bounds rotated coordinates.  It needs the float inputs.  Off
+# by default, so a run sends what it always sent and draws what it always drew.
+_rotate: int = 0
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
               authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None,
-              dp_noise: int | None = None):
+              dp_noise: int | None = None, rotate: int | None = None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
     "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
     many parameters into a ring word, False turns them off, None leaves them as they are.  dp_noise: the coin
     flips per parameter of every client's binomial noise share (even, 2..1024; 0 turns it off, None leaves it as
-    it is); it needs the float inputs, and turning those off turns it off."""
+    it is); it needs the float inputs, and turning those off turns it off.  rotate: log2 of the block of the randomised
+    Hadamard rotation in front of the codec (4..12; 0 turns it off, None leaves it as it is); it needs the float
+    inputs, and turning those off turns it off."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise
+    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate
     if codec is not None:
         if codec is False:
-            _codec, _codec_pack, _dp_noise = None, 1, 0
+            _codec, _codec_pack, _dp_noise, _rotate = None, 1, 0, 0
         else:
             f, c, mode = codec[:3]
             pack = int(codec[3]) if len(codec) == 4 else 1
@@ -109,6 +116,13 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
         if b and _codec is None:
             raise ValueError("dp_noise needs the float inputs (codec=...)")
         _dp_noise = b
+    if rotate is not None:
+        h = int(rotate)
+        if h != 0 and not 4 <= h <= 12:
+            raise ValueError("rotate must be 0 or a log2 block size in 4..12")
+        if h and _codec is None:
+            raise ValueError("rotate needs the float inputs (codec=...)")
+        _rotate = h
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -289,9 +303,27 @@ def codec_noise_bits() -> int:
     return _dp_noise if _codec is not None else 0
 
 
+def rotate_bits() -> int:
+    """log2 of the rotation's block: 0 when the rotation is off (or the float inputs are)."""
+    return _rotate if _codec is not None else 0
+
+
+def rotated_len() -> int:
+    """Parameters the codec sees: vector_len, rounded up to whole blocks of the rotation when it is on."""
+    H = 1 << rotate_bits()
+    return -(-vector_len // H) * H
+
+
+def rotation_key(iteration: int) -> bytes:
+    """The iteration's public rotation key, the same for every client and the server:
+    SHA-256(b"flamingo rotation" || root_seed || iteration as 8 bytes little-endian)."""
+    import hashlib
+    return hashlib.sha256(b"flamingo rotation" + root_seed + int(iteration).to_bytes(8, "little")).digest()
+
+
 def ring_len() -> int:
-    """Words of a ring row (a VECTOR body, a mask, the sums): ceil(vector_len / codec_pack())."""
-    return -(-vector_len // codec_pack())
+    """Words of a ring row (a VECTOR body, a mask, the sums): ceil(rotated_len() / codec_pack())."""
+    return -(-rotated_len() // codec_pack())
 
 
 def dkg_on() -> bool:

@@ -88,7 +88,7 @@ class SA_ServiceAgent(Agent):
             # are named only when on, so an engine that offers the plain codec alone still serves a plain run
             kw = {"pack": param.codec_pack()} if param.codec_pack() != 1 else {}
             if param.codec_noise_bits():
-                kw.update(noise_bits=param.codec_noise_bits(), L=param.vector_len)
+                kw.update(noise_bits=param.codec_noise_bits(), L=param.rotated_len())
             param.engine().codec_check(param.codec()[0], param.codec()[1], n, **kw)
         self.online_counts = {}      # iteration -> |U|
         self.pairs_per_iteration = {}  # iteration -> D dropout pairs recovered
@@ -356,6 +356,9 @@ class SA_ServiceAgent(Agent):
                          + (f", {gpu:.3f} ms GPU" if gpu is not None else ""))
         if codec is not None and self.final_mean is None:
             self.final_mean = self._mean(count, param.engine(), "decode_sum", "decode_unpack", self.final_sum)
+        if codec is not None and param.rotate_bits():   # the mean of the rotated updates, rotated back
+            self.final_mean = param.engine().rotate(self.final_mean, param.rotation_key(self.current_iteration),
+                                                    param.rotate_bits(), inverse=True, L=self.vector_len)
         if codec is not None:
             self.means[self.current_iteration] = self.final_mean
             self.online_ids[self.current_iteration] = sorted(self.user_vectors)
@@ -368,12 +371,13 @@ class SA_ServiceAgent(Agent):
     def _mean(self, count, on, unpacked, packed, *head):
         """The final sum as the mean over `count` clients, by a method of `on` (the store, or the engine for a sum on
         the host): unpacked(*head, frac_bits, count) at pack 1 (in place), else packed(*head, L, frac_bits, clip, pack,
-        count), every device unpacking its word shard into its floats; with noise the bias carries noise_bits / 2."""
+        count), every device unpacking its word shard into its floats; with noise the bias carries noise_bits / 2.
+        L is param.rotated_len(): with the rotation on the codec's parameters are the rotated ones."""
         (frac_bits, clip), pack, noise_bits = param.codec()[:2], param.codec_pack(), param.codec_noise_bits()
         if pack == 1:
             return getattr(on, unpacked)(*head, frac_bits, count)
         kw = {"noise_bits": noise_bits} if noise_bits else {}
-        return getattr(on, packed)(*head, self.vector_len, frac_bits, clip, pack, count, **kw)
+        return getattr(on, packed)(*head, param.rotated_len(), frac_bits, clip, pack, count, **kw)
 
     def recordTime(self, startTime, categoryName):
         self.elapsed_time[categoryName] += pd.Timestamp("now") - startTime

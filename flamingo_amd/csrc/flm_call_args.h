@@ -145,6 +145,29 @@ inline const char *prg_expand_launch_error(int K, size_t L) {
     return prg_expand_units(K, L) > 0xFFFFFFFFull ? "more than 2^32 1024-slot units" : nullptr;
 }
 
+// flm_rotate_check, flm_rotate[_dev]: the randomised block Hadamard rotation's one rule.  Blocks of H = 2^log2_block
+// parameters, log2_block in 4..12 (a 4096-parameter tile of rotate_kernel holds whole blocks; below 16 a thread's 16
+// parameters would span blocks); a row of L > 0 parameters counts as *L_rot = round_up(L, H).  The sign of parameter l
+// is bit l % 32 of word l / 32 of PRG(key): L_rot / 32 words (rounded up) that must end at or below the PRG's 2^36
+// slots, else FLM_ERANGE (*range set) -- which also keeps round_up from wrapping.
+inline const char *rotate_error(uint64_t L, int log2_block, bool *range, uint64_t *L_rot) {
+    *range = false;
+    if (log2_block < 4 || log2_block > 12) return "log2_block outside 4..12";
+    if (L == 0) return "a row of no parameters";
+    *range = true;
+    if (L > (uint64_t(1) << 41) || !flm::plan::slot_range_ok(0, round_up(round_up(L, uint64_t(1) << log2_block), 32) / 32))
+        return "the sign stream of a row that long ends beyond 2^36 PRG slots";
+    *range = false;
+    *L_rot = round_up(L, uint64_t(1) << log2_block);
+    return nullptr;
+}
+// words of sign stream for a rotated row
+constexpr uint64_t rotate_sign_words(uint64_t L_rot) { return (L_rot + 31) / 32; }
+// rotate_kernel's one-dimensional grid of flm::rotate_groups workgroups
+inline const char *rotate_launch_error(uint64_t groups) {
+    return groups > 0x7fffffffull ? "more than 2^31 - 1 4096-parameter tiles" : nullptr;
+}
+
 // flm_aggregate_dev, flm_aggregate_unmask_dev: the rows, the mask window and its PRG slots, the output.
 // *range: the refusal is the slot range's (FLM_ERANGE).
 inline const char *aggregate_error(const void *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
@@ -347,6 +370,15 @@ inline ArgList client_encode_mask_args(size_t N, size_t K, size_t L, size_t Lw, 
 // sum (Lw words), out (L floats); Lw = L: the unpacked decode, which may then run in place
 inline ArgList decode_unpack_args(size_t L, size_t Lw) {
     return {{in_place(arg_in(Lw * 4, rows)), in_place(arg_out(L * 4, out))}, 2};
+}
+// flm_rotate: x (N rows of L_in floats), out (N rows of L_out floats), key, nonfinite; forward L_in = L and L_out =
+// L_rot, the inverse the other way round.  x and out in place as the decode's, rows at the in-place pitch of
+// round_up(width, 16) bytes, which is what rotate_kernel's 16-byte accesses need.  The sign words the key expands
+// to live in a buffer of the context that no list names (flm_ctx::rot_signs).
+inline ArgList rotate_args(size_t N, size_t L_in, size_t L_out, bool nonfinite) {
+    return {{in_place(pitched(arg_in(L_in * 4, rows), N, host_row_pitch(L_in))),
+             in_place(pitched(arg_out(L_out * 4, out), N, host_row_pitch(L_out))), arg_in(32, seeds),
+             arg_out(N * 4, bytes_out, nonfinite)}, 4};
 }
 // seeds, out (K rows)
 inline ArgList prg_expand_args(size_t K, size_t L) {

@@ -66,6 +66,15 @@ hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, fl
 // not d_sum; both 16-byte aligned
 hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int64_t count_bias, double denom, float *d_out,
                                 hipStream_t stream);
+// Randomised block Hadamard rotation (rotate_kernel): rows of L parameters taken as L_rot = round_up(L, 2^log2_block),
+// log2_block in 4..12; forward reads L floats a row (up to round_up(L, 4) of them, 16 bytes at a time) and writes L_rot,
+// inverse reads L_rot and writes L; d_sign_bits ceil(L_rot / 32) words; d_out may be d_x at equal pitches; d_nonfinite
+// (forward only) N words, zeroed by the caller, or NULL.  One workgroup per (row, 4096-parameter tile) of a
+// one-dimensional grid (rotate_groups(N, L_rot) of them, at most 2^31 - 1).
+uint64_t rotate_groups(int N, uint64_t L_rot);
+hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
+                         const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
+                         uint32_t *d_nonfinite, hipStream_t stream);
 uint32_t pair_units_count(int K, uint64_t L, uint32_t *n_tiles);
 hipError_t launch_pair_units(bool side, const SeedRec *d_recs, int K, uint32_t *d_dst, uint64_t L, uint32_t *d_ws,
                              int groups, hipStream_t stream);

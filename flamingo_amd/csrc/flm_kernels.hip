@@ -28,6 +28,9 @@
 //   * 1024-thread workgroups: 16 waves split an item's rows/seeds, partial
 //     sums are combined through LDS; tiles shared by several items are
 //     combined with u32 atomics (exact: integer adds commute).
+#include <cmath>
+#include <cstring>
+
 #include "flm_internal.h"
 
 namespace flm {
@@ -1257,6 +1260,171 @@ __global__ __launch_bounds__(256) void decode_unpack_kernel(const uint32_t *__re
     if (l < L) out[l] = unpack_field<P>(sum[l / P], (int)(l % P), cb, denom);
 }
 
+// ------------------------------------------------------------ randomised block Hadamard rotation
+// A float -> float step in front of the codec and behind its decode (include/flamingo_hip.h, DESIGN.md section 5,
+// tests/rotate_cases.py): per block of H = 2^h parameters, forward: non-finite -> +0.0 (counted), sign flips,
+// butterfly stages 0 .. h - 1 in that order, one multiply by c_h; inverse: the stages, the multiply, the flips.
+
+// The tile's LDS image: element idx of the tile lives at word rot_sw(idx), idx with bits 2..3 XORed by bits 5..6
+// and bit 4 by bit 8.  Bits 0..1 stay, so four consecutive elements stay one aligned 16-byte quad.  Banks
+// (MI355X: b32 accesses in two groups of 32 lanes, bank = word mod 32, bits 0..4 of the word; b128 stores in
+// groups of 8 lanes, bank = word mod 32; b128 loads in the four 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,
+// 28-31} and those + 32, bank = word mod 64), with t the thread and t_i its bits:
+//   first write, b128, idx = 16 t + 4 q: the 8 lanes of a group differ in t_0..t_2 = idx bits 4..6; word bits
+//     2..4 are (q_0 ^ t_1, q_1 ^ t_2, t_0 ^ t_4): a bijection of t_0..t_2, 8 quads on 8 different quad-banks;
+//   second access (read, and the write back to the same words), b32, idx = (t >> 4) << 8 | k << 4 | (t & 15):
+//     the 32 lanes of a group differ in t_0..t_4 = idx bits 0..3 and 8; word bits 0..4 are (t_0, t_1,
+//     t_2 ^ k_1, t_3 ^ k_2, k_0 ^ t_4): a bijection of t_0..t_4, 32 banks;
+//   third access (read and write back), b32, idx = k << 8 | t: the lanes differ in idx bits 0..4, bits 5, 6 and 8
+//     are the group's own: word bits 0..4 are t_0..t_4 XOR a constant, 32 banks;
+//   last read, b128, idx = 1024 m + 4 t: word bits 2..5 are (t_0 ^ t_3, t_1 ^ t_4, t_2 ^ t_6, t_3); a 16-lane
+//     group is four runs of four lanes whose (t_2, t_3) are (0,0), (1,1), (1,0), (0,1) in some order with t_4
+//     fixed per run, so (bit 4, bit 5) tells the runs apart and (bit 2, bit 3) the lanes of a run: 16 quads on
+//     the 16 quad-banks.
+// So no access conflicts at all.
+__device__ __forceinline__ int rot_sw(int idx) { return idx ^ (((idx >> 5) & 3) << 2) ^ (((idx >> 8) & 1) << 4); }
+
+// Stages LO .. LO + 3 on 16 values, v[k] the element whose index bits LO .. LO + 3 are k; stages >= h are skipped
+// (h is uniform over the launch: scalar branches).
+template <int LO>
+__device__ __forceinline__ void rot_stages(float (&v)[16], int h) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        if (LO + s < h) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                if (i >> s & 1) continue;
+                const float a = v[i], b = v[i | 1 << s];
+                v[i] = a + b;
+                v[i | 1 << s] = a - b;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ float rot_flip(float v, uint32_t bits, int j) {
+    return __uint_as_float(__float_as_uint(v) ^ ((bits >> j & 1u) << 31));
+}
+
+// out = the rotation of x, rows of L parameters taken as L_rot = round_up(L, 2^h): forward reads L floats a row
+// (a predicate per element past L: the padding of a row may hold anything) and writes L_rot, inverse reads L_rot and
+// writes the L.  Workgroup g = (row, 4096-parameter tile) = (g / tiles, g % tiles) of a one-dimensional grid; a tile
+// holds whole blocks.  Thread t loads parameters 16 t .. 16 t + 15 (four 16-byte loads) and runs stages 0..3 in
+// registers; PHASES = ceil(h / 4) > 1: the tile goes through LDS (rot_sw above) and the thread takes the 16 elements
+// that differ in index bits 4..7 for stages 4..7, and PHASES = 3 once more those in bits 8..11.  The scaled values
+// go back to the words they came from and the tile is stored from LDS in order, 16 bytes a thread and 4 KiB
+// contiguous per store instruction of the workgroup (PHASES = 1 stores its registers, 64 bytes contiguous a thread).
+// Every global load of a tile precedes its first barrier, and a thread of PHASES = 1 writes what it alone read, so
+// out may be x.  sign_bits: ceil(L_rot / 32) words of PRG(key), bit l % 32 of word l / 32 flips parameter l.
+// nonfinite[row] (forward, zeroed by the call, or NULL): the threads' counts meet in LDS, the first wave adds them
+// up and its first lane adds a non-zero total with one atomic.
+template <bool INVERSE, int PHASES>
+__global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_pitch, uint64_t L, uint64_t L_rot,
+                                                     uint32_t tiles, int h, float scale,
+                                                     const uint32_t *__restrict__ sign_bits, float *out,
+                                                     uint64_t out_pitch, uint32_t *__restrict__ nonfinite) {
+#pragma clang fp contract(off)
+    __shared__ float4 lds4[PHASES > 1 ? 1024 : 1];  // the tile: 16 KiB
+    __shared__ uint32_t cnt[INVERSE ? 1 : 256];
+    float *lds = reinterpret_cast<float *>(lds4);
+    const int t = threadIdx.x;
+    const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+    const uint64_t base = (uint64_t)tile * 4096u;
+    const float *xr = x + (uint64_t)row * x_pitch;
+    float *orow = out + (uint64_t)row * out_pitch;
+
+    // four consecutive results at parameter s of the row (s a multiple of 4, so they share a sign word)
+    auto emit = [&](uint64_t s, float4 q) {
+        if constexpr (!INVERSE) {
+            if (s < L_rot) *reinterpret_cast<float4 *>(orow + s) = q;
+        } else {
+            if (s >= L) return;
+            const uint32_t b = sign_bits[s >> 5] >> (s & 31);
+            q = make_float4(rot_flip(q.x, b, 0), rot_flip(q.y, b, 1), rot_flip(q.z, b, 2), rot_flip(q.w, b, 3));
+            if (s + 3 < L) {
+                *reinterpret_cast<float4 *>(orow + s) = q;
+            } else {
+                orow[s] = q.x;
+                if (s + 1 < L) orow[s + 1] = q.y;
+                if (s + 2 < L) orow[s + 2] = q.z;
+            }
+        }
+    };
+
+    float v[16];
+    const uint64_t p0 = base + 16u * (uint64_t)t;  // 16 parameters: all below L_rot, or none
+    if constexpr (INVERSE) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float4 q = p0 < L_rot ? *reinterpret_cast<const float4 *>(xr + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[4 * j] = q.x, v[4 * j + 1] = q.y, v[4 * j + 2] = q.z, v[4 * j + 3] = q.w;
+        }
+    } else {
+        uint32_t bad = 0;
+        const uint32_t sb = p0 < L_rot ? sign_bits[p0 >> 5] >> (p0 & 16) : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t s = p0 + 4u * j;
+            // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+            const float4 q = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[4 * j] = s < L ? q.x : 0.0f, v[4 * j + 1] = s + 1 < L ? q.y : 0.0f;
+            v[4 * j + 2] = s + 2 < L ? q.z : 0.0f, v[4 * j + 3] = s + 3 < L ? q.w : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const bool nf = (__float_as_uint(v[j]) & 0x7f800000u) == 0x7f800000u;  // NaN or +-Inf
+            bad += nf ? 1u : 0u;
+            v[j] = rot_flip(nf ? 0.0f : v[j], sb, j);
+        }
+        if (nonfinite) cnt[t] = bad;
+    }
+    rot_stages<0>(v, h);
+
+    if constexpr (PHASES == 1) {
+        if constexpr (!INVERSE) {
+            if (nonfinite) __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            emit(p0 + 4u * j, make_float4(v[4 * j] * scale, v[4 * j + 1] * scale, v[4 * j + 2] * scale, v[4 * j + 3] * scale));
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            lds4[rot_sw(16 * t + 4 * q) >> 2] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        __syncthreads();
+        const int i1 = (t >> 4) << 8 | (t & 15);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = lds[rot_sw(i1 | k << 4)];
+        rot_stages<4>(v, h);
+        if constexpr (PHASES == 2) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) lds[rot_sw(i1 | k << 4)] = v[k] * scale;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) lds[rot_sw(i1 | k << 4)] = v[k];
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = lds[rot_sw(k << 8 | t)];
+            rot_stages<8>(v, h);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) lds[rot_sw(k << 8 | t)] = v[k] * scale;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < 4; ++m) emit(base + 1024u * m + 4u * t, lds4[rot_sw(1024 * m + 4 * t) >> 2]);
+    }
+
+    if constexpr (!INVERSE) {
+        if (nonfinite && t < 64) {  // after the first barrier of either shape
+            uint32_t c = cnt[t] + cnt[t + 64] + cnt[t + 128] + cnt[t + 192];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+            if (t == 0 && c) atomicAdd(nonfinite + row, c);
+        }
+    }
+}
+
 #undef FLM_QR
 #undef FLM_ROTL
 
@@ -1305,6 +1473,30 @@ hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, fl
     if (n == 0) return hipSuccess;
     const uint64_t g = std::min<uint64_t>(4096, (n / 4 + 255) / 256 + 1);
     hipLaunchKernelGGL(decode_sum_kernel, dim3((unsigned)g), dim3(256), 0, stream, d_sum, n, denom, d_out);
+    return hipGetLastError();
+}
+
+uint64_t rotate_groups(int N, uint64_t L_rot) { return (uint64_t)N * ((L_rot + 4095) / 4096); }
+
+hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
+                         const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
+                         uint32_t *d_nonfinite, hipStream_t stream) {
+    const uint64_t groups = rotate_groups(N, L_rot);
+    if (groups == 0) return hipSuccess;
+    if (groups > 0x7fffffffull || log2_block < 4 || log2_block > 12 || L_rot % (1u << log2_block) || L > L_rot)
+        return hipErrorInvalidValue;
+    // c_h = float32(2^(-h / 2)): a power of two, times float32(sqrt(1 / 2)) = 0x3F3504F3 for odd h
+    const uint32_t rsqrt2_bits = 0x3F3504F3u;
+    float rsqrt2;
+    memcpy(&rsqrt2, &rsqrt2_bits, sizeof rsqrt2);
+    const float scale = ldexpf(log2_block % 2 ? rsqrt2 : 1.0f, -(log2_block / 2));
+    // [inverse][phases - 1], phases = ceil(h / 4)
+    static constexpr decltype(&rotate_kernel<false, 1>) kernels[2][3] = {
+        {rotate_kernel<false, 1>, rotate_kernel<false, 2>, rotate_kernel<false, 3>},
+        {rotate_kernel<true, 1>, rotate_kernel<true, 2>, rotate_kernel<true, 3>}};
+    hipLaunchKernelGGL(kernels[inverse][(log2_block - 1) / 4], dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, L,
+                       L_rot, (uint32_t)((L_rot + 4095) / 4096), log2_block, scale, d_sign_bits, d_out, out_pitch,
+                       inverse ? nullptr : d_nonfinite);
     return hipGetLastError();
 }
 

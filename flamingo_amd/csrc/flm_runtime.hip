@@ -205,6 +205,7 @@ struct flm_ctx {
     std::vector<SeedTable *> tables;  // ring of device seed tables (SeedTable)
     SeedTable *cur_table = nullptr;   // the table the last seed-schedule / small-round launch wrote
     SeedTable *pub_table = nullptr;   // the table flm_seed_table_dev published for flm_aggregate_dev
+    DevBuf rot_signs;                 // flm_rotate's sign words: PRG(key), in no call's array list (flm_call_args.h)
     DevBuf small_meta;                // sign counts of the one-launch small round (no seed table)
     bool last_small = false;          // the last sign counts came from a small round (flm_check_signs)
     uint64_t table_clock = 0;
@@ -1054,7 +1055,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1097,7 +1098,7 @@ void flm_free(flm_ctx *ctx) {
     if (ctx->small_meta.p) (void)hipDeviceSynchronize();  // small rounds on any stream may still write it
     ctx->small_meta.release();
     for (DevBuf *b : {&ctx->rows, &ctx->out, &ctx->seeds, &ctx->signs, &ctx->bytes_in, &ctx->bytes_out, &ctx->ec_in,
-                      &ctx->ec_base, &ctx->ec_scal, &ctx->ec_jac, &ctx->ec_out, &ctx->ec_dig, &ctx->ec_flags})
+                      &ctx->ec_base, &ctx->ec_scal, &ctx->ec_jac, &ctx->ec_out, &ctx->ec_dig, &ctx->ec_flags, &ctx->rot_signs})
         b->release();
     for (StageSlot *s : ctx->slots) {
         if (s->host) (void)hipHostFree(s->host);
@@ -1463,6 +1464,64 @@ int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, ui
     set_last_plan(ctx, (int)std::min<uint64_t>(flm::rt::prg_expand_units(K, L), (uint64_t)groups), flm::kWaveSlots, 0,
                   kExpandVariant);
     return 0;
+}
+
+// ---- the randomised block Hadamard rotation (flm_call_args.h has the rule)
+
+int flm_rotate_check(uint64_t L, int log2_block, uint64_t *L_rot) {
+    bool range = false;
+    uint64_t lr = 0;
+    if (int rc = refuse(nullptr, flm::rt::rotate_error(L, log2_block, &range, &lr), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (L_rot) *L_rot = lr;
+    return 0;
+}
+
+int flm_rotate_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
+                   const uint32_t *d_sign_bits, int inverse, float *d_out, size_t out_pitch, uint32_t *d_nonfinite,
+                   void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    bool range = false;
+    uint64_t L_rot = 0;
+    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (inverse && d_nonfinite) return fail(ctx, FLM_EINVAL, "the inverse rotation counts nothing: nonfinite must be NULL");
+    if (N == 0) return 0;
+    if (!d_x || !d_out || !d_sign_bits) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, inverse ? L_rot : L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, inverse ? L : L_rot))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out, d_sign_bits}))) return rc;
+    if (int rc = refuse(ctx, flm::rt::rotate_launch_error(flm::rotate_groups(N, L_rot)))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+    FLM_ON_DEVICE(ctx);
+    if (d_nonfinite) FLM_HIP(ctx, hipMemsetAsync(d_nonfinite, 0, (size_t)N * sizeof(uint32_t), s));
+    FLM_HIP(ctx, flm::launch_rotate(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, inverse != 0, d_out, out_pitch,
+                                    d_nonfinite, s));
+    return 0;
+}
+
+int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], int inverse,
+               float *out, uint32_t *nonfinite) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    bool range = false;
+    uint64_t L_rot = 0;
+    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (inverse && nonfinite) return fail(ctx, FLM_EINVAL, "the inverse rotation counts nothing: nonfinite must be NULL");
+    if (N == 0) return 0;
+    if (!x || !out || !key) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    const size_t L_in = inverse ? L_rot : L, L_out = inverse ? L : L_rot, words = flm::rt::rotate_sign_words(L_rot);
+    FLM_HIP(ctx, ctx->rot_signs.reserve(round_up(words, 4) * sizeof(uint32_t)));
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::rotate_args(N, L_in, L_out, nonfinite != nullptr), {x, out, key, nonfinite});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_prg_expand_dev(ctx, hc.dev<uint8_t>(2), 1, words, 0, ctx->rot_signs.as<uint32_t>(), round_up(words, 4),
+                                    ctx->stream))
+        return rc;
+    if (int rc = flm_rotate_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, log2_block, ctx->rot_signs.as<uint32_t>(), inverse,
+                                hc.dev<float>(1), hc.pitch(1) / 4, hc.dev<uint32_t>(3), ctx->stream))
+        return rc;
+    return hc.finish();
 }
 
 int flm_mask_accumulate(flm_ctx *ctx, const uint8_t *seeds, const int8_t *signs, int K, uint32_t *acc, size_t L,

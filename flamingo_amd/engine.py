@@ -360,6 +360,52 @@ class MaskEngine:
         self._check(rc, "flm_decode_unpack_noise")
         return out
 
+    # ------------------------------------- randomised block Hadamard rotation
+    def rotate_check(self, L: int, log2_block: int) -> int:
+        """L_rot = round_up(L, 2^log2_block), the length a row of L parameters has once rotated; raises for
+        log2_block outside 4..12, L = 0, or a row whose sign stream would pass the PRG's range.  No device call.
+        flm_rotate_check."""
+        L_rot = ctypes.c_uint64(0)
+        self._check(self.lib.flm_rotate_check(int(L), int(log2_block), ctypes.byref(L_rot)), "flm_rotate_check")
+        return int(L_rot.value)
+
+    def rotate(self, x: np.ndarray, key, log2_block: int, inverse: bool = False, L: int | None = None,
+               return_nonfinite: bool = False):
+        """The randomised block Hadamard rotation of float32 rows under the 32-byte public `key` (flm_rotate).
+        Forward: x (N, L) or (L,) in, (N, L_rot) out, L_rot = round_up(L, 2^log2_block); non-finite inputs become
+        +0.0 and, with return_nonfinite, are counted per row.  Inverse: x (N, L_rot) in and the first L parameters
+        out (L is required: the rows' length before the rotation)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        if x.ndim != 2:
+            raise RuntimeError("x must be (N, L) or (L,)")
+        N = x.shape[0]
+        if not inverse:
+            if L is not None and int(L) != x.shape[1]:
+                raise RuntimeError("forward: L is the row length of x")
+            L = x.shape[1]
+        elif L is None:
+            raise RuntimeError("inverse: L, the rows' length before the rotation, is required")
+        L = int(L)
+        L_rot = self.rotate_check(L, log2_block)
+        if inverse and x.shape[1] != L_rot:
+            raise RuntimeError(f"inverse: x must hold rows of L_rot = {L_rot} floats")
+        if inverse and return_nonfinite:
+            raise RuntimeError("the inverse rotation counts nothing")
+        key = _seeds_array([key] if isinstance(key, (bytes, bytearray)) else key)
+        if key.shape[0] != 1:
+            raise RuntimeError("one 32-byte rotation key")
+        out = np.empty((N, L if inverse else L_rot), dtype=np.float32)
+        nonfinite = np.zeros(N, dtype=np.uint32)
+        rc = self.lib.flm_rotate(self.ctx, p_f32(x), N, L, int(log2_block), p_u8(key), int(bool(inverse)), p_f32(out),
+                                 p_u32(nonfinite) if return_nonfinite else None)
+        self._check(rc, "flm_rotate")
+        if one:
+            out = out[0]
+        return (out, nonfinite) if return_nonfinite else out
+
     def decode_sum(self, total: np.ndarray, frac_bits: int, count: int = 1) -> np.ndarray:
         """float32(int32(total) / (count * 2^frac_bits)): the ring sum as the mean of `count` contributors."""
         total = np.ascontiguousarray(total, dtype=np.uint32)
@@ -564,6 +610,29 @@ class MaskEngine:
                                                   pack, int(noise_bits), int(count), ctypes.c_void_p(out.data_ptr()),
                                                   self._stream_handle(stream))
         self._check(rc, "flm_decode_unpack_noise_dev")
+        return out
+
+    def rotate_dev(self, x, out, L: int, log2_block: int, sign_bits, inverse: bool = False, nonfinite=None, stream=None):
+        """Device rotate: x and out (>= N, >= row length) float32 CUDA tensors with unit column stride, rows at their
+        own strides (out may be x); forward reads L and writes L_rot floats a row, inverse reads L_rot and writes L.
+        sign_bits: >= ceil(L_rot / 32) 32-bit words, prg_expand_dev of the key (K = 1); nonfinite (>= N,) 32-bit or
+        None, forward only.  Enqueued on `stream`; nothing is synchronised.  flm_rotate_dev."""
+        import torch
+        L_rot = self.rotate_check(L, log2_block)
+        N = x.shape[0] if x.dim() == 2 else -1
+        for name, t, n in (("x", x, L_rot if inverse else L), ("out", out, L if inverse else L_rot)):
+            if t.dim() != 2 or t.shape[0] != N or t.shape[1] < n or t.dtype != torch.float32 or t.stride(1) != 1:
+                raise RuntimeError(f"{name} must be ({N}, >= {n}) float32 with unit column stride")
+        if sign_bits.element_size() != 4 or sign_bits.numel() < -(-L_rot // 32) or not sign_bits.is_contiguous():
+            raise RuntimeError(f"sign_bits must hold >= {-(-L_rot // 32)} contiguous 32-bit words")
+        if nonfinite is not None and (nonfinite.dim() != 1 or nonfinite.shape[0] < N or nonfinite.element_size() != 4
+                                      or not nonfinite.is_contiguous()):
+            raise RuntimeError(f"nonfinite must be a contiguous (>= {N},) 32-bit tensor")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        rc = self.lib.flm_rotate_dev(self.ctx, ptr(x), x.stride(0) if N > 1 else x.shape[1], N, int(L), int(log2_block),
+                                     ptr(sign_bits), int(bool(inverse)), ptr(out),
+                                     out.stride(0) if N > 1 else out.shape[1], ptr(nonfinite), self._stream_handle(stream))
+        self._check(rc, "flm_rotate_dev")
         return out
 
     def prg_expand_dev(self, seeds_dev, out, L: int, slot0: int = 0, stream=None):

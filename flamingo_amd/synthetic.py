@@ -29,10 +29,16 @@ from . import params as P
 from .abides.flamingo.seeds import lagrange_at_zero, shamir_share
 
 
-def float_update(client_id: int, L: int, clip: float) -> np.ndarray:
+def float_update(client_id: int, L: int, clip: float, rotate_bits: int = 0) -> np.ndarray:
     """A client's float32 update for the agents' float_inputs option when none is set: L normal draws of
-    deviation clip / 8 from PCG64(client_id): nothing reaches +-clip, so the decoded mean is within half a step of theirs."""
+    deviation clip / 8 from PCG64(client_id): nothing reaches +-clip, so the decoded mean is within half a step of theirs.
+    rotate_bits = h > 0 (the randomised Hadamard rotation is on, and the clip bounds rotated coordinates): L uniform
+    draws within +-clip 2^-(ceil(h / 2) + 1) instead, so that no rotated coordinate, at most 2^(h / 2) times the
+    largest input, can pass clip / 2."""
     rng = np.random.Generator(np.random.PCG64(int(client_id)))
+    if rotate_bits:
+        bound = clip * 2.0 ** -((int(rotate_bits) + 1) // 2 + 1)
+        return (rng.uniform(-1.0, 1.0, L) * bound).astype(np.float32)
     return (rng.standard_normal(L) * (clip / 8.0)).astype(np.float32)
 
 

@@ -297,6 +297,59 @@ int flm_decode_unpack_noise(flm_ctx *ctx, const uint32_t *sum, size_t L, int fra
 int flm_decode_unpack_noise_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
                                 int noise_bits, int64_t count, float *d_out, void *stream);
 
+/* ------------------------------ randomised block Hadamard rotation of float updates */
+
+/* A float -> float step in front of the codec's encode and behind its decode, the flattening the
+ * distributed-DP literature the codec follows applies before quantising (cpSGD; Kairouz et al., "The Distributed
+ * Discrete Gaussian Mechanism", ICML 2021): the clip then has to cover about ||x||_2 / sqrt(H) per coordinate,
+ * not ||x||_inf.  The rotation is linear and orthonormal, so it commutes with the secure sum and keeps the noise
+ * variance per coordinate.  It stands where the reference says "For machine learning, replace it with model
+ * weights" (agent/flamingo/SA_ClientAgent.py:300-304) on the way in, and behind the server's final sum
+ * (SA_ServiceAgent.py:538-540, 605) on the way out.  Normative:
+ *   log2_block h in 4..12, block H = 2^h parameters; a 32-byte rotation `key`, public, the same for every client and
+ *     the server.  A row of L parameters is treated as L_rot = round_up(L, H) parameters; parameters >= L read as
+ *     +0.0 whatever the memory behind L holds.
+ *   signs: S = PRG(key), the word stream of every mask; parameter l is negated iff bit (l mod 32) of S[l / 32] is 1:
+ *     indexed by parameter within the row, one sign vector for all rows of a call; a flip is an XOR of the float's
+ *     sign bit.
+ *   forward (client, before the encode), per block, in this order:
+ *     1. an input that is NaN or +-Inf becomes +0.0 and counts as non-finite for its row (padding and parameters
+ *        >= L never count);
+ *     2. the sign flips;
+ *     3. for s = 0, 1, ..., h - 1 in that order, for every pair (i, i ^ 2^s) with bit s of i clear:
+ *        (a, b) <- (a + b, a - b), float32 round-to-nearest adds;
+ *     4. every element times c_h = float32(2^(-h / 2)), once: 2^(-h / 2) exactly for even h,
+ *        0x3F3504F3 * 2^(-(h - 1) / 2) for odd h;
+ *     5. L_rot floats out.
+ *   inverse (server, after the decode): the same butterflies in the same order on L_rot inputs, the multiply by c_h,
+ *     then the sign flips; only parameters < L are written.  No non-finite handling: IEEE arithmetic on whatever
+ *     comes in.
+ *   Every add has fixed operands, so any evaluation order of this butterfly DAG gives the same bits.
+ * Accuracy: per block |fl(y) - y| <= (h + 1) 2^-24 ||x_block||_2 per element; a quantisation error of at most
+ * 2^-(f + 1) per rotated coordinate becomes at most sqrt(H) 2^-(f + 1) per original coordinate (rms unchanged).
+ * The rotation is block-wise: no whole-vector transform, no padding rule but round-up-to-H, no per-client keys.
+ *
+ * flm_rotate_check (SA_ClientAgent.py:300-304; SA_ServiceAgent.py:538-540, 605): FLM_EINVAL for h outside 4..12 or
+ * L = 0; FLM_ERANGE when the L_rot / 32 words of sign stream would pass the PRG's slot range; else *L_rot (may be
+ * NULL).  No context, no device. */
+int flm_rotate_check(uint64_t L, int log2_block, uint64_t *L_rot);
+/* The rotation on device buffers (SA_ClientAgent.py:300-304; SA_ServiceAgent.py:538-540, 605), enqueued on `stream`;
+ * nothing is synchronised.  Forward reads L and writes L_rot floats per row: x_pitch >= round_up(L, 4), out_pitch
+ * >= L_rot; inverse reads L_rot and writes L: x_pitch >= L_rot, out_pitch >= round_up(L, 4).  Pitches are multiples
+ * of 4, pointers 16-byte aligned.  Whatever the padding of a row holds is neither read as input nor counted, and
+ * nothing behind the floats written is touched.  d_out may be d_x at equal pitches >= L_rot, in both directions.
+ * d_sign_bits: ceil(L_rot / 32) words, which the caller makes with flm_prg_expand_dev(key, K = 1, L = ceil(L_rot /
+ * 32), slot0 = 0); the call runs no ChaCha.  d_nonfinite (N words or NULL) is zeroed on the stream first; forward
+ * only: it must be NULL for the inverse (FLM_EINVAL). */
+int flm_rotate_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
+                   const uint32_t *d_sign_bits, int inverse, float *d_out, size_t out_pitch, uint32_t *d_nonfinite,
+                   void *stream);
+/* The host-pointer form (SA_ClientAgent.py:300-304; SA_ServiceAgent.py:538-540, 605): x is N x L packed and out
+ * N x L_rot (forward), or N x L_rot in and N x L out (inverse); the key is expanded on the device; nonfinite: N
+ * counts (written), or NULL; NULL for the inverse. */
+int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], int inverse,
+               float *out, uint32_t *nonfinite);
+
 /* Device-resident PRG expansion: d_out[k*pitch + l] = PRG(seed k)[slot0 + l]. */
 int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, uint64_t slot0,
                        uint32_t *d_out, size_t pitch, void *stream);

@@ -1,6 +1,6 @@
 // args_check.cpp -- the host side of the calls that come in a host-pointer and a *_dev form, without a GPU, for
 // the host sanitizers: the round path (flm_client_mask, flm_client_encode_mask, flm_decode_sum, flm_prg_expand,
-// flm_mask_accumulate, flm_aggregate_unmask, flm_chacha20_xor) and the batch crypto calls (flm_shamir_combine /
+// flm_mask_accumulate, flm_aggregate_unmask, flm_chacha20_xor, flm_rotate) and the batch crypto calls (flm_shamir_combine /
 // _deal, flm_aes_gcm_xor / _seal / _open, flm_ecdsa_verify, flm_feldman_verify, flm_ec_combine, flm_ec_mul,
 // hash to curve):
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
@@ -145,6 +145,22 @@ static void check_round_lists() {
                     through_bounce(decode_unpack_args(L, L));
                     through_bounce(chacha20_xor_args(L));
                 }
+    // flm_rotate: forward L in and L_rot out, the inverse the other way round, with and without the counts
+    for (size_t L : {size_t(1), size_t(15), size_t(16), size_t(17), size_t(4097)})
+        for (int h : {4, 5, 12})
+            for (size_t N : {size_t(1), size_t(3)})
+                for (int opt = 0; opt < 2; ++opt) {
+                    bool range = false;
+                    uint64_t L_rot = 0;
+                    CHECK(!rotate_error(L, h, &range, &L_rot) && L_rot % (1u << h) == 0 && L_rot >= L && L_rot - L < (1u << h));
+                    through_bounce(rotate_args(N, L, L_rot, opt));
+                    if (!opt) through_bounce(rotate_args(N, L_rot, L, false));
+                }
+    const ArgList ro = rotate_args(3, 5, 16, true), ri = rotate_args(3, 16, 5, false);
+    CHECK(ro.n == 4 && ro.a[0].slot == rows && ro.a[0].width == 20 && ro.a[0].rows == 3 && ro.a[0].in_place && !ro.a[0].is_out &&
+          ro.a[1].slot == out && ro.a[1].width == 64 && ro.a[1].is_out && ro.a[1].in_place && ro.a[2].width == 32 &&
+          ro.a[2].slot == seeds && ro.a[3].present && ro.a[3].is_out && ro.a[3].width == 12);
+    CHECK(ri.a[0].width == 64 && ri.a[1].width == 20 && !ri.a[3].present);
     // rows travel at the host forms' pitch; what is optional is exactly what the flags name
     const ArgList m = client_mask_args(3, 7, 5, false), e = client_encode_mask_args(3, 7, 5, 5, false, false, true);
     CHECK(host_row_pitch(1) == 256 && host_row_pitch(64) == 256 && host_row_pitch(65) == 512);
@@ -243,6 +259,19 @@ static void check_round_rules() {
     const ArgList ne = client_encode_mask_args(3, 7, 5, 2, false, true, true);
     CHECK(ne.n == 6 && ne.a[3].present && ne.a[3].width == 96 && !ne.a[2].present && ne.a[4].is_out && ne.a[4].width == 8);
     CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
+    // the rotation's rule: h in 4..12, L > 0, L_rot = round_up(L, 2^h), L_rot / 32 sign words within 2^36 PRG slots
+    uint64_t L_rot = 0;
+    for (int h : {3, 13, 0, -1}) CHECK(rotate_error(100, h, &range, &L_rot) && !range);
+    CHECK(rotate_error(0, 4, &range, &L_rot) && !range);
+    CHECK(!rotate_error(1, 4, &range, &L_rot) && L_rot == 16 && !rotate_error(16, 4, &range, &L_rot) && L_rot == 16);
+    CHECK(!rotate_error(17, 4, &range, &L_rot) && L_rot == 32 && !rotate_error(4001, 5, &range, &L_rot) && L_rot == 4032);
+    CHECK(!rotate_error(4097, 12, &range, &L_rot) && L_rot == 8192 && !range);
+    CHECK(!rotate_error(1ull << 41, 12, &range, &L_rot) && L_rot == 1ull << 41);          // 2^36 words exactly
+    CHECK(!rotate_error((1ull << 41) - 4095, 12, &range, &L_rot) && L_rot == 1ull << 41);
+    CHECK(rotate_error((1ull << 41) + 1, 4, &range, &L_rot) && range && rotate_error(~0ull, 12, &range, &L_rot) && range);
+    CHECK(rotate_error(~0ull, 3, &range, &L_rot) && !range);                               // the block before the length
+    CHECK(rotate_sign_words(16) == 1 && rotate_sign_words(32) == 1 && rotate_sign_words(48) == 2);
+    CHECK(!rotate_launch_error(0x7fffffffull) && rotate_launch_error(0x80000000ull));
     CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));
     CHECK(!slot_range_error(0, 1ull << 36) && slot_range_error(16, 1ull << 36) && slot_range_error(1ull << 36, 1) &&
           !slot_range_error(1ull << 36, 0) && slot_range_error(~0ull, 2));
