@@ -17,8 +17,8 @@
 //     t 2^256 = t (2^224 - 2^192 - 2^96 + 1) (mod p), until no limb carries.
 // Values are kept lazily in [0, 2^256) (possibly >= p); canon() gives the representative < p.
 // The carry passes loop until no lane of the wave carries (wave-uniform branch after each pass): one
-// pass for almost every input, up to ~10 for adversarial ones (tools/ec_row_model.py runs the same
-// loops).
+// pass for almost every input, up to 7 (product columns) and 11 (signed passes) for the adversarial
+// ones found (tools/ec_row_model.py runs the same loops; tests/fe_cases.py searches them).
 // Normal form (no Montgomery factor): the reduction is the parallel NIST fold, not the sequential
 // Montgomery digit chain.
 #pragma once

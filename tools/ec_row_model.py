@@ -5,7 +5,13 @@ the cooperative scalar multiplication's latency chain (DESIGN.md section 10.2, V
    row, the product columns, the carry passes, the NIST fold with the 8x8 coefficient matrix, the
    signed passes with the top carry folded back -- checked against Python's own mod-p arithmetic,
    and the number of carry passes each loop takes (the kernel loops while any lane of the wave
-   carries, so the passes are part of the instruction count).
+   carries, so the passes are part of the instruction count).  Random operands take one pass of
+   each loop almost always and at most three; the structured search of tests/fe_cases.py
+   (row_pass_search: all pairs of 68 edge and limb-pattern values) reaches every count up to 7
+   column passes and 11 fold passes in row_mul, 11 in row_add and in row_sub, and 8 borrow passes
+   in row_canon (1 to 5, 7 and 8): the largest found, not proven bounds.  The counts here are of
+   passes that moved a carry; the kernel's do-while loops run at least one.  row_canon and
+   row_is_zero restate row::canon and row::is_zero for lazy values in [0, 2^256).
 2. VALU instructions per field operation for both layouts: the per-lane Montgomery field of
    flm_fe256.h (gfx950 ISA counts, DESIGN.md section 5: fe_mul 258, fe_sqr 265, fe_add 28, fe_sub
    20) and the row field (ISA counts of tools/probes/ec_row_probe.hip's chains, plus the carry
@@ -78,6 +84,31 @@ def row_add(a, b):
 def row_sub(a, b):
     out, p = snorm([x - y for x, y in zip(limbs(a), limbs(b))])
     return val(out), p
+
+
+def row_canon(a):
+    """row::canon: the representative < p of a lazy a in [0, 2^256): a - p limb-wise, the borrows passed
+    along the row, the borrows out of limb 7 summed in `top`; returns (value, passes)."""
+    la = limbs(a)
+    d = [x - y for x, y in zip(la, limbs(P))]
+    c = [x >> 32 for x in d]
+    lo = [x & M32 for x in d]
+    top = passes = 0
+    while True:                         # do-while: the kernel's first pass is unconditional
+        top += c[7]
+        d = [lo[r] + (c[r - 1] if r else 0) for r in range(8)]
+        c = [x >> 32 for x in d]
+        lo = [x & M32 for x in d]
+        passes += 1
+        if not any(c):
+            break
+    return (val(lo) if top == 0 else a), passes
+
+
+def row_is_zero(a):
+    """row::is_zero: a lazy a in [0, 2^256) is 0 mod p when its limbs are all zero or p's own"""
+    la = limbs(a)
+    return all(x == 0 for x in la) or la == limbs(P)
 
 
 def check(n_random=2000, seed=3):
