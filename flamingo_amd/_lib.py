@@ -63,6 +63,13 @@ SIGNATURES = {
     "flm_rotate_check": (_int, [_u64, _int, ctypes.POINTER(_u64)]),
     "flm_rotate_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _int, _vp, _sz, _vp, _vp]),
     "flm_rotate": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, _int, _f32p, _u32p]),
+    "flm_l2_clip_check": (_int, [_u64, ctypes.c_float, _int, ctypes.POINTER(_u64)]),
+    "flm_l2_factors_dev": (_int, [_vp, _vp, _sz, _int, _sz, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "flm_scale_rows_dev": (_int, [_vp, _vp, _sz, _int, _sz, _vp, _vp, _sz, _vp]),
+    "flm_rotate_clip_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "flm_l2_clip": (_int, [_vp, _f32p, _int, _sz, ctypes.c_float, _f32p, _f32p, ctypes.POINTER(ctypes.c_double)]),
+    "flm_rotate_clip": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, ctypes.c_float, _f32p, _u32p, _f32p,
+                               ctypes.POINTER(ctypes.c_double)]),
     "flm_prg_expand_dev": (_int, [_vp, _vp, _int, _sz, _u64, _vp, _sz, _vp]),
     "flm_check_signs": (_int, [_vp, ctypes.POINTER(_int)]),
     "flm_last_plan": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),

@@ -88,6 +88,11 @@ def parse(argv):
     # (protocol.configure(rotate=...)): CLIP then bounds the rotated coordinates, about ||x||_2 / 2^(LOG2BLOCK / 2)
     # per block where it had to cover the largest coordinate; needs --float_inputs; off by default
     ap.add_argument("--rotate", type=int, default=0, metavar="LOG2BLOCK")
+    # every client scales its float update to an L2 norm of at most C before the rotation, or in the rotation's own
+    # pass with --rotate (protocol.configure(l2_clip=...)): one client then moves the sum by at most C in L2, the
+    # sensitivity --dp_noise is measured against; turning C into a privacy statement is the caller's business; needs
+    # --float_inputs; off by default
+    ap.add_argument("--l2_clip", type=float, default=0.0, metavar="C")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -175,7 +180,7 @@ def _run(args):
                     gpu_verify=True if args.gpu_verify else None,
                     authenticate_shares=True if args.authenticate_shares else None,
                     dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs),
-                    dp_noise=args.dp_noise, rotate=args.rotate)
+                    dp_noise=args.dp_noise, rotate=args.rotate, l2_clip=args.l2_clip)
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -247,9 +252,13 @@ def _run(args):
             if param.rotate_bits():
                 rotated = f", rotated in blocks of 2^{param.rotate_bits()}"
                 nonfinite = f", {sum(agents[i].nonfinite for i in server.online_ids[it])} non-finite"
+            scaled = ""
+            if param.l2_clip() is not None:
+                scaled = (f", {sum(agents[i].l2_factor < 1.0 for i in server.online_ids[it])} of {len(server.online_ids[it])} "
+                          f"clients scaled to norm {param.l2_clip():g}")
             print(f"    iteration {it}: float inputs {param.codec()}{packed}{rotated}: largest |final_mean - mean of the clients' floats| = "
                   f"{float(np.max(np.abs(diff))):.3e}{noised}, "
-                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped{nonfinite}")
+                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped{nonfinite}{scaled}")
     print()
     results["server"] = server
     results["clients"] = agents[:n]

@@ -96,6 +96,8 @@ class SA_ClientAgent(Agent):
         self.clipped = 0             # float inputs: elements of the last update that were clipped
         self.nonfinite = 0           # ... and, with the rotation on, its non-finite elements (clipped then counts
                                      # rotated coordinates)
+        self.l2_factor = None        # float inputs with --l2_clip: the factor the last update was scaled by (1.0: within
+        self.l2_norm = None          # the norm), and the update's own L2 norm, sqrt of the library's sum of squares
         self.dither_seed = None      # float inputs, stochastic rounding: the last iteration's dither seed
         self.noise_seed = None       # float inputs with --dp_noise: the last iteration's noise seed
         pki = param.pki(num_clients)
@@ -240,9 +242,18 @@ class SA_ClientAgent(Agent):
                 self.input_vector = float_update(self.id, self.vector_len, clip, param.rotate_bits())
             x = np.asarray(self.input_vector, np.float32)[None, :]
             L = self.vector_len
+            norm = param.l2_clip()    # the update scaled to an L2 norm of at most this: before the rotation, or with it
+            if norm is not None and not param.rotate_bits():
+                x, factors, sumsq = param.engine().l2_clip(x, norm)
+                self.l2_factor, self.l2_norm = float(factors[0]), float(np.sqrt(sumsq[0]))
             if param.rotate_bits():   # the iteration's public rotation in front of the encode; the clip bounds its output
-                x, nonfinite = param.engine().rotate(x, param.rotation_key(self.current_iteration), param.rotate_bits(),
-                                                     return_nonfinite=True)
+                key = param.rotation_key(self.current_iteration)
+                if norm is None:
+                    x, nonfinite = param.engine().rotate(x, key, param.rotate_bits(), return_nonfinite=True)
+                else:
+                    x, nonfinite, factors, sumsq = param.engine().rotate(x, key, param.rotate_bits(), return_nonfinite=True,
+                                                                         clip_norm=norm)
+                    self.l2_factor, self.l2_norm = float(factors[0]), float(np.sqrt(sumsq[0]))
                 L, self.nonfinite = param.rotated_len(), int(nonfinite[0])
             dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
                 if rounding == "stochastic" else None

@@ -80,25 +80,32 @@ _dp_noise: int = 0
 # server rotates the decoded mean back; the clip then bounds rotated coordinates.  It needs the float inputs.  Off
 # by default, so a run sends what it always sent and draws what it always drew.
 _rotate: int = 0
+# L2 clip (config_flamingo's --l2_clip C): every client scales its float update to an L2 norm of at most C before the
+# rotation, or with it when the rotation is on (MaskEngine.l2_clip, MaskEngine.rotate(clip_norm=...)), so that one
+# client moves the sum by at most C in L2.  It needs the float inputs.  Off (None) by default, so a run calls what it
+# always called, sends what it always sent and draws what it always drew.
+_l2_clip: float | None = None
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
               authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None,
-              dp_noise: int | None = None, rotate: int | None = None):
+              dp_noise: int | None = None, rotate: int | None = None, l2_clip: float | None = None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
     "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
     many parameters into a ring word, False turns them off, None leaves them as they are.  dp_noise: the coin
     flips per parameter of every client's binomial noise share (even, 2..1024; 0 turns it off, None leaves it as
     it is); it needs the float inputs, and turning those off turns it off.  rotate: log2 of the block of the randomised
     Hadamard rotation in front of the codec (4..12; 0 turns it off, None leaves it as it is); it needs the float
-    inputs, and turning those off turns it off."""
+    inputs, and turning those off turns it off.  l2_clip: the L2 norm every client scales its update down to (finite
+    and positive; 0 turns it off, None leaves it as it is); it needs the float inputs, and turning those off turns it
+    off."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate
+    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate, _l2_clip
     if codec is not None:
         if codec is False:
-            _codec, _codec_pack, _dp_noise, _rotate = None, 1, 0, 0
+            _codec, _codec_pack, _dp_noise, _rotate, _l2_clip = None, 1, 0, 0, None
         else:
             f, c, mode = codec[:3]
             pack = int(codec[3]) if len(codec) == 4 else 1
@@ -123,6 +130,15 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
         if h and _codec is None:
             raise ValueError("rotate needs the float inputs (codec=...)")
         _rotate = h
+    if l2_clip is not None:
+        import ctypes
+        import math
+        c = ctypes.c_float(float(l2_clip)).value   # the float32 radius the library takes
+        if l2_clip != 0 and not (math.isfinite(c) and c > 0.0):
+            raise ValueError("l2_clip must be 0 or a finite positive norm")
+        if c and _codec is None:
+            raise ValueError("l2_clip needs the float inputs (codec=...)")
+        _l2_clip = c if c else None
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -306,6 +322,11 @@ def codec_noise_bits() -> int:
 def rotate_bits() -> int:
     """log2 of the rotation's block: 0 when the rotation is off (or the float inputs are)."""
     return _rotate if _codec is not None else 0
+
+
+def l2_clip() -> float | None:
+    """The L2 norm the clients scale their updates down to, or None when that is off (or the float inputs are)."""
+    return _l2_clip if _codec is not None else None
 
 
 def rotated_len() -> int:

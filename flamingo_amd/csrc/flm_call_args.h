@@ -168,6 +168,24 @@ inline const char *rotate_launch_error(uint64_t groups) {
     return groups > 0x7fffffffull ? "more than 2^31 - 1 4096-parameter tiles" : nullptr;
 }
 
+// flm_l2_clip_check, flm_l2_factors_dev, flm_scale_rows_dev, flm_l2_clip, flm_rotate_clip: the L2 clip's one rule.
+// N >= 1 rows of L > 0 parameters, a clip radius that is finite and positive; one workgroup per (row, 4096-parameter
+// tile) of a one-dimensional grid, so N ceil(L / 4096) <= 2^31 - 1, else FLM_ERANGE (*range set).  *work_doubles: the
+// tile partials of a call, N ceil(L / 4096).
+inline const char *l2_clip_error(uint64_t L, float clip_norm, int N, bool *range, uint64_t *work_doubles) {
+    *range = false;
+    if (L == 0) return "a row of no parameters";
+    if (N < 1) return "N must be at least 1";
+    if (!(clip_norm > 0.0f) || !std::isfinite(clip_norm)) return "clip_norm must be finite and positive";
+    const uint64_t tiles = L / 4096 + (L % 4096 ? 1 : 0);
+    if (tiles > 0x7fffffffull / (uint64_t)N) {
+        *range = true;
+        return "more than 2^31 - 1 4096-parameter tiles";
+    }
+    *work_doubles = (uint64_t)N * tiles;
+    return nullptr;
+}
+
 // flm_aggregate_dev, flm_aggregate_unmask_dev: the rows, the mask window and its PRG slots, the output.
 // *range: the refusal is the slot range's (FLM_ERANGE).
 inline const char *aggregate_error(const void *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
@@ -379,6 +397,20 @@ inline ArgList rotate_args(size_t N, size_t L_in, size_t L_out, bool nonfinite) 
     return {{in_place(pitched(arg_in(L_in * 4, rows), N, host_row_pitch(L_in))),
              in_place(pitched(arg_out(L_out * 4, out), N, host_row_pitch(L_out))), arg_in(32, seeds),
              arg_out(N * 4, bytes_out, nonfinite)}, 4};
+}
+// flm_l2_clip: x and out (N rows of L floats, in place as the rotation's), factors (N floats), sumsq (N doubles).
+// The tile partials, and the factors when the caller wants none back, live in a buffer of the context that no list
+// names (flm_ctx::l2_work).
+inline ArgList l2_clip_args(size_t N, size_t L, bool factors, bool sumsq) {
+    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))),
+             in_place(pitched(arg_out(L * 4, out), N, host_row_pitch(L))), arg_out(N * 4, ec_flags, factors),
+             arg_out(N * 8, ec_dig, sumsq)}, 4};
+}
+// flm_rotate_clip: flm_rotate's forward list, then factors and sumsq as flm_l2_clip's
+inline ArgList rotate_clip_args(size_t N, size_t L, size_t L_rot, bool nonfinite, bool factors, bool sumsq) {
+    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))),
+             in_place(pitched(arg_out(L_rot * 4, out), N, host_row_pitch(L_rot))), arg_in(32, seeds),
+             arg_out(N * 4, bytes_out, nonfinite), arg_out(N * 4, ec_flags, factors), arg_out(N * 8, ec_dig, sumsq)}, 6};
 }
 // seeds, out (K rows)
 inline ArgList prg_expand_args(size_t K, size_t L) {

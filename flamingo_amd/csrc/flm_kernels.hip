@@ -1319,12 +1319,17 @@ __device__ __forceinline__ float rot_flip(float v, uint32_t bits, int j) {
 // out may be x.  sign_bits: ceil(L_rot / 32) words of PRG(key), bit l % 32 of word l / 32 flips parameter l.
 // nonfinite[row] (forward, zeroed by the call, or NULL): the threads' counts meet in LDS, the first wave adds them
 // up and its first lane adds a non-zero total with one atomic.
-template <bool INVERSE, int PHASES>
+// FACTOR (forward only): the L2 clip rides in the load (the section below): every finite input is first multiplied
+// by row_factor[row], one float32 multiply between the non-finite zeroing and the sign flip; the row is the
+// workgroup's, so the factor is one scalar load.  Without FACTOR row_factor is not read.
+template <bool INVERSE, int PHASES, bool FACTOR>
 __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_pitch, uint64_t L, uint64_t L_rot,
                                                      uint32_t tiles, int h, float scale,
                                                      const uint32_t *__restrict__ sign_bits, float *out,
-                                                     uint64_t out_pitch, uint32_t *__restrict__ nonfinite) {
+                                                     uint64_t out_pitch, uint32_t *__restrict__ nonfinite,
+                                                     const float *__restrict__ row_factor) {
 #pragma clang fp contract(off)
+    static_assert(!(INVERSE && FACTOR), "the clip is the forward rotation's");
     __shared__ float4 lds4[PHASES > 1 ? 1024 : 1];  // the tile: 16 KiB
     __shared__ uint32_t cnt[INVERSE ? 1 : 256];
     float *lds = reinterpret_cast<float *>(lds4);
@@ -1363,6 +1368,8 @@ __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_
     } else {
         uint32_t bad = 0;
         const uint32_t sb = p0 < L_rot ? sign_bits[p0 >> 5] >> (p0 & 16) : 0u;
+        float rf = 1.0f;
+        if constexpr (FACTOR) rf = row_factor[row];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint64_t s = p0 + 4u * j;
@@ -1375,7 +1382,8 @@ __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_
         for (int j = 0; j < 16; ++j) {
             const bool nf = (__float_as_uint(v[j]) & 0x7f800000u) == 0x7f800000u;  // NaN or +-Inf
             bad += nf ? 1u : 0u;
-            v[j] = rot_flip(nf ? 0.0f : v[j], sb, j);
+            if constexpr (FACTOR) v[j] = rot_flip(nf ? 0.0f : v[j] * rf, sb, j);
+            else v[j] = rot_flip(nf ? 0.0f : v[j], sb, j);
         }
         if (nonfinite) cnt[t] = bad;
     }
@@ -1421,6 +1429,101 @@ __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
             if (t == 0 && c) atomicAdd(nonfinite + row, c);
+        }
+    }
+}
+
+// ------------------------------------------------------------ L2 clip of float updates
+// The step in front of the rotation (include/flamingo_hip.h has the rule, tests/l2_cases.py restates it): per row
+// the sum S of the squares in float64, in an order that depends on L alone, the factor s = min(1, C / sqrt(S)) as a
+// float32, and x s.  No atomics anywhere: every add has fixed operands.
+
+// a <- a + a[lane ^ off] for off = 1, 2, 4, 8, 16, 32: both lanes of a pair add the same two values (IEEE addition
+// commutes), so every lane of the wave ends with the same bits.
+__device__ __forceinline__ double l2_wave_sum(double a) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) a = a + __shfl_xor(a, off);
+    return a;
+}
+
+// work[row tiles + tile] = the tile's partial sum of squares.  Workgroup g = (row, 4096-parameter tile) and thread t
+// of it takes parameters 16 t .. 16 t + 15 of the tile with four 16-byte loads, as rotate_kernel does, with the same
+// predicate per element past L and the same non-finite rule: what the rotation reads as +0.0 counts as +0.0.  The
+// square of a float is exact in float64, so fma(d, d, acc) is acc + d d.
+__global__ __launch_bounds__(256) void l2_sumsq_kernel(const float *__restrict__ x, uint64_t x_pitch, uint64_t L,
+                                                       uint32_t tiles, double *__restrict__ work) {
+#pragma clang fp contract(off)
+    __shared__ double wave_sums[4];
+    const int t = threadIdx.x;
+    const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+    const float *xr = x + (uint64_t)row * x_pitch;
+    const uint64_t p0 = (uint64_t)tile * 4096u + 16u * (uint64_t)t;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t s = p0 + 4u * j;
+        // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+        const float4 q = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float e[4] = {s < L ? q.x : 0.0f, s + 1 < L ? q.y : 0.0f, s + 2 < L ? q.z : 0.0f, s + 3 < L ? q.w : 0.0f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool nf = (__float_as_uint(e[i]) & 0x7f800000u) == 0x7f800000u;  // NaN or +-Inf
+            const double d = (double)(nf ? 0.0f : e[i]);
+            acc = fma(d, d, acc);
+        }
+    }
+    acc = l2_wave_sum(acc);
+    if ((t & 63) == 0) wave_sums[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) work[(uint64_t)row * tiles + tile] = ((wave_sums[0] + wave_sums[1]) + wave_sums[2]) + wave_sums[3];
+}
+
+// One wave per row: lane k adds the row's partials k, k + 64, ... in that order, the wave sum is S, and
+// factors[row] = S <= C^2 ? 1 : float32(C / sqrt(S)) in float64 (C^2 is exact there); sumsq[row] = S when asked.
+__global__ __launch_bounds__(64) void l2_factor_kernel(const double *__restrict__ work, uint32_t tiles, float clip_norm,
+                                                      float *__restrict__ factors, double *__restrict__ sumsq) {
+#pragma clang fp contract(off)
+    const uint32_t row = blockIdx.x;
+    const double *w = work + (uint64_t)row * tiles;
+    double acc = 0.0;
+    for (uint32_t i = threadIdx.x; i < tiles; i += 64) acc = acc + w[i];
+    const double S = l2_wave_sum(acc);
+    if (threadIdx.x == 0) {
+        const double C = (double)clip_norm;
+        factors[row] = S <= C * C ? 1.0f : (float)(C / sqrt(S));
+        if (sumsq) sumsq[row] = S;
+    }
+}
+
+// out = x factors[row] over the L parameters of every row, one float32 multiply each (plain IEEE: NaN stays NaN, a
+// factor of 1 leaves the bits).  Workgroup g = (row, 4096-parameter tile); thread t takes the quads t, t + 256,
+// t + 512, t + 768 of the tile, 16 bytes a load and a store, the last quad of a row element by element.  A thread
+// writes what it alone read, so out may be x at equal pitches.
+__global__ __launch_bounds__(256) void scale_rows_kernel(const float *x, uint64_t x_pitch, uint64_t L, uint32_t tiles,
+                                                         const float *__restrict__ factors, float *out,
+                                                         uint64_t out_pitch) {
+#pragma clang fp contract(off)
+    const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+    const float f = factors[row];
+    const float *xr = x + (uint64_t)row * x_pitch;
+    float *orow = out + (uint64_t)row * out_pitch;
+    float4 q[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const uint64_t s = (uint64_t)tile * 4096u + 1024u * m + 4u * threadIdx.x;
+        q[m] = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const uint64_t s = (uint64_t)tile * 4096u + 1024u * m + 4u * threadIdx.x;
+        if (s >= L) continue;
+        const float4 r = make_float4(q[m].x * f, q[m].y * f, q[m].z * f, q[m].w * f);
+        if (s + 3 < L) {
+            *reinterpret_cast<float4 *>(orow + s) = r;
+        } else {
+            orow[s] = r.x;
+            if (s + 1 < L) orow[s + 1] = r.y;
+            if (s + 2 < L) orow[s + 2] = r.z;
         }
     }
 }
@@ -1478,12 +1581,14 @@ hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, fl
 
 uint64_t rotate_groups(int N, uint64_t L_rot) { return (uint64_t)N * ((L_rot + 4095) / 4096); }
 
-hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
-                         const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
-                         uint32_t *d_nonfinite, hipStream_t stream) {
+// d_factors: the fused L2 clip's factor per row (forward only), or NULL for the rotation alone
+static hipError_t launch_rotate_any(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
+                                    const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
+                                    uint32_t *d_nonfinite, const float *d_factors, hipStream_t stream) {
     const uint64_t groups = rotate_groups(N, L_rot);
     if (groups == 0) return hipSuccess;
-    if (groups > 0x7fffffffull || log2_block < 4 || log2_block > 12 || L_rot % (1u << log2_block) || L > L_rot)
+    if (groups > 0x7fffffffull || log2_block < 4 || log2_block > 12 || L_rot % (1u << log2_block) || L > L_rot ||
+        (inverse && d_factors))
         return hipErrorInvalidValue;
     // c_h = float32(2^(-h / 2)): a power of two, times float32(sqrt(1 / 2)) = 0x3F3504F3 for odd h
     const uint32_t rsqrt2_bits = 0x3F3504F3u;
@@ -1491,12 +1596,54 @@ hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, 
     memcpy(&rsqrt2, &rsqrt2_bits, sizeof rsqrt2);
     const float scale = ldexpf(log2_block % 2 ? rsqrt2 : 1.0f, -(log2_block / 2));
     // [inverse][phases - 1], phases = ceil(h / 4)
-    static constexpr decltype(&rotate_kernel<false, 1>) kernels[2][3] = {
-        {rotate_kernel<false, 1>, rotate_kernel<false, 2>, rotate_kernel<false, 3>},
-        {rotate_kernel<true, 1>, rotate_kernel<true, 2>, rotate_kernel<true, 3>}};
-    hipLaunchKernelGGL(kernels[inverse][(log2_block - 1) / 4], dim3((unsigned)groups), dim3(256), 0, stream, d_x, x_pitch, L,
-                       L_rot, (uint32_t)((L_rot + 4095) / 4096), log2_block, scale, d_sign_bits, d_out, out_pitch,
-                       inverse ? nullptr : d_nonfinite);
+    static constexpr decltype(&rotate_kernel<false, 1, false>) kernels[2][3] = {
+        {rotate_kernel<false, 1, false>, rotate_kernel<false, 2, false>, rotate_kernel<false, 3, false>},
+        {rotate_kernel<true, 1, false>, rotate_kernel<true, 2, false>, rotate_kernel<true, 3, false>}};
+    // the forward rotation with the clip's multiply in its load
+    static constexpr decltype(&rotate_kernel<false, 1, true>) clip_kernels[3] = {
+        rotate_kernel<false, 1, true>, rotate_kernel<false, 2, true>, rotate_kernel<false, 3, true>};
+    const int phases = (log2_block - 1) / 4;
+    hipLaunchKernelGGL(d_factors ? clip_kernels[phases] : kernels[inverse][phases], dim3((unsigned)groups), dim3(256), 0,
+                       stream, d_x, x_pitch, L, L_rot, (uint32_t)((L_rot + 4095) / 4096), log2_block, scale, d_sign_bits,
+                       d_out, out_pitch, inverse ? nullptr : d_nonfinite, d_factors);
+    return hipGetLastError();
+}
+
+hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
+                         const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
+                         uint32_t *d_nonfinite, hipStream_t stream) {
+    return launch_rotate_any(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, inverse, d_out, out_pitch, d_nonfinite,
+                             nullptr, stream);
+}
+
+hipError_t launch_rotate_clip(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
+                              const uint32_t *d_sign_bits, const float *d_factors, float *d_out, uint64_t out_pitch,
+                              uint32_t *d_nonfinite, hipStream_t stream) {
+    if (!d_factors) return hipErrorInvalidValue;
+    return launch_rotate_any(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, false, d_out, out_pitch, d_nonfinite,
+                             d_factors, stream);
+}
+
+uint64_t l2_tiles(uint64_t L) { return L / 4096 + (L % 4096 ? 1 : 0); }
+
+hipError_t launch_l2_factors(const float *d_x, uint64_t x_pitch, int N, uint64_t L, float clip_norm, double *d_work,
+                             float *d_factors, double *d_sumsq, hipStream_t stream) {
+    const uint64_t tiles = l2_tiles(L);
+    if (N < 1 || tiles == 0 || tiles > 0x7fffffffull / (uint64_t)N) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(l2_sumsq_kernel, dim3((unsigned)(tiles * (uint64_t)N)), dim3(256), 0, stream, d_x, x_pitch, L,
+                       (uint32_t)tiles, d_work);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(l2_factor_kernel, dim3((unsigned)N), dim3(64), 0, stream, d_work, (uint32_t)tiles, clip_norm,
+                       d_factors, d_sumsq);
+    return hipGetLastError();
+}
+
+hipError_t launch_scale_rows(const float *d_x, uint64_t x_pitch, int N, uint64_t L, const float *d_factors, float *d_out,
+                             uint64_t out_pitch, hipStream_t stream) {
+    const uint64_t tiles = l2_tiles(L);
+    if (N < 1 || tiles == 0 || tiles > 0x7fffffffull / (uint64_t)N) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)(tiles * (uint64_t)N)), dim3(256), 0, stream, d_x, x_pitch, L,
+                       (uint32_t)tiles, d_factors, d_out, out_pitch);
     return hipGetLastError();
 }
 

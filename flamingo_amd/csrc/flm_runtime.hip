@@ -206,6 +206,7 @@ struct flm_ctx {
     SeedTable *cur_table = nullptr;   // the table the last seed-schedule / small-round launch wrote
     SeedTable *pub_table = nullptr;   // the table flm_seed_table_dev published for flm_aggregate_dev
     DevBuf rot_signs;                 // flm_rotate's sign words: PRG(key), in no call's array list (flm_call_args.h)
+    DevBuf l2_work;                   // flm_l2_clip's and flm_rotate_clip's tile partials (and factors nobody asked for)
     DevBuf small_meta;                // sign counts of the one-launch small round (no seed table)
     bool last_small = false;          // the last sign counts came from a small round (flm_check_signs)
     uint64_t table_clock = 0;
@@ -1055,7 +1056,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1098,7 +1099,7 @@ void flm_free(flm_ctx *ctx) {
     if (ctx->small_meta.p) (void)hipDeviceSynchronize();  // small rounds on any stream may still write it
     ctx->small_meta.release();
     for (DevBuf *b : {&ctx->rows, &ctx->out, &ctx->seeds, &ctx->signs, &ctx->bytes_in, &ctx->bytes_out, &ctx->ec_in,
-                      &ctx->ec_base, &ctx->ec_scal, &ctx->ec_jac, &ctx->ec_out, &ctx->ec_dig, &ctx->ec_flags, &ctx->rot_signs})
+                      &ctx->ec_base, &ctx->ec_scal, &ctx->ec_jac, &ctx->ec_out, &ctx->ec_dig, &ctx->ec_flags, &ctx->rot_signs, &ctx->l2_work})
         b->release();
     for (StageSlot *s : ctx->slots) {
         if (s->host) (void)hipHostFree(s->host);
@@ -1520,6 +1521,140 @@ int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, co
         return rc;
     if (int rc = flm_rotate_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, log2_block, ctx->rot_signs.as<uint32_t>(), inverse,
                                 hc.dev<float>(1), hc.pitch(1) / 4, hc.dev<uint32_t>(3), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+// ---- the L2 clip in front of the rotation (flm_call_args.h has the rule)
+
+namespace {
+int check_l2(flm_ctx *ctx, uint64_t L, float clip_norm, int N, uint64_t *work_doubles) {
+    bool range = false;
+    return refuse(ctx, flm::rt::l2_clip_error(L, clip_norm, N, &range, work_doubles), range ? FLM_ERANGE : FLM_EINVAL);
+}
+}  // namespace
+
+int flm_l2_clip_check(uint64_t L, float clip_norm, int N, uint64_t *work_doubles) {
+    uint64_t wd = 0;
+    if (int rc = check_l2(nullptr, L, clip_norm, N, &wd)) return rc;
+    if (work_doubles) *work_doubles = wd;
+    return 0;
+}
+
+int flm_l2_factors_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, float clip_norm, double *d_work,
+                       float *d_factors, double *d_sumsq, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint64_t wd = 0;
+    if (int rc = check_l2(ctx, L, clip_norm, N, &wd)) return rc;
+    if (!d_x || !d_work || !d_factors) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x}))) return rc;
+    if (((uintptr_t)d_work | (uintptr_t)d_sumsq) & 7 || (uintptr_t)d_factors & 3)
+        return fail(ctx, FLM_EINVAL, "work and sumsq must be 8-byte aligned, factors 4-byte aligned");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_l2_factors(d_x, x_pitch, N, L, clip_norm, d_work, d_factors, d_sumsq,
+                                        static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_scale_rows_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, const float *d_factors,
+                       float *d_out, size_t out_pitch, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint64_t wd = 0;
+    if (int rc = check_l2(ctx, L, 1.0f, N, &wd)) return rc;
+    if (!d_x || !d_factors || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
+    if ((uintptr_t)d_factors & 3) return fail(ctx, FLM_EINVAL, "factors must be 4-byte aligned");
+    if (d_out == d_x && out_pitch != x_pitch) return fail(ctx, FLM_EINVAL, "in place needs equal pitches");
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, flm::launch_scale_rows(d_x, x_pitch, N, L, d_factors, d_out, out_pitch, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int flm_rotate_clip_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
+                        const uint32_t *d_sign_bits, const float *d_factors, float *d_out, size_t out_pitch,
+                        uint32_t *d_nonfinite, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    bool range = false;
+    uint64_t L_rot = 0;
+    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (N == 0) return 0;
+    if (!d_x || !d_out || !d_sign_bits || !d_factors) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, L_rot))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out, d_sign_bits}))) return rc;
+    if ((uintptr_t)d_factors & 3) return fail(ctx, FLM_EINVAL, "factors must be 4-byte aligned");
+    if (int rc = refuse(ctx, flm::rt::rotate_launch_error(flm::rotate_groups(N, L_rot)))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+    FLM_ON_DEVICE(ctx);
+    if (d_nonfinite) FLM_HIP(ctx, hipMemsetAsync(d_nonfinite, 0, (size_t)N * sizeof(uint32_t), s));
+    FLM_HIP(ctx, flm::launch_rotate_clip(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, d_factors, d_out, out_pitch,
+                                         d_nonfinite, s));
+    return 0;
+}
+
+namespace {
+// the context's tile partials for N rows of L, and behind them N factors for a caller who wants none back
+int reserve_l2_work(flm_ctx *ctx, uint64_t work_doubles, int N, double **work, float **spare_factors) {
+    FLM_HIP(ctx, ctx->l2_work.reserve(work_doubles * sizeof(double) + (size_t)N * sizeof(float)));
+    *work = ctx->l2_work.as<double>();
+    *spare_factors = reinterpret_cast<float *>(*work + work_doubles);
+    return 0;
+}
+}  // namespace
+
+int flm_l2_clip(flm_ctx *ctx, const float *x, int N, size_t L, float clip_norm, float *out, float *factors, double *sumsq) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint64_t wd = 0;
+    if (int rc = check_l2(ctx, L, clip_norm, N, &wd)) return rc;
+    if (!x || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    double *work = nullptr;
+    float *spare = nullptr;
+    if (int rc = reserve_l2_work(ctx, wd, N, &work, &spare)) return rc;
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::l2_clip_args(N, L, factors != nullptr, sumsq != nullptr), {x, out, factors, sumsq});
+    if (int rc = hc.begin()) return rc;
+    float *d_factors = factors ? hc.dev<float>(2) : spare;
+    if (int rc = flm_l2_factors_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, clip_norm, work, d_factors, hc.dev<double>(3),
+                                    ctx->stream))
+        return rc;
+    if (int rc = flm_scale_rows_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, d_factors, hc.dev<float>(1), hc.pitch(1) / 4,
+                                    ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+int flm_rotate_clip(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], float clip_norm,
+                    float *out, uint32_t *nonfinite, float *factors, double *sumsq) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    bool range = false;
+    uint64_t L_rot = 0, wd = 0;
+    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (int rc = check_l2(ctx, L, clip_norm, N, &wd)) return rc;
+    if (!x || !out || !key) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    const size_t words = flm::rt::rotate_sign_words(L_rot);
+    FLM_HIP(ctx, ctx->rot_signs.reserve(round_up(words, 4) * sizeof(uint32_t)));
+    double *work = nullptr;
+    float *spare = nullptr;
+    if (int rc = reserve_l2_work(ctx, wd, N, &work, &spare)) return rc;
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::rotate_clip_args(N, L, L_rot, nonfinite != nullptr, factors != nullptr, sumsq != nullptr),
+               {x, out, key, nonfinite, factors, sumsq});
+    if (int rc = hc.begin()) return rc;
+    float *d_factors = factors ? hc.dev<float>(4) : spare;
+    if (int rc = flm_prg_expand_dev(ctx, hc.dev<uint8_t>(2), 1, words, 0, ctx->rot_signs.as<uint32_t>(), round_up(words, 4),
+                                    ctx->stream))
+        return rc;
+    if (int rc = flm_l2_factors_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, clip_norm, work, d_factors, hc.dev<double>(5),
+                                    ctx->stream))
+        return rc;
+    if (int rc = flm_rotate_clip_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, log2_block, ctx->rot_signs.as<uint32_t>(),
+                                     d_factors, hc.dev<float>(1), hc.pitch(1) / 4, hc.dev<uint32_t>(3), ctx->stream))
         return rc;
     return hc.finish();
 }

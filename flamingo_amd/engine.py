@@ -370,11 +370,14 @@ class MaskEngine:
         return int(L_rot.value)
 
     def rotate(self, x: np.ndarray, key, log2_block: int, inverse: bool = False, L: int | None = None,
-               return_nonfinite: bool = False):
+               return_nonfinite: bool = False, clip_norm: float | None = None):
         """The randomised block Hadamard rotation of float32 rows under the 32-byte public `key` (flm_rotate).
         Forward: x (N, L) or (L,) in, (N, L_rot) out, L_rot = round_up(L, 2^log2_block); non-finite inputs become
         +0.0 and, with return_nonfinite, are counted per row.  Inverse: x (N, L_rot) in and the first L parameters
-        out (L is required: the rows' length before the rotation)."""
+        out (L is required: the rows' length before the rotation).
+        clip_norm = C (forward only): every row is first scaled to an L2 norm of at most C, in the same pass
+        (flm_rotate_clip), and the factors (N,) float32 and sums of squares (N,) float64 are returned behind the
+        other results: (out, factors, sumsq), or (out, nonfinite, factors, sumsq)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         one = x.ndim == 1
         if one:
@@ -394,17 +397,58 @@ class MaskEngine:
             raise RuntimeError(f"inverse: x must hold rows of L_rot = {L_rot} floats")
         if inverse and return_nonfinite:
             raise RuntimeError("the inverse rotation counts nothing")
+        if inverse and clip_norm is not None:
+            raise RuntimeError("the inverse rotation clips nothing")
         key = _seeds_array([key] if isinstance(key, (bytes, bytearray)) else key)
         if key.shape[0] != 1:
             raise RuntimeError("one 32-byte rotation key")
         out = np.empty((N, L if inverse else L_rot), dtype=np.float32)
         nonfinite = np.zeros(N, dtype=np.uint32)
+        if clip_norm is not None:
+            self.l2_clip_check(L, clip_norm, N)
+            factors, sumsq = np.empty(N, dtype=np.float32), np.empty(N, dtype=np.float64)
+            rc = self.lib.flm_rotate_clip(self.ctx, p_f32(x), N, L, int(log2_block), p_u8(key), float(clip_norm), p_f32(out),
+                                          p_u32(nonfinite) if return_nonfinite else None, p_f32(factors),
+                                          sumsq.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+            self._check(rc, "flm_rotate_clip")
+            if one:
+                out = out[0]
+            return (out, nonfinite, factors, sumsq) if return_nonfinite else (out, factors, sumsq)
         rc = self.lib.flm_rotate(self.ctx, p_f32(x), N, L, int(log2_block), p_u8(key), int(bool(inverse)), p_f32(out),
                                  p_u32(nonfinite) if return_nonfinite else None)
         self._check(rc, "flm_rotate")
         if one:
             out = out[0]
         return (out, nonfinite) if return_nonfinite else out
+
+    # ------------------------------------- L2 clip in front of the rotation
+    def l2_clip_check(self, L: int, clip_norm: float, N: int = 1) -> int:
+        """The doubles of work space flm_l2_factors_dev needs for N rows of L parameters, N ceil(L / 4096); raises for
+        L = 0, N < 1, a clip_norm that is not finite and positive, or more tiles than one launch takes.  No device
+        call.  flm_l2_clip_check."""
+        work = ctypes.c_uint64(0)
+        self._check(self.lib.flm_l2_clip_check(int(L), float(clip_norm), int(N), ctypes.byref(work)), "flm_l2_clip_check")
+        return int(work.value)
+
+    def l2_clip(self, x: np.ndarray, clip_norm: float):
+        """x (N, L) or (L,) float32 scaled row by row to an L2 norm of at most clip_norm (flm_l2_clip):
+        (out, factors (N,) float32, sumsq (N,) float64), out = x factors[row], factors = min(1, clip_norm /
+        sqrt(sumsq)) by the rule of include/flamingo_hip.h; non-finite inputs count as 0 in sumsq and are scaled
+        like any other (NaN stays NaN)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        if x.ndim != 2:
+            raise RuntimeError("x must be (N, L) or (L,)")
+        N, L = x.shape
+        self.l2_clip_check(L, clip_norm, N)
+        out = np.empty((N, L), dtype=np.float32)
+        factors, sumsq = np.empty(N, dtype=np.float32), np.empty(N, dtype=np.float64)
+        rc = self.lib.flm_l2_clip(self.ctx, p_f32(x), N, L, float(clip_norm), p_f32(out), p_f32(factors),
+                                  sumsq.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        self._check(rc, "flm_l2_clip")
+        return (out[0] if one else out), factors, sumsq
 
     def decode_sum(self, total: np.ndarray, frac_bits: int, count: int = 1) -> np.ndarray:
         """float32(int32(total) / (count * 2^frac_bits)): the ring sum as the mean of `count` contributors."""
@@ -633,6 +677,63 @@ class MaskEngine:
                                      ptr(sign_bits), int(bool(inverse)), ptr(out),
                                      out.stride(0) if N > 1 else out.shape[1], ptr(nonfinite), self._stream_handle(stream))
         self._check(rc, "flm_rotate_dev")
+        return out
+
+    @staticmethod
+    def _float_rows(name: str, t, N: int, n: int) -> int:
+        """The row pitch of a (N, >= n) float32 CUDA tensor with unit column stride."""
+        import torch
+        if t.dim() != 2 or t.shape[0] != N or t.shape[1] < n or t.dtype != torch.float32 or t.stride(1) != 1:
+            raise RuntimeError(f"{name} must be ({N}, >= {n}) float32 with unit column stride")
+        return t.stride(0) if N > 1 else t.shape[1]
+
+    def l2_factors_dev(self, x, L: int, clip_norm: float, work, factors, sumsq=None, stream=None):
+        """Device L2 factors: x (N, >= L) float32 rows at their own stride; work >= l2_clip_check(L, clip_norm, N)
+        float64, the caller's, one per stream in flight; factors (>= N,) float32 and sumsq (>= N,) float64 or None are
+        written.  Two launches enqueued on `stream`; nothing is synchronised.  flm_l2_factors_dev."""
+        import torch
+        N = x.shape[0] if x.dim() == 2 else -1
+        need = self.l2_clip_check(L, clip_norm, N)
+        pitch = self._float_rows("x", x, N, L)
+        for name, t, n, dt in (("work", work, need, torch.float64), ("factors", factors, N, torch.float32),
+                               ("sumsq", sumsq, N, torch.float64)):
+            if t is not None and (t.dim() != 1 or t.shape[0] < n or t.dtype != dt or not t.is_contiguous()):
+                raise RuntimeError(f"{name} must be a contiguous (>= {n},) {dt} tensor")
+        rc = self.lib.flm_l2_factors_dev(self.ctx, _vp(x), pitch, N, int(L), float(clip_norm), _vp(work), _vp(factors),
+                                         _vp(sumsq), self._stream_handle(stream))
+        self._check(rc, "flm_l2_factors_dev")
+        return factors
+
+    def scale_rows_dev(self, x, out, L: int, factors, stream=None):
+        """Device scale: out[row, :L] = x[row, :L] factors[row], float32 rows at their own strides (out may be x);
+        nothing behind L is written.  Enqueued on `stream`; nothing is synchronised.  flm_scale_rows_dev."""
+        import torch
+        N = x.shape[0] if x.dim() == 2 else -1
+        xp, op = self._float_rows("x", x, N, L), self._float_rows("out", out, N, L)
+        if factors.dim() != 1 or factors.shape[0] < N or factors.dtype != torch.float32 or not factors.is_contiguous():
+            raise RuntimeError(f"factors must be a contiguous (>= {N},) float32 tensor")
+        rc = self.lib.flm_scale_rows_dev(self.ctx, _vp(x), xp, N, int(L), _vp(factors), _vp(out), op,
+                                         self._stream_handle(stream))
+        self._check(rc, "flm_scale_rows_dev")
+        return out
+
+    def rotate_clip_dev(self, x, out, L: int, log2_block: int, sign_bits, factors, nonfinite=None, stream=None):
+        """rotate_dev's forward direction with the L2 clip's multiply by factors[row] (l2_factors_dev) in its load:
+        scale_rows_dev followed by rotate_dev, bit for bit, in one pass.  flm_rotate_clip_dev."""
+        import torch
+        L_rot = self.rotate_check(L, log2_block)
+        N = x.shape[0] if x.dim() == 2 else -1
+        xp, op = self._float_rows("x", x, N, L), self._float_rows("out", out, N, L_rot)
+        if sign_bits.element_size() != 4 or sign_bits.numel() < -(-L_rot // 32) or not sign_bits.is_contiguous():
+            raise RuntimeError(f"sign_bits must hold >= {-(-L_rot // 32)} contiguous 32-bit words")
+        if factors.dim() != 1 or factors.shape[0] < N or factors.dtype != torch.float32 or not factors.is_contiguous():
+            raise RuntimeError(f"factors must be a contiguous (>= {N},) float32 tensor")
+        if nonfinite is not None and (nonfinite.dim() != 1 or nonfinite.shape[0] < N or nonfinite.element_size() != 4
+                                      or not nonfinite.is_contiguous()):
+            raise RuntimeError(f"nonfinite must be a contiguous (>= {N},) 32-bit tensor")
+        rc = self.lib.flm_rotate_clip_dev(self.ctx, _vp(x), xp, N, int(L), int(log2_block), _vp(sign_bits), _vp(factors),
+                                          _vp(out), op, _vp(nonfinite), self._stream_handle(stream))
+        self._check(rc, "flm_rotate_clip_dev")
         return out
 
     def prg_expand_dev(self, seeds_dev, out, L: int, slot0: int = 0, stream=None):

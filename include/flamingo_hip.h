@@ -350,6 +350,64 @@ int flm_rotate_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t
 int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], int inverse,
                float *out, uint32_t *nonfinite);
 
+/* ------------------------------ L2 clip of float updates, in front of the rotation */
+
+/* The first step of the same recipe (cpSGD; Kairouz et al., above): every client scales its update to an L2 norm
+ * of at most C before it rotates, rounds and adds noise, so that one client moves the sum by at most C in L2 --
+ * the sensitivity the noise of flm_client_encode_noise_mask is measured against.  The codec's `clip` alone bounds
+ * coordinates, which bounds the L2 norm only by clip sqrt(L).  Turning C into a privacy statement is the caller's
+ * business.  It stands where the reference says "For machine learning, replace it with model weights"
+ * (agent/flamingo/SA_ClientAgent.py:300-304).  Normative, per row of L float32 parameters, clip radius C (float32,
+ * finite, > 0):
+ *   1. squares: d_l = (double)x_l; a NaN or +-Inf input, and every parameter >= L, counts as +0.0 (the rotation's
+ *      own rule: the norm is that of what the rotation transforms); d_l d_l is exact in float64.
+ *   2. the sum S, in an order that depends on L only (not on N, the pitch, the grid or the stream): tiles of 4096
+ *      parameters; in a tile, t = 0..255 adds the squares of parameters 16 t .. 16 t + 15 to +0.0 in index order;
+ *      in each run of 64 consecutive t ("wave"), for off = 1, 2, 4, 8, 16, 32 in that order every a_t becomes
+ *      a_t + a_(t ^ off) at once, after which all 64 are equal; the tile's partial is ((w0 + w1) + w2) + w3 over
+ *      its four waves.  Per row, k = 0..63 adds partials k, k + 64, k + 128, ... to +0.0 in that order, and the
+ *      same six steps over the 64 sums give S.  All adds are float64, round to nearest.
+ *   3. the factor: s = 1.0f if S <= (double)C (double)C (exact in float64; S = 0 included), else
+ *      s = (float)((double)C / sqrt(S)): IEEE double square root and division, then one rounding to float32.
+ *      s <= 1; s may be a float32 subnormal for astronomically large rows (nothing is flushed to zero).
+ *   4. the clip: x'_l = x_l s, one float32 round-to-nearest multiply.  A row with s == 1.0f comes out with its bits,
+ *      -0.0 and subnormals included.  Standalone this is plain IEEE on whatever comes in (NaN stays NaN); fused into
+ *      the forward rotation the multiply stands between the non-finite zeroing and the sign flips (steps 1 and 2
+ *      of the rotation), and because a sign flip commutes exactly with a multiply, flm_rotate_clip gives the bits of
+ *      flm_l2_clip followed by flm_rotate.
+ * Guarantee (inputs and products normal floats): ||x'||_2 <= C (1 + 2^-22): S carries a relative error of at most
+ * about L 2^-53, s one float32 rounding (2^-24), and every product one more (2^-24), which moves the norm by at most
+ * that: together under 2^-22.
+ *
+ * flm_l2_clip_check (SA_ClientAgent.py:300-304): FLM_EINVAL for L = 0, N < 1, or C not finite and positive;
+ * FLM_ERANGE when N ceil(L / 4096) passes 2^31 - 1 workgroups; else *work_doubles = N ceil(L / 4096) (may be NULL).
+ * No context, no device. */
+int flm_l2_clip_check(uint64_t L, float clip_norm, int N, uint64_t *work_doubles);
+/* Steps 1-3 on device rows (SA_ClientAgent.py:300-304): d_factors[row] = s, and d_sumsq[row] = S unless NULL.  Two
+ * launches on `stream`; nothing is synchronised.  x_pitch (floats) a multiple of 4 and >= round_up(L, 4), d_x 16-byte
+ * aligned; what lies behind L in a row is never read as input.  d_work: *work_doubles doubles of the caller's,
+ * written and read by this call alone, one buffer per stream in flight (the context keeps none: two streams would
+ * race on it). */
+int flm_l2_factors_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, float clip_norm, double *d_work,
+                       float *d_factors, double *d_sumsq, void *stream);
+/* Step 4 on device rows (SA_ClientAgent.py:300-304): d_out[row][l] = d_x[row][l] d_factors[row] for l < L, nothing
+ * behind L written.  Pitches multiples of 4 and >= round_up(L, 4), pointers 16-byte aligned; d_out may be d_x at
+ * equal pitches.  Enqueued on `stream`; nothing is synchronised. */
+int flm_scale_rows_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, const float *d_factors,
+                       float *d_out, size_t out_pitch, void *stream);
+/* The forward rotation with step 4 in its load (SA_ClientAgent.py:300-304): flm_rotate_dev's forward arguments, rules
+ * for pitches, alignment, in place and d_nonfinite, plus d_factors (N floats, from flm_l2_factors_dev on the same
+ * stream or earlier).  Equals flm_scale_rows_dev followed by flm_rotate_dev bit for bit, in one pass over the row. */
+int flm_rotate_clip_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
+                        const uint32_t *d_sign_bits, const float *d_factors, float *d_out, size_t out_pitch,
+                        uint32_t *d_nonfinite, void *stream);
+/* The host-pointer forms, synchronous (SA_ClientAgent.py:300-304).  flm_l2_clip: x and out N x L packed (out may be
+ * x), factors N floats or NULL, sumsq N doubles or NULL: the factors, then the scale.  flm_rotate_clip: x N x L, out
+ * N x L_rot, nonfinite as flm_rotate's: the factors, then the fused forward rotation under `key`. */
+int flm_l2_clip(flm_ctx *ctx, const float *x, int N, size_t L, float clip_norm, float *out, float *factors, double *sumsq);
+int flm_rotate_clip(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], float clip_norm,
+                    float *out, uint32_t *nonfinite, float *factors, double *sumsq);
+
 /* Device-resident PRG expansion: d_out[k*pitch + l] = PRG(seed k)[slot0 + l]. */
 int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, uint64_t slot0,
                        uint32_t *d_out, size_t pitch, void *stream);

@@ -67,6 +67,12 @@ for _name, _res, _args in (
         ("flm_decode_unpack_noise", _int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _f32p]),
         ("flm_store_unmask_unpack_noise_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
                                                      ctypes.c_int64, _f32p]),
+        ("flm_rotate_check", _int, [ctypes.c_uint64, _int, ctypes.POINTER(ctypes.c_uint64)]),
+        ("flm_rotate", _int, [_vp, _f32p, _int, _sz, _int, _u8p, _int, _f32p, _u32p]),
+        ("flm_l2_clip_check", _int, [ctypes.c_uint64, ctypes.c_float, _int, ctypes.POINTER(ctypes.c_uint64)]),
+        ("flm_l2_clip", _int, [_vp, _f32p, _int, _sz, ctypes.c_float, _f32p, _f32p, ctypes.POINTER(ctypes.c_double)]),
+        ("flm_rotate_clip", _int, [_vp, _f32p, _int, _sz, _int, _u8p, ctypes.c_float, _f32p, _u32p, _f32p,
+                                   ctypes.POINTER(ctypes.c_double)]),
         ("flm_hash_to_curve", _int, [_vp, _u8p, _u32p, _int, _u8p, _u32p]),
         ("flm_hash_to_curve_decimal", _int, [_vp, ctypes.c_uint32, _int, _u8p, _u32p])):
     _f = getattr(_lib, _name)
@@ -456,6 +462,61 @@ def client_encode_noise_mask(seeds, signs, L, x, frac_bits, clip, pack=1, dither
         raise RuntimeError("pack must be 1, 2 or 4")
     return _encode_mask(_lib.flm_client_encode_noise_mask, lambda d, z: (int(pack), d, int(noise_bits), z), seeds, signs, L,
                         x, frac_bits, clip, pack, dither, noise)
+
+
+def l2_clip_check(L, clip_norm, N=1):
+    """Raise unless N updates of L parameters can be clipped to the L2 norm clip_norm (finite and positive; L > 0,
+    N >= 1, at most 2^31 - 1 tiles of 4096 parameters in all); returns N ceil(L / 4096), the doubles of work space
+    the device form takes.  No device call."""
+    work = ctypes.c_uint64(0)
+    if _lib.flm_l2_clip_check(int(L), float(clip_norm), int(N), ctypes.byref(work)):
+        raise RuntimeError(_lib.flm_last_error(None).decode())
+    return int(work.value)
+
+
+def l2_clip(x, clip_norm):
+    """One client's float32 update ("replace it with model weights", SA_ClientAgent.py:300-304) scaled to an L2 norm of
+    at most clip_norm, in front of client_encode_*mask when no rotation is used: (x s, s, S) with S the sum of the
+    squares in float64 (non-finite elements count as 0) and s = 1 if S <= clip_norm^2, else float32(clip_norm /
+    sqrt(S)).  One client then moves the sum by at most clip_norm (1 + 2^-22) in L2."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 1:
+        raise RuntimeError("vector length error")
+    out, s, S = np.empty_like(x), np.zeros(1, np.float32), np.zeros(1, np.float64)
+    _check(_lib.flm_l2_clip(_context(), x.ctypes.data_as(_f32p), 1, x.shape[0], float(clip_norm), out.ctypes.data_as(_f32p),
+                            s.ctypes.data_as(_f32p), S.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out, float(s[0]), float(S[0])
+
+
+def rotate(x, key, log2_block, inverse=False, L=None, clip_norm=None):
+    """The randomised block Hadamard rotation under the 32-byte public `key`, blocks of 2^log2_block parameters (4..12).
+    Forward, the client's step in front of client_encode_*mask (SA_ClientAgent.py:300-304): x float32[L] ->
+    (float32[L_rot], non-finite inputs zeroed), L_rot = L rounded up to whole blocks, which is then the L of the encode;
+    with clip_norm the update is first scaled to that L2 norm in the same pass, as l2_clip does:
+    (float32[L_rot], non-finite, s, S).  Inverse, the server's step behind decode_sum / decode_unpack
+    (SA_ServiceAgent.py:538-540, 605): x float32[L_rot] and L, the length before the rotation -> float32[L]."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 1 or len(key) != 32:
+        raise RuntimeError("one float32 vector and a 32-byte key")
+    if inverse and (L is None or clip_norm is not None):
+        raise RuntimeError("the inverse rotation takes L and no clip_norm")
+    L = int(L) if inverse else x.shape[0]
+    L_rot = ctypes.c_uint64(0)
+    if _lib.flm_rotate_check(L, int(log2_block), ctypes.byref(L_rot)):
+        raise RuntimeError(_lib.flm_last_error(None).decode())
+    if inverse and x.shape[0] != L_rot.value:
+        raise RuntimeError("vector length error")
+    k = np.frombuffer(bytes(key), np.uint8).copy()
+    out, bad = np.empty(L if inverse else L_rot.value, np.float32), np.zeros(1, np.uint32)
+    if clip_norm is None:
+        _check(_lib.flm_rotate(_context(), x.ctypes.data_as(_f32p), 1, L, int(log2_block), k.ctypes.data_as(_u8p),
+                               int(bool(inverse)), out.ctypes.data_as(_f32p), None if inverse else bad.ctypes.data_as(_u32p)))
+        return out if inverse else (out, int(bad[0]))
+    s, S = np.zeros(1, np.float32), np.zeros(1, np.float64)
+    _check(_lib.flm_rotate_clip(_context(), x.ctypes.data_as(_f32p), 1, L, int(log2_block), k.ctypes.data_as(_u8p),
+                                float(clip_norm), out.ctypes.data_as(_f32p), bad.ctypes.data_as(_u32p),
+                                s.ctypes.data_as(_f32p), S.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out, int(bad[0]), float(s[0]), float(S[0])
 
 
 class VectorStore:

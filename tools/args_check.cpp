@@ -155,7 +155,15 @@ static void check_round_lists() {
                     CHECK(!rotate_error(L, h, &range, &L_rot) && L_rot % (1u << h) == 0 && L_rot >= L && L_rot - L < (1u << h));
                     through_bounce(rotate_args(N, L, L_rot, opt));
                     if (!opt) through_bounce(rotate_args(N, L_rot, L, false));
+                    // flm_rotate_clip and flm_l2_clip: the optional outputs together or none of them
+                    through_bounce(rotate_clip_args(N, L, L_rot, opt, opt, opt));
+                    through_bounce(l2_clip_args(N, L, opt, !opt));
                 }
+    const ArgList rc = rotate_clip_args(3, 5, 16, true, true, false), lc = l2_clip_args(3, 5, false, true);
+    CHECK(rc.n == 6 && rc.a[0].width == 20 && rc.a[1].width == 64 && rc.a[1].is_out && rc.a[3].present && rc.a[4].present &&
+          rc.a[4].is_out && rc.a[4].width == 12 && rc.a[4].slot == ec_flags && !rc.a[5].present && !names_slot_twice(rc));
+    CHECK(lc.n == 4 && lc.a[0].slot == rows && lc.a[1].slot == out && lc.a[1].in_place && lc.a[1].width == 20 && !lc.a[2].present &&
+          lc.a[3].present && lc.a[3].is_out && lc.a[3].width == 24 && lc.a[3].slot == ec_dig && !names_slot_twice(lc));
     const ArgList ro = rotate_args(3, 5, 16, true), ri = rotate_args(3, 16, 5, false);
     CHECK(ro.n == 4 && ro.a[0].slot == rows && ro.a[0].width == 20 && ro.a[0].rows == 3 && ro.a[0].in_place && !ro.a[0].is_out &&
           ro.a[1].slot == out && ro.a[1].width == 64 && ro.a[1].is_out && ro.a[1].in_place && ro.a[2].width == 32 &&
@@ -272,6 +280,15 @@ static void check_round_rules() {
     CHECK(rotate_error(~0ull, 3, &range, &L_rot) && !range);                               // the block before the length
     CHECK(rotate_sign_words(16) == 1 && rotate_sign_words(32) == 1 && rotate_sign_words(48) == 2);
     CHECK(!rotate_launch_error(0x7fffffffull) && rotate_launch_error(0x80000000ull));
+    // the L2 clip's rule: L > 0, N >= 1, a finite positive radius, N ceil(L / 4096) <= 2^31 - 1 tiles
+    uint64_t work = 0;
+    CHECK(!l2_clip_error(1, 1.0f, 1, &range, &work) && work == 1 && !l2_clip_error(4097, 0.5f, 3, &range, &work) && work == 6);
+    CHECK(l2_clip_error(0, 1.0f, 1, &range, &work) && !range && l2_clip_error(5, 1.0f, 0, &range, &work) && !range);
+    for (float c : {0.0f, -1.0f, INFINITY, NAN}) CHECK(l2_clip_error(5, c, 1, &range, &work) && !range);
+    CHECK(!l2_clip_error(4096ull * 0x7fffffffull, 1.0f, 1, &range, &work) && work == 0x7fffffffull);
+    CHECK(l2_clip_error(4096ull * 0x7fffffffull + 1, 1.0f, 1, &range, &work) && range);
+    CHECK(l2_clip_error(~0ull, 1.0f, 1, &range, &work) && range && l2_clip_error(~0ull, 1.0f, 0, &range, &work) && !range);
+    CHECK(l2_clip_error(4096ull << 20, 1.0f, 2048, &range, &work) && range);
     CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));
     CHECK(!slot_range_error(0, 1ull << 36) && slot_range_error(16, 1ull << 36) && slot_range_error(1ull << 36, 1) &&
           !slot_range_error(1ull << 36, 0) && slot_range_error(~0ull, 2));
