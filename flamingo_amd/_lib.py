@@ -17,6 +17,7 @@ _i8p = ctypes.POINTER(ctypes.c_int8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _f32p = ctypes.POINTER(ctypes.c_float)
+_f64p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _u64 = ctypes.c_uint64
@@ -67,9 +68,8 @@ SIGNATURES = {
     "flm_l2_factors_dev": (_int, [_vp, _vp, _sz, _int, _sz, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "flm_scale_rows_dev": (_int, [_vp, _vp, _sz, _int, _sz, _vp, _vp, _sz, _vp]),
     "flm_rotate_clip_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "flm_l2_clip": (_int, [_vp, _f32p, _int, _sz, ctypes.c_float, _f32p, _f32p, ctypes.POINTER(ctypes.c_double)]),
-    "flm_rotate_clip": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, ctypes.c_float, _f32p, _u32p, _f32p,
-                               ctypes.POINTER(ctypes.c_double)]),
+    "flm_l2_clip": (_int, [_vp, _f32p, _int, _sz, ctypes.c_float, _f32p, _f32p, _f64p]),
+    "flm_rotate_clip": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, ctypes.c_float, _f32p, _u32p, _f32p, _f64p]),
     "flm_prg_expand_dev": (_int, [_vp, _vp, _int, _sz, _u64, _vp, _sz, _vp]),
     "flm_check_signs": (_int, [_vp, ctypes.POINTER(_int)]),
     "flm_last_plan": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
@@ -186,6 +186,10 @@ def p_u32(a):
 
 def p_f32(a):
     return a.ctypes.data_as(_f32p)
+
+
+def p_f64(a):
+    return a.ctypes.data_as(_f64p)
 
 
 def p_i64(a):

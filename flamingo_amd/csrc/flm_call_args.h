@@ -68,6 +68,15 @@ inline const char *align16_error(std::initializer_list<const void *> dev) {
     for (const void *p : dev) all |= (uintptr_t)p;
     return all & 15 ? "device arrays must be 16-byte aligned" : nullptr;
 }
+// the L2 clip's smaller accesses (NULL passes): the factors of a call, 4 bytes each ...
+inline const char *align4_error(const void *factors) {
+    return (uintptr_t)factors & 3 ? "factors must be 4-byte aligned" : nullptr;
+}
+// ... and, in the call that also takes doubles, those at 8 bytes: one text for the three arrays
+inline const char *l2_factors_align_error(const void *work, const void *sumsq, const void *factors) {
+    return (((uintptr_t)work | (uintptr_t)sumsq) & 7) || align4_error(factors)
+               ? "work and sumsq must be 8-byte aligned, factors 4-byte aligned" : nullptr;
+}
 
 inline const char *frac_bits_error(int frac_bits) {
     return frac_bits < 0 || frac_bits > 30 ? "frac_bits outside 0..30" : nullptr;
@@ -163,10 +172,10 @@ inline const char *rotate_error(uint64_t L, int log2_block, bool *range, uint64_
 }
 // words of sign stream for a rotated row
 constexpr uint64_t rotate_sign_words(uint64_t L_rot) { return (L_rot + 31) / 32; }
-// rotate_kernel's one-dimensional grid of flm::rotate_groups workgroups
-inline const char *rotate_launch_error(uint64_t groups) {
-    return groups > 0x7fffffffull ? "more than 2^31 - 1 4096-parameter tiles" : nullptr;
-}
+// rotate_kernel's, and the L2 kernels', one-dimensional grid of a workgroup per (row, tile)
+static_assert(flm::kFloatTile == 4096, "the text below names the tile");
+constexpr const char *kTooManyFloatTiles = "more than 2^31 - 1 4096-parameter tiles";
+inline const char *rotate_launch_error(uint64_t groups) { return groups > 0x7fffffffull ? kTooManyFloatTiles : nullptr; }
 
 // flm_l2_clip_check, flm_l2_factors_dev, flm_scale_rows_dev, flm_l2_clip, flm_rotate_clip: the L2 clip's one rule.
 // N >= 1 rows of L > 0 parameters, a clip radius that is finite and positive; one workgroup per (row, 4096-parameter
@@ -177,11 +186,9 @@ inline const char *l2_clip_error(uint64_t L, float clip_norm, int N, bool *range
     if (L == 0) return "a row of no parameters";
     if (N < 1) return "N must be at least 1";
     if (!(clip_norm > 0.0f) || !std::isfinite(clip_norm)) return "clip_norm must be finite and positive";
-    const uint64_t tiles = L / 4096 + (L % 4096 ? 1 : 0);
-    if (tiles > 0x7fffffffull / (uint64_t)N) {
-        *range = true;
-        return "more than 2^31 - 1 4096-parameter tiles";
-    }
+    const uint64_t tiles = flm::float_tiles(L);
+    *range = tiles > 0x7fffffffull / (uint64_t)N;
+    if (*range) return kTooManyFloatTiles;
     *work_doubles = (uint64_t)N * tiles;
     return nullptr;
 }
@@ -389,14 +396,15 @@ inline ArgList client_encode_mask_args(size_t N, size_t K, size_t L, size_t Lw, 
 inline ArgList decode_unpack_args(size_t L, size_t Lw) {
     return {{in_place(arg_in(Lw * 4, rows)), in_place(arg_out(L * 4, out))}, 2};
 }
-// flm_rotate: x (N rows of L_in floats), out (N rows of L_out floats), key, nonfinite; forward L_in = L and L_out =
-// L_rot, the inverse the other way round.  x and out in place as the decode's, rows at the in-place pitch of
-// round_up(width, 16) bytes, which is what rotate_kernel's 16-byte accesses need.  The sign words the key expands
-// to live in a buffer of the context that no list names (flm_ctx::rot_signs).
-inline ArgList rotate_args(size_t N, size_t L_in, size_t L_out, bool nonfinite) {
+// flm_rotate, flm_rotate_clip: x (N rows of L_in floats), out (N rows of L_out floats), key, nonfinite, and the clip's
+// factors and sumsq as flm_l2_clip's (absent for the plain rotation); forward L_in = L and L_out = L_rot, the inverse
+// the other way round.  x and out in place as the decode's, rows at the in-place pitch of round_up(width, 16) bytes,
+// which is what rotate_kernel's 16-byte accesses need.  The sign words the key expands to live in a buffer of the
+// context that no list names (flm_ctx::rot_signs).
+inline ArgList rotate_args(size_t N, size_t L_in, size_t L_out, bool nonfinite, bool factors, bool sumsq) {
     return {{in_place(pitched(arg_in(L_in * 4, rows), N, host_row_pitch(L_in))),
              in_place(pitched(arg_out(L_out * 4, out), N, host_row_pitch(L_out))), arg_in(32, seeds),
-             arg_out(N * 4, bytes_out, nonfinite)}, 4};
+             arg_out(N * 4, bytes_out, nonfinite), arg_out(N * 4, ec_flags, factors), arg_out(N * 8, ec_dig, sumsq)}, 6};
 }
 // flm_l2_clip: x and out (N rows of L floats, in place as the rotation's), factors (N floats), sumsq (N doubles).
 // The tile partials, and the factors when the caller wants none back, live in a buffer of the context that no list
@@ -405,12 +413,6 @@ inline ArgList l2_clip_args(size_t N, size_t L, bool factors, bool sumsq) {
     return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))),
              in_place(pitched(arg_out(L * 4, out), N, host_row_pitch(L))), arg_out(N * 4, ec_flags, factors),
              arg_out(N * 8, ec_dig, sumsq)}, 4};
-}
-// flm_rotate_clip: flm_rotate's forward list, then factors and sumsq as flm_l2_clip's
-inline ArgList rotate_clip_args(size_t N, size_t L, size_t L_rot, bool nonfinite, bool factors, bool sumsq) {
-    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))),
-             in_place(pitched(arg_out(L_rot * 4, out), N, host_row_pitch(L_rot))), arg_in(32, seeds),
-             arg_out(N * 4, bytes_out, nonfinite), arg_out(N * 4, ec_flags, factors), arg_out(N * 8, ec_dig, sumsq)}, 6};
 }
 // seeds, out (K rows)
 inline ArgList prg_expand_args(size_t K, size_t L) {

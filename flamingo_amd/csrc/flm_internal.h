@@ -69,21 +69,18 @@ hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int
 // Randomised block Hadamard rotation (rotate_kernel): rows of L parameters taken as L_rot = round_up(L, 2^log2_block),
 // log2_block in 4..12; forward reads L floats a row (up to round_up(L, 4) of them, 16 bytes at a time) and writes L_rot,
 // inverse reads L_rot and writes L; d_sign_bits ceil(L_rot / 32) words; d_out may be d_x at equal pitches; d_nonfinite
-// (forward only) N words, zeroed by the caller, or NULL.  One workgroup per (row, 4096-parameter tile) of a
-// one-dimensional grid (rotate_groups(N, L_rot) of them, at most 2^31 - 1).
+// (forward only) N words, zeroed by the caller, or NULL.  One workgroup per (row, kFloatTile-parameter tile) of a
+// one-dimensional grid (rotate_groups(N, L_rot) of them, at most 2^31 - 1).  d_factors NULL: the rotation alone; else
+// (forward only, the inverse with factors is refused) the L2 clip's multiply rides in the load (rotate_kernel<false,
+// PHASES, true>): every finite input times d_factors[row] first, everything else as without.
 uint64_t rotate_groups(int N, uint64_t L_rot);
 hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
                          const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
-                         uint32_t *d_nonfinite, hipStream_t stream);
-// ... and the forward rotation with the L2 clip's multiply in its load (rotate_kernel<false, PHASES, true>): every
-// finite input times d_factors[row] first; everything else as launch_rotate's forward direction
-hipError_t launch_rotate_clip(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
-                              const uint32_t *d_sign_bits, const float *d_factors, float *d_out, uint64_t out_pitch,
-                              uint32_t *d_nonfinite, hipStream_t stream);
-// L2 clip (l2_sumsq_kernel, l2_factor_kernel, scale_rows_kernel): rows of L > 0 floats, read 16 bytes at a time as the
-// rotation reads them.  launch_l2_factors: d_work N l2_tiles(L) doubles (one partial per 4096-parameter tile, written
-// then read), d_factors N floats, d_sumsq N doubles or NULL; two launches.  launch_scale_rows: d_out = d_x
-// d_factors[row], d_out may be d_x at equal pitches.  One workgroup per (row, tile), at most 2^31 - 1 of them.
+                         uint32_t *d_nonfinite, const float *d_factors, hipStream_t stream);
+// L2 clip (l2_sumsq_kernel, l2_factor_kernel, scale_rows_kernel): rows of L > 0 floats, read through the rotation's
+// own row read.  launch_l2_factors: d_work N l2_tiles(L) doubles (one partial per tile, written then read),
+// d_factors N floats, d_sumsq N doubles or NULL; two launches.  launch_scale_rows: d_out = d_x d_factors[row], d_out
+// may be d_x at equal pitches.  One workgroup per (row, tile), at most 2^31 - 1 of them.
 uint64_t l2_tiles(uint64_t L);
 hipError_t launch_l2_factors(const float *d_x, uint64_t x_pitch, int N, uint64_t L, float clip_norm, double *d_work,
                              float *d_factors, double *d_sumsq, hipStream_t stream);

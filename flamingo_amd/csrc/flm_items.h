@@ -11,6 +11,10 @@ constexpr int kWaveSlots = 1024;
 constexpr int kWavesPerGroup = 16;          // 1024-thread workgroups
 constexpr int kThreads = 64 * kWavesPerGroup;
 
+// The float front end (rotate_kernel, the L2 clip's kernels): one workgroup per 4096-parameter tile of a row.
+constexpr uint64_t kFloatTile = 4096;
+constexpr uint64_t float_tiles(uint64_t L) { return L / kFloatTile + (L % kFloatTile ? 1 : 0); }
+
 // Per-seed schedule, built on the device by seed_schedule_kernel: the key, the
 // sign folded into an XOR constant, and everything of ChaCha's first double
 // round that does not depend on the block counter (block counter high word is

@@ -1307,16 +1307,49 @@ __device__ __forceinline__ float rot_flip(float v, uint32_t bits, int j) {
     return __uint_as_float(__float_as_uint(v) ^ ((bits >> j & 1u) << 31));
 }
 
+// The float front end's thread geometry: a workgroup takes one tile of a row, 16 parameters a thread.
+static_assert(256 * 16 == kFloatTile, "256 threads x 16 parameters are one tile");
+
+// NaN or +-Inf: what the forward rotation, and the clip in front of it, take as +0.0
+__device__ __forceinline__ bool rot_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// The forward read of a row of L floats: v = parameters p0 .. p0 + 15 (p0 a multiple of 16) as four 16-byte loads,
+// 0.0 for every parameter at or past L (a predicate per element: the padding of a row may hold anything).
+// rotate_kernel and l2_sumsq_kernel both read a row through this one body and rot_nonfinite, so the clip's sum is
+// over exactly the values the rotation sees.
+__device__ __forceinline__ void rot_read16(const float *xr, uint64_t p0, uint64_t L, float (&v)[16]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t s = p0 + 4u * j;
+        // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+        const float4 q = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[4 * j] = s < L ? q.x : 0.0f, v[4 * j + 1] = s + 1 < L ? q.y : 0.0f;
+        v[4 * j + 2] = s + 2 < L ? q.z : 0.0f, v[4 * j + 3] = s + 3 < L ? q.w : 0.0f;
+    }
+}
+
+// Four results at parameter s of a row of L, s < L a multiple of 4: one 16-byte store, the last quad of a row element
+// by element (nothing at or behind L is written).
+__device__ __forceinline__ void rot_store4(float *orow, uint64_t s, uint64_t L, float4 q) {
+    if (s + 3 < L) {
+        *reinterpret_cast<float4 *>(orow + s) = q;
+    } else {
+        orow[s] = q.x;
+        if (s + 1 < L) orow[s + 1] = q.y;
+        if (s + 2 < L) orow[s + 2] = q.z;
+    }
+}
+
 // out = the rotation of x, rows of L parameters taken as L_rot = round_up(L, 2^h): forward reads L floats a row
-// (a predicate per element past L: the padding of a row may hold anything) and writes L_rot, inverse reads L_rot and
-// writes the L.  Workgroup g = (row, 4096-parameter tile) = (g / tiles, g % tiles) of a one-dimensional grid; a tile
-// holds whole blocks.  Thread t loads parameters 16 t .. 16 t + 15 (four 16-byte loads) and runs stages 0..3 in
-// registers; PHASES = ceil(h / 4) > 1: the tile goes through LDS (rot_sw above) and the thread takes the 16 elements
-// that differ in index bits 4..7 for stages 4..7, and PHASES = 3 once more those in bits 8..11.  The scaled values
-// go back to the words they came from and the tile is stored from LDS in order, 16 bytes a thread and 4 KiB
-// contiguous per store instruction of the workgroup (PHASES = 1 stores its registers, 64 bytes contiguous a thread).
-// Every global load of a tile precedes its first barrier, and a thread of PHASES = 1 writes what it alone read, so
-// out may be x.  sign_bits: ceil(L_rot / 32) words of PRG(key), bit l % 32 of word l / 32 flips parameter l.
+// (rot_read16) and writes L_rot, inverse reads L_rot and writes the L (rot_store4).  Workgroup g = (row,
+// 4096-parameter tile) = (g / tiles, g % tiles) of a one-dimensional grid; a tile holds whole blocks.  Thread t
+// loads parameters 16 t .. 16 t + 15 (four 16-byte loads) and runs stages 0..3 in registers; PHASES = ceil(h / 4)
+// > 1: the tile goes through LDS (rot_sw above) and the thread takes the 16 elements that differ in index bits 4..7
+// for stages 4..7, and PHASES = 3 once more those in bits 8..11.  The scaled values go back to the words they came
+// from and the tile is stored from LDS in order, 16 bytes a thread and 4 KiB contiguous per store instruction of
+// the workgroup (PHASES = 1 stores its registers, 64 bytes contiguous a thread).  Every global load of a tile
+// precedes its first barrier, and a thread of PHASES = 1 writes what it alone read, so out may be x.  sign_bits:
+// ceil(L_rot / 32) words of PRG(key), bit l % 32 of word l / 32 flips parameter l.
 // nonfinite[row] (forward, zeroed by the call, or NULL): the threads' counts meet in LDS, the first wave adds them
 // up and its first lane adds a non-zero total with one atomic.
 // FACTOR (forward only): the L2 clip rides in the load (the section below): every finite input is first multiplied
@@ -1335,7 +1368,7 @@ __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_
     float *lds = reinterpret_cast<float *>(lds4);
     const int t = threadIdx.x;
     const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
-    const uint64_t base = (uint64_t)tile * 4096u;
+    const uint64_t base = (uint64_t)tile * kFloatTile;
     const float *xr = x + (uint64_t)row * x_pitch;
     float *orow = out + (uint64_t)row * out_pitch;
 
@@ -1347,13 +1380,7 @@ __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_
             if (s >= L) return;
             const uint32_t b = sign_bits[s >> 5] >> (s & 31);
             q = make_float4(rot_flip(q.x, b, 0), rot_flip(q.y, b, 1), rot_flip(q.z, b, 2), rot_flip(q.w, b, 3));
-            if (s + 3 < L) {
-                *reinterpret_cast<float4 *>(orow + s) = q;
-            } else {
-                orow[s] = q.x;
-                if (s + 1 < L) orow[s + 1] = q.y;
-                if (s + 2 < L) orow[s + 2] = q.z;
-            }
+            rot_store4(orow, s, L, q);
         }
     };
 
@@ -1370,17 +1397,10 @@ __global__ __launch_bounds__(256) void rotate_kernel(const float *x, uint64_t x_
         const uint32_t sb = p0 < L_rot ? sign_bits[p0 >> 5] >> (p0 & 16) : 0u;
         float rf = 1.0f;
         if constexpr (FACTOR) rf = row_factor[row];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t s = p0 + 4u * j;
-            // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
-            const float4 q = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
-            v[4 * j] = s < L ? q.x : 0.0f, v[4 * j + 1] = s + 1 < L ? q.y : 0.0f;
-            v[4 * j + 2] = s + 2 < L ? q.z : 0.0f, v[4 * j + 3] = s + 3 < L ? q.w : 0.0f;
-        }
+        rot_read16(xr, p0, L, v);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const bool nf = (__float_as_uint(v[j]) & 0x7f800000u) == 0x7f800000u;  // NaN or +-Inf
+            const bool nf = rot_nonfinite(v[j]);
             bad += nf ? 1u : 0u;
             if constexpr (FACTOR) v[j] = rot_flip(nf ? 0.0f : v[j] * rf, sb, j);
             else v[j] = rot_flip(nf ? 0.0f : v[j], sb, j);
@@ -1447,9 +1467,9 @@ __device__ __forceinline__ double l2_wave_sum(double a) {
 }
 
 // work[row tiles + tile] = the tile's partial sum of squares.  Workgroup g = (row, 4096-parameter tile) and thread t
-// of it takes parameters 16 t .. 16 t + 15 of the tile with four 16-byte loads, as rotate_kernel does, with the same
-// predicate per element past L and the same non-finite rule: what the rotation reads as +0.0 counts as +0.0.  The
-// square of a float is exact in float64, so fma(d, d, acc) is acc + d d.
+// of it takes parameters 16 t .. 16 t + 15 of the tile through rot_read16 and rot_nonfinite, rotate_kernel's own read:
+// what the rotation reads as +0.0 counts as +0.0.  The square of a float is exact in float64, so fma(d, d, acc) is
+// acc + d d, added in the order v[0] .. v[15].
 __global__ __launch_bounds__(256) void l2_sumsq_kernel(const float *__restrict__ x, uint64_t x_pitch, uint64_t L,
                                                        uint32_t tiles, double *__restrict__ work) {
 #pragma clang fp contract(off)
@@ -1457,20 +1477,13 @@ __global__ __launch_bounds__(256) void l2_sumsq_kernel(const float *__restrict__
     const int t = threadIdx.x;
     const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
     const float *xr = x + (uint64_t)row * x_pitch;
-    const uint64_t p0 = (uint64_t)tile * 4096u + 16u * (uint64_t)t;
+    float v[16];
+    rot_read16(xr, (uint64_t)tile * kFloatTile + 16u * (uint64_t)t, L, v);
     double acc = 0.0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint64_t s = p0 + 4u * j;
-        // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
-        const float4 q = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float e[4] = {s < L ? q.x : 0.0f, s + 1 < L ? q.y : 0.0f, s + 2 < L ? q.z : 0.0f, s + 3 < L ? q.w : 0.0f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool nf = (__float_as_uint(e[i]) & 0x7f800000u) == 0x7f800000u;  // NaN or +-Inf
-            const double d = (double)(nf ? 0.0f : e[i]);
-            acc = fma(d, d, acc);
-        }
+    for (int j = 0; j < 16; ++j) {
+        const double d = (double)(rot_nonfinite(v[j]) ? 0.0f : v[j]);
+        acc = fma(d, d, acc);
     }
     acc = l2_wave_sum(acc);
     if ((t & 63) == 0) wave_sums[t >> 6] = acc;
@@ -1497,7 +1510,7 @@ __global__ __launch_bounds__(64) void l2_factor_kernel(const double *__restrict_
 
 // out = x factors[row] over the L parameters of every row, one float32 multiply each (plain IEEE: NaN stays NaN, a
 // factor of 1 leaves the bits).  Workgroup g = (row, 4096-parameter tile); thread t takes the quads t, t + 256,
-// t + 512, t + 768 of the tile, 16 bytes a load and a store, the last quad of a row element by element.  A thread
+// t + 512, t + 768 of the tile, 16 bytes a load and a store (rot_store4 at the end of a row).  A thread
 // writes what it alone read, so out may be x at equal pitches.
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float *x, uint64_t x_pitch, uint64_t L, uint32_t tiles,
                                                          const float *__restrict__ factors, float *out,
@@ -1510,21 +1523,13 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(const float *x, uint64_
     float4 q[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const uint64_t s = (uint64_t)tile * 4096u + 1024u * m + 4u * threadIdx.x;
+        const uint64_t s = (uint64_t)tile * kFloatTile + 1024u * m + 4u * threadIdx.x;
         q[m] = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const uint64_t s = (uint64_t)tile * 4096u + 1024u * m + 4u * threadIdx.x;
-        if (s >= L) continue;
-        const float4 r = make_float4(q[m].x * f, q[m].y * f, q[m].z * f, q[m].w * f);
-        if (s + 3 < L) {
-            *reinterpret_cast<float4 *>(orow + s) = r;
-        } else {
-            orow[s] = r.x;
-            if (s + 1 < L) orow[s + 1] = r.y;
-            if (s + 2 < L) orow[s + 2] = r.z;
-        }
+        const uint64_t s = (uint64_t)tile * kFloatTile + 1024u * m + 4u * threadIdx.x;
+        if (s < L) rot_store4(orow, s, L, make_float4(q[m].x * f, q[m].y * f, q[m].z * f, q[m].w * f));
     }
 }
 
@@ -1579,12 +1584,11 @@ hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, fl
     return hipGetLastError();
 }
 
-uint64_t rotate_groups(int N, uint64_t L_rot) { return (uint64_t)N * ((L_rot + 4095) / 4096); }
+uint64_t rotate_groups(int N, uint64_t L_rot) { return (uint64_t)N * float_tiles(L_rot); }
 
-// d_factors: the fused L2 clip's factor per row (forward only), or NULL for the rotation alone
-static hipError_t launch_rotate_any(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
-                                    const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
-                                    uint32_t *d_nonfinite, const float *d_factors, hipStream_t stream) {
+hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
+                         const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
+                         uint32_t *d_nonfinite, const float *d_factors, hipStream_t stream) {
     const uint64_t groups = rotate_groups(N, L_rot);
     if (groups == 0) return hipSuccess;
     if (groups > 0x7fffffffull || log2_block < 4 || log2_block > 12 || L_rot % (1u << log2_block) || L > L_rot ||
@@ -1595,36 +1599,18 @@ static hipError_t launch_rotate_any(const float *d_x, uint64_t x_pitch, int N, u
     float rsqrt2;
     memcpy(&rsqrt2, &rsqrt2_bits, sizeof rsqrt2);
     const float scale = ldexpf(log2_block % 2 ? rsqrt2 : 1.0f, -(log2_block / 2));
-    // [inverse][phases - 1], phases = ceil(h / 4)
-    static constexpr decltype(&rotate_kernel<false, 1, false>) kernels[2][3] = {
+    // [forward, inverse, forward with the clip's multiply in its load][phases - 1], phases = ceil(h / 4)
+    static constexpr decltype(&rotate_kernel<false, 1, false>) kernels[3][3] = {
         {rotate_kernel<false, 1, false>, rotate_kernel<false, 2, false>, rotate_kernel<false, 3, false>},
-        {rotate_kernel<true, 1, false>, rotate_kernel<true, 2, false>, rotate_kernel<true, 3, false>}};
-    // the forward rotation with the clip's multiply in its load
-    static constexpr decltype(&rotate_kernel<false, 1, true>) clip_kernels[3] = {
-        rotate_kernel<false, 1, true>, rotate_kernel<false, 2, true>, rotate_kernel<false, 3, true>};
-    const int phases = (log2_block - 1) / 4;
-    hipLaunchKernelGGL(d_factors ? clip_kernels[phases] : kernels[inverse][phases], dim3((unsigned)groups), dim3(256), 0,
-                       stream, d_x, x_pitch, L, L_rot, (uint32_t)((L_rot + 4095) / 4096), log2_block, scale, d_sign_bits,
-                       d_out, out_pitch, inverse ? nullptr : d_nonfinite, d_factors);
+        {rotate_kernel<true, 1, false>, rotate_kernel<true, 2, false>, rotate_kernel<true, 3, false>},
+        {rotate_kernel<false, 1, true>, rotate_kernel<false, 2, true>, rotate_kernel<false, 3, true>}};
+    hipLaunchKernelGGL(kernels[d_factors ? 2 : inverse][(log2_block - 1) / 4], dim3((unsigned)groups), dim3(256), 0, stream,
+                       d_x, x_pitch, L, L_rot, (uint32_t)float_tiles(L_rot), log2_block, scale, d_sign_bits, d_out, out_pitch,
+                       inverse ? nullptr : d_nonfinite, d_factors);
     return hipGetLastError();
 }
 
-hipError_t launch_rotate(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
-                         const uint32_t *d_sign_bits, bool inverse, float *d_out, uint64_t out_pitch,
-                         uint32_t *d_nonfinite, hipStream_t stream) {
-    return launch_rotate_any(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, inverse, d_out, out_pitch, d_nonfinite,
-                             nullptr, stream);
-}
-
-hipError_t launch_rotate_clip(const float *d_x, uint64_t x_pitch, int N, uint64_t L, uint64_t L_rot, int log2_block,
-                              const uint32_t *d_sign_bits, const float *d_factors, float *d_out, uint64_t out_pitch,
-                              uint32_t *d_nonfinite, hipStream_t stream) {
-    if (!d_factors) return hipErrorInvalidValue;
-    return launch_rotate_any(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, false, d_out, out_pitch, d_nonfinite,
-                             d_factors, stream);
-}
-
-uint64_t l2_tiles(uint64_t L) { return L / 4096 + (L % 4096 ? 1 : 0); }
+uint64_t l2_tiles(uint64_t L) { return float_tiles(L); }
 
 hipError_t launch_l2_factors(const float *d_x, uint64_t x_pitch, int N, uint64_t L, float clip_norm, double *d_work,
                              float *d_factors, double *d_sumsq, hipStream_t stream) {

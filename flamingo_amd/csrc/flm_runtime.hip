@@ -1467,72 +1467,121 @@ int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, ui
     return 0;
 }
 
-// ---- the randomised block Hadamard rotation (flm_call_args.h has the rule)
+// ---- the randomised block Hadamard rotation and the L2 clip in front of it (flm_call_args.h has the rules)
 
-int flm_rotate_check(uint64_t L, int log2_block, uint64_t *L_rot) {
+namespace {
+int check_rotate(flm_ctx *ctx, uint64_t L, int log2_block, uint64_t *L_rot) {
     bool range = false;
-    uint64_t lr = 0;
-    if (int rc = refuse(nullptr, flm::rt::rotate_error(L, log2_block, &range, &lr), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
-    if (L_rot) *L_rot = lr;
-    return 0;
+    const char *why = flm::rt::rotate_error(L, log2_block, &range, L_rot);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
+int check_l2(flm_ctx *ctx, uint64_t L, float clip_norm, int N, uint64_t *work_doubles) {
+    bool range = false;
+    const char *why = flm::rt::l2_clip_error(L, clip_norm, N, &range, work_doubles);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
 }
 
-int flm_rotate_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
-                   const uint32_t *d_sign_bits, int inverse, float *d_out, size_t out_pitch, uint32_t *d_nonfinite,
-                   void *stream) {
+// flm_rotate_dev, and flm_rotate_clip_dev (clip: forward, d_factors required and multiplied into the load).  The
+// factors come from elsewhere, so the L2 rule is not consulted.
+int rotate_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block, const uint32_t *d_sign_bits,
+               bool inverse, bool clip, const float *d_factors, float *d_out, size_t out_pitch, uint32_t *d_nonfinite,
+               void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    bool range = false;
     uint64_t L_rot = 0;
-    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (int rc = check_rotate(ctx, L, log2_block, &L_rot)) return rc;
     if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
     if (inverse && d_nonfinite) return fail(ctx, FLM_EINVAL, "the inverse rotation counts nothing: nonfinite must be NULL");
     if (N == 0) return 0;
-    if (!d_x || !d_out || !d_sign_bits) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (!d_x || !d_out || !d_sign_bits || (clip && !d_factors)) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, inverse ? L_rot : L))) return rc;
     if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, inverse ? L : L_rot))) return rc;
     if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out, d_sign_bits}))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align4_error(d_factors))) return rc;
     if (int rc = refuse(ctx, flm::rt::rotate_launch_error(flm::rotate_groups(N, L_rot)))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
     FLM_ON_DEVICE(ctx);
     if (d_nonfinite) FLM_HIP(ctx, hipMemsetAsync(d_nonfinite, 0, (size_t)N * sizeof(uint32_t), s));
-    FLM_HIP(ctx, flm::launch_rotate(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, inverse != 0, d_out, out_pitch,
-                                    d_nonfinite, s));
+    FLM_HIP(ctx, flm::launch_rotate(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, inverse, d_out, out_pitch, d_nonfinite,
+                                    d_factors, s));
     return 0;
 }
 
-int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], int inverse,
-               float *out, uint32_t *nonfinite) {
+// the context's tile partials for N rows of L, and behind them N factors for a caller who wants none back
+int reserve_l2_work(flm_ctx *ctx, uint64_t work_doubles, int N, double **work, float **spare_factors) {
+    FLM_HIP(ctx, ctx->l2_work.reserve(work_doubles * sizeof(double) + (size_t)N * sizeof(float)));
+    *work = ctx->l2_work.as<double>();
+    *spare_factors = reinterpret_cast<float *>(*work + work_doubles);
+    return 0;
+}
+
+// flm_rotate, and flm_rotate_clip (clip_norm given: forward, the L2 rule after the rotation's, the factors computed
+// in front of the rotation and with sumsq handed back where asked).  The L2 rule wants N >= 1; the plain rotation
+// takes N = 0 as nothing to do.
+int rotate_host(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t *key, bool inverse,
+                const float *clip_norm, float *out, uint32_t *nonfinite, float *factors, double *sumsq) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    bool range = false;
-    uint64_t L_rot = 0;
-    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
-    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    if (inverse && nonfinite) return fail(ctx, FLM_EINVAL, "the inverse rotation counts nothing: nonfinite must be NULL");
-    if (N == 0) return 0;
+    uint64_t L_rot = 0, wd = 0;
+    if (int rc = check_rotate(ctx, L, log2_block, &L_rot)) return rc;
+    if (clip_norm) {
+        if (int rc = check_l2(ctx, L, *clip_norm, N, &wd)) return rc;
+    } else {
+        if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+        if (inverse && nonfinite) return fail(ctx, FLM_EINVAL, "the inverse rotation counts nothing: nonfinite must be NULL");
+        if (N == 0) return 0;
+    }
     if (!x || !out || !key) return fail(ctx, FLM_EINVAL, "NULL argument");
     FLM_ON_DEVICE(ctx);
     const size_t L_in = inverse ? L_rot : L, L_out = inverse ? L : L_rot, words = flm::rt::rotate_sign_words(L_rot);
     FLM_HIP(ctx, ctx->rot_signs.reserve(round_up(words, 4) * sizeof(uint32_t)));
+    double *work = nullptr;
+    float *d_factors = nullptr;
+    if (clip_norm)
+        if (int rc = reserve_l2_work(ctx, wd, N, &work, &d_factors)) return rc;
     HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::rotate_args(N, L_in, L_out, nonfinite != nullptr), {x, out, key, nonfinite});
+    hc.declare(flm::rt::rotate_args(N, L_in, L_out, nonfinite != nullptr, factors != nullptr, sumsq != nullptr),
+               {x, out, key, nonfinite, factors, sumsq});
     if (int rc = hc.begin()) return rc;
+    if (factors) d_factors = hc.dev<float>(4);
     if (int rc = flm_prg_expand_dev(ctx, hc.dev<uint8_t>(2), 1, words, 0, ctx->rot_signs.as<uint32_t>(), round_up(words, 4),
                                     ctx->stream))
         return rc;
-    if (int rc = flm_rotate_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, log2_block, ctx->rot_signs.as<uint32_t>(), inverse,
-                                hc.dev<float>(1), hc.pitch(1) / 4, hc.dev<uint32_t>(3), ctx->stream))
+    if (clip_norm)
+        if (int rc = flm_l2_factors_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, *clip_norm, work, d_factors,
+                                        hc.dev<double>(5), ctx->stream))
+            return rc;
+    if (int rc = rotate_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, log2_block, ctx->rot_signs.as<uint32_t>(), inverse,
+                            clip_norm != nullptr, d_factors, hc.dev<float>(1), hc.pitch(1) / 4, hc.dev<uint32_t>(3), ctx->stream))
         return rc;
     return hc.finish();
 }
-
-// ---- the L2 clip in front of the rotation (flm_call_args.h has the rule)
-
-namespace {
-int check_l2(flm_ctx *ctx, uint64_t L, float clip_norm, int N, uint64_t *work_doubles) {
-    bool range = false;
-    return refuse(ctx, flm::rt::l2_clip_error(L, clip_norm, N, &range, work_doubles), range ? FLM_ERANGE : FLM_EINVAL);
-}
 }  // namespace
+
+int flm_rotate_check(uint64_t L, int log2_block, uint64_t *L_rot) {
+    uint64_t lr = 0;
+    if (int rc = check_rotate(nullptr, L, log2_block, &lr)) return rc;
+    if (L_rot) *L_rot = lr;
+    return 0;
+}
+int flm_rotate_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
+                   const uint32_t *d_sign_bits, int inverse, float *d_out, size_t out_pitch, uint32_t *d_nonfinite,
+                   void *stream) {
+    return rotate_dev(ctx, d_x, x_pitch, N, L, log2_block, d_sign_bits, inverse != 0, false, nullptr, d_out, out_pitch,
+                      d_nonfinite, stream);
+}
+int flm_rotate_clip_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
+                        const uint32_t *d_sign_bits, const float *d_factors, float *d_out, size_t out_pitch,
+                        uint32_t *d_nonfinite, void *stream) {
+    return rotate_dev(ctx, d_x, x_pitch, N, L, log2_block, d_sign_bits, false, true, d_factors, d_out, out_pitch, d_nonfinite,
+                      stream);
+}
+int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], int inverse,
+               float *out, uint32_t *nonfinite) {
+    return rotate_host(ctx, x, N, L, log2_block, key, inverse != 0, nullptr, out, nonfinite, nullptr, nullptr);
+}
+int flm_rotate_clip(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], float clip_norm,
+                    float *out, uint32_t *nonfinite, float *factors, double *sumsq) {
+    return rotate_host(ctx, x, N, L, log2_block, key, false, &clip_norm, out, nonfinite, factors, sumsq);
+}
 
 int flm_l2_clip_check(uint64_t L, float clip_norm, int N, uint64_t *work_doubles) {
     uint64_t wd = 0;
@@ -1549,8 +1598,7 @@ int flm_l2_factors_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, si
     if (!d_x || !d_work || !d_factors) return fail(ctx, FLM_EINVAL, "NULL argument");
     if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
     if (int rc = refuse(ctx, flm::rt::align16_error({d_x}))) return rc;
-    if (((uintptr_t)d_work | (uintptr_t)d_sumsq) & 7 || (uintptr_t)d_factors & 3)
-        return fail(ctx, FLM_EINVAL, "work and sumsq must be 8-byte aligned, factors 4-byte aligned");
+    if (int rc = refuse(ctx, flm::rt::l2_factors_align_error(d_work, d_sumsq, d_factors))) return rc;
     FLM_ON_DEVICE(ctx);
     FLM_HIP(ctx, flm::launch_l2_factors(d_x, x_pitch, N, L, clip_norm, d_work, d_factors, d_sumsq,
                                         static_cast<hipStream_t>(stream)));
@@ -1566,45 +1614,12 @@ int flm_scale_rows_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, si
     if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
     if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, L))) return rc;
     if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out}))) return rc;
-    if ((uintptr_t)d_factors & 3) return fail(ctx, FLM_EINVAL, "factors must be 4-byte aligned");
+    if (int rc = refuse(ctx, flm::rt::align4_error(d_factors))) return rc;
     if (d_out == d_x && out_pitch != x_pitch) return fail(ctx, FLM_EINVAL, "in place needs equal pitches");
     FLM_ON_DEVICE(ctx);
     FLM_HIP(ctx, flm::launch_scale_rows(d_x, x_pitch, N, L, d_factors, d_out, out_pitch, static_cast<hipStream_t>(stream)));
     return 0;
 }
-
-int flm_rotate_clip_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int log2_block,
-                        const uint32_t *d_sign_bits, const float *d_factors, float *d_out, size_t out_pitch,
-                        uint32_t *d_nonfinite, void *stream) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    bool range = false;
-    uint64_t L_rot = 0;
-    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
-    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    if (N == 0) return 0;
-    if (!d_x || !d_out || !d_sign_bits || !d_factors) return fail(ctx, FLM_EINVAL, "NULL argument");
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
-    if (int rc = refuse(ctx, flm::rt::row_pitch_error(out_pitch, L_rot))) return rc;
-    if (int rc = refuse(ctx, flm::rt::align16_error({d_x, d_out, d_sign_bits}))) return rc;
-    if ((uintptr_t)d_factors & 3) return fail(ctx, FLM_EINVAL, "factors must be 4-byte aligned");
-    if (int rc = refuse(ctx, flm::rt::rotate_launch_error(flm::rotate_groups(N, L_rot)))) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-    FLM_ON_DEVICE(ctx);
-    if (d_nonfinite) FLM_HIP(ctx, hipMemsetAsync(d_nonfinite, 0, (size_t)N * sizeof(uint32_t), s));
-    FLM_HIP(ctx, flm::launch_rotate_clip(d_x, x_pitch, N, L, L_rot, log2_block, d_sign_bits, d_factors, d_out, out_pitch,
-                                         d_nonfinite, s));
-    return 0;
-}
-
-namespace {
-// the context's tile partials for N rows of L, and behind them N factors for a caller who wants none back
-int reserve_l2_work(flm_ctx *ctx, uint64_t work_doubles, int N, double **work, float **spare_factors) {
-    FLM_HIP(ctx, ctx->l2_work.reserve(work_doubles * sizeof(double) + (size_t)N * sizeof(float)));
-    *work = ctx->l2_work.as<double>();
-    *spare_factors = reinterpret_cast<float *>(*work + work_doubles);
-    return 0;
-}
-}  // namespace
 
 int flm_l2_clip(flm_ctx *ctx, const float *x, int N, size_t L, float clip_norm, float *out, float *factors, double *sumsq) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
@@ -1624,37 +1639,6 @@ int flm_l2_clip(flm_ctx *ctx, const float *x, int N, size_t L, float clip_norm, 
         return rc;
     if (int rc = flm_scale_rows_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, d_factors, hc.dev<float>(1), hc.pitch(1) / 4,
                                     ctx->stream))
-        return rc;
-    return hc.finish();
-}
-
-int flm_rotate_clip(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], float clip_norm,
-                    float *out, uint32_t *nonfinite, float *factors, double *sumsq) {
-    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    bool range = false;
-    uint64_t L_rot = 0, wd = 0;
-    if (int rc = refuse(ctx, flm::rt::rotate_error(L, log2_block, &range, &L_rot), range ? FLM_ERANGE : FLM_EINVAL)) return rc;
-    if (int rc = check_l2(ctx, L, clip_norm, N, &wd)) return rc;
-    if (!x || !out || !key) return fail(ctx, FLM_EINVAL, "NULL argument");
-    FLM_ON_DEVICE(ctx);
-    const size_t words = flm::rt::rotate_sign_words(L_rot);
-    FLM_HIP(ctx, ctx->rot_signs.reserve(round_up(words, 4) * sizeof(uint32_t)));
-    double *work = nullptr;
-    float *spare = nullptr;
-    if (int rc = reserve_l2_work(ctx, wd, N, &work, &spare)) return rc;
-    HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::rotate_clip_args(N, L, L_rot, nonfinite != nullptr, factors != nullptr, sumsq != nullptr),
-               {x, out, key, nonfinite, factors, sumsq});
-    if (int rc = hc.begin()) return rc;
-    float *d_factors = factors ? hc.dev<float>(4) : spare;
-    if (int rc = flm_prg_expand_dev(ctx, hc.dev<uint8_t>(2), 1, words, 0, ctx->rot_signs.as<uint32_t>(), round_up(words, 4),
-                                    ctx->stream))
-        return rc;
-    if (int rc = flm_l2_factors_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, clip_norm, work, d_factors, hc.dev<double>(5),
-                                    ctx->stream))
-        return rc;
-    if (int rc = flm_rotate_clip_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, log2_block, ctx->rot_signs.as<uint32_t>(),
-                                     d_factors, hc.dev<float>(1), hc.pitch(1) / 4, hc.dev<uint32_t>(3), ctx->stream))
         return rc;
     return hc.finish();
 }

@@ -30,7 +30,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import p_f32, p_i8, p_i64, p_u8, p_u32
+from ._lib import p_f32, p_f64, p_i8, p_i64, p_u8, p_u32
 
 NONCE = b"\x00" * 8
 
@@ -72,6 +72,28 @@ def _dev_bytes(t, name: str, cols: int, rows: int, dtype_bytes: int = 1):
 def _vp(t) -> ctypes.c_void_p:
     """A CUDA tensor's address for a *_dev call; None: a NULL pointer."""
     return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _dev_vector(name: str, t, n: int, kind, label: str | None = None, flat: bool = False):
+    """t is None or a contiguous (>= n,) tensor of dtype `kind` (an int: of that element size), which the message
+    names by `label`, or as the dtype prints; flat: of any shape, >= n elements."""
+    if t is None:
+        return
+    fits = t.numel() >= n if flat else t.dim() == 1 and t.shape[0] >= n
+    if not (fits and (t.element_size() if isinstance(kind, int) else t.dtype) == kind and t.is_contiguous()):
+        raise RuntimeError(f"{name} must hold >= {n} contiguous {label or kind} words" if flat else
+                           f"{name} must be a contiguous (>= {n},) {label or kind} tensor")
+
+
+def _float_rows_array(x) -> tuple:
+    """x (N, L) or (L,) as a contiguous (N, L) float32 array, and whether it came as one row."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    one = x.ndim == 1
+    if one:
+        x = x[None, :]
+    if x.ndim != 2:
+        raise RuntimeError("x must be (N, L) or (L,)")
+    return x, one
 
 
 def _dev_rows(rows, L: int) -> int:
@@ -378,12 +400,7 @@ class MaskEngine:
         clip_norm = C (forward only): every row is first scaled to an L2 norm of at most C, in the same pass
         (flm_rotate_clip), and the factors (N,) float32 and sums of squares (N,) float64 are returned behind the
         other results: (out, factors, sumsq), or (out, nonfinite, factors, sumsq)."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        one = x.ndim == 1
-        if one:
-            x = x[None, :]
-        if x.ndim != 2:
-            raise RuntimeError("x must be (N, L) or (L,)")
+        x, one = _float_rows_array(x)
         N = x.shape[0]
         if not inverse:
             if L is not None and int(L) != x.shape[1]:
@@ -404,22 +421,20 @@ class MaskEngine:
             raise RuntimeError("one 32-byte rotation key")
         out = np.empty((N, L if inverse else L_rot), dtype=np.float32)
         nonfinite = np.zeros(N, dtype=np.uint32)
+        counts = p_u32(nonfinite) if return_nonfinite else None
+        clipped = ()
         if clip_norm is not None:
             self.l2_clip_check(L, clip_norm, N)
-            factors, sumsq = np.empty(N, dtype=np.float32), np.empty(N, dtype=np.float64)
+            clipped = (np.empty(N, dtype=np.float32), np.empty(N, dtype=np.float64))
             rc = self.lib.flm_rotate_clip(self.ctx, p_f32(x), N, L, int(log2_block), p_u8(key), float(clip_norm), p_f32(out),
-                                          p_u32(nonfinite) if return_nonfinite else None, p_f32(factors),
-                                          sumsq.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+                                          counts, p_f32(clipped[0]), p_f64(clipped[1]))
             self._check(rc, "flm_rotate_clip")
-            if one:
-                out = out[0]
-            return (out, nonfinite, factors, sumsq) if return_nonfinite else (out, factors, sumsq)
-        rc = self.lib.flm_rotate(self.ctx, p_f32(x), N, L, int(log2_block), p_u8(key), int(bool(inverse)), p_f32(out),
-                                 p_u32(nonfinite) if return_nonfinite else None)
-        self._check(rc, "flm_rotate")
-        if one:
-            out = out[0]
-        return (out, nonfinite) if return_nonfinite else out
+        else:
+            rc = self.lib.flm_rotate(self.ctx, p_f32(x), N, L, int(log2_block), p_u8(key), int(bool(inverse)), p_f32(out),
+                                     counts)
+            self._check(rc, "flm_rotate")
+        res = (out[0] if one else out,) + ((nonfinite,) if return_nonfinite else ()) + clipped
+        return res if len(res) > 1 else res[0]
 
     # ------------------------------------- L2 clip in front of the rotation
     def l2_clip_check(self, L: int, clip_norm: float, N: int = 1) -> int:
@@ -435,18 +450,13 @@ class MaskEngine:
         (out, factors (N,) float32, sumsq (N,) float64), out = x factors[row], factors = min(1, clip_norm /
         sqrt(sumsq)) by the rule of include/flamingo_hip.h; non-finite inputs count as 0 in sumsq and are scaled
         like any other (NaN stays NaN)."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        one = x.ndim == 1
-        if one:
-            x = x[None, :]
-        if x.ndim != 2:
-            raise RuntimeError("x must be (N, L) or (L,)")
+        x, one = _float_rows_array(x)
         N, L = x.shape
         self.l2_clip_check(L, clip_norm, N)
         out = np.empty((N, L), dtype=np.float32)
         factors, sumsq = np.empty(N, dtype=np.float32), np.empty(N, dtype=np.float64)
         rc = self.lib.flm_l2_clip(self.ctx, p_f32(x), N, L, float(clip_norm), p_f32(out), p_f32(factors),
-                                  sumsq.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+                                  p_f64(sumsq))
         self._check(rc, "flm_l2_clip")
         return (out[0] if one else out), factors, sumsq
 
@@ -661,21 +671,14 @@ class MaskEngine:
         own strides (out may be x); forward reads L and writes L_rot floats a row, inverse reads L_rot and writes L.
         sign_bits: >= ceil(L_rot / 32) 32-bit words, prg_expand_dev of the key (K = 1); nonfinite (>= N,) 32-bit or
         None, forward only.  Enqueued on `stream`; nothing is synchronised.  flm_rotate_dev."""
-        import torch
         L_rot = self.rotate_check(L, log2_block)
         N = x.shape[0] if x.dim() == 2 else -1
-        for name, t, n in (("x", x, L_rot if inverse else L), ("out", out, L if inverse else L_rot)):
-            if t.dim() != 2 or t.shape[0] != N or t.shape[1] < n or t.dtype != torch.float32 or t.stride(1) != 1:
-                raise RuntimeError(f"{name} must be ({N}, >= {n}) float32 with unit column stride")
-        if sign_bits.element_size() != 4 or sign_bits.numel() < -(-L_rot // 32) or not sign_bits.is_contiguous():
-            raise RuntimeError(f"sign_bits must hold >= {-(-L_rot // 32)} contiguous 32-bit words")
-        if nonfinite is not None and (nonfinite.dim() != 1 or nonfinite.shape[0] < N or nonfinite.element_size() != 4
-                                      or not nonfinite.is_contiguous()):
-            raise RuntimeError(f"nonfinite must be a contiguous (>= {N},) 32-bit tensor")
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        rc = self.lib.flm_rotate_dev(self.ctx, ptr(x), x.stride(0) if N > 1 else x.shape[1], N, int(L), int(log2_block),
-                                     ptr(sign_bits), int(bool(inverse)), ptr(out),
-                                     out.stride(0) if N > 1 else out.shape[1], ptr(nonfinite), self._stream_handle(stream))
+        xp = self._float_rows("x", x, N, L_rot if inverse else L)
+        op = self._float_rows("out", out, N, L if inverse else L_rot)
+        _dev_vector("sign_bits", sign_bits, -(-L_rot // 32), 4, "32-bit", flat=True)
+        _dev_vector("nonfinite", nonfinite, N, 4, "32-bit")
+        rc = self.lib.flm_rotate_dev(self.ctx, _vp(x), xp, N, int(L), int(log2_block), _vp(sign_bits), int(bool(inverse)),
+                                     _vp(out), op, _vp(nonfinite), self._stream_handle(stream))
         self._check(rc, "flm_rotate_dev")
         return out
 
@@ -697,8 +700,7 @@ class MaskEngine:
         pitch = self._float_rows("x", x, N, L)
         for name, t, n, dt in (("work", work, need, torch.float64), ("factors", factors, N, torch.float32),
                                ("sumsq", sumsq, N, torch.float64)):
-            if t is not None and (t.dim() != 1 or t.shape[0] < n or t.dtype != dt or not t.is_contiguous()):
-                raise RuntimeError(f"{name} must be a contiguous (>= {n},) {dt} tensor")
+            _dev_vector(name, t, n, dt)
         rc = self.lib.flm_l2_factors_dev(self.ctx, _vp(x), pitch, N, int(L), float(clip_norm), _vp(work), _vp(factors),
                                          _vp(sumsq), self._stream_handle(stream))
         self._check(rc, "flm_l2_factors_dev")
@@ -710,8 +712,7 @@ class MaskEngine:
         import torch
         N = x.shape[0] if x.dim() == 2 else -1
         xp, op = self._float_rows("x", x, N, L), self._float_rows("out", out, N, L)
-        if factors.dim() != 1 or factors.shape[0] < N or factors.dtype != torch.float32 or not factors.is_contiguous():
-            raise RuntimeError(f"factors must be a contiguous (>= {N},) float32 tensor")
+        _dev_vector("factors", factors, N, torch.float32, "float32")
         rc = self.lib.flm_scale_rows_dev(self.ctx, _vp(x), xp, N, int(L), _vp(factors), _vp(out), op,
                                          self._stream_handle(stream))
         self._check(rc, "flm_scale_rows_dev")
@@ -724,13 +725,9 @@ class MaskEngine:
         L_rot = self.rotate_check(L, log2_block)
         N = x.shape[0] if x.dim() == 2 else -1
         xp, op = self._float_rows("x", x, N, L), self._float_rows("out", out, N, L_rot)
-        if sign_bits.element_size() != 4 or sign_bits.numel() < -(-L_rot // 32) or not sign_bits.is_contiguous():
-            raise RuntimeError(f"sign_bits must hold >= {-(-L_rot // 32)} contiguous 32-bit words")
-        if factors.dim() != 1 or factors.shape[0] < N or factors.dtype != torch.float32 or not factors.is_contiguous():
-            raise RuntimeError(f"factors must be a contiguous (>= {N},) float32 tensor")
-        if nonfinite is not None and (nonfinite.dim() != 1 or nonfinite.shape[0] < N or nonfinite.element_size() != 4
-                                      or not nonfinite.is_contiguous()):
-            raise RuntimeError(f"nonfinite must be a contiguous (>= {N},) 32-bit tensor")
+        _dev_vector("sign_bits", sign_bits, -(-L_rot // 32), 4, "32-bit", flat=True)
+        _dev_vector("factors", factors, N, torch.float32, "float32")
+        _dev_vector("nonfinite", nonfinite, N, 4, "32-bit")
         rc = self.lib.flm_rotate_clip_dev(self.ctx, _vp(x), xp, N, int(L), int(log2_block), _vp(sign_bits), _vp(factors),
                                           _vp(out), op, _vp(nonfinite), self._stream_handle(stream))
         self._check(rc, "flm_rotate_clip_dev")

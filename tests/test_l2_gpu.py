@@ -5,6 +5,7 @@ fused forward rotation against the restatement, against the two-pass device path
 host forms, the reference-side binding and the stream contract.  NaN compares as NaN, everything else by its bits."""
 from __future__ import annotations
 
+import ctypes
 import importlib.util
 import os
 
@@ -18,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = np.float32(-123456.75)
+FLM_EINVAL = -1   # include/flamingo_hip.h
 
 
 @pytest.fixture(scope="module")
@@ -256,6 +258,27 @@ def test_refusals_on_the_device(eng):
         eng.l2_clip(np.zeros((2, 5), np.float32), 0.0)
     with pytest.raises(RuntimeError):
         eng.rotate(np.zeros((2, 32), np.float32), R.KEY, 5, inverse=True, L=20, clip_norm=1.0)
+    # The C calls themselves, where flm_rotate_clip[_dev] differ from flm_rotate[_dev] (tests/test_rotate_gpu.py has
+    # those): every case returns before a launch, so one-element tensors and NULL stand in for the arrays.
+    lib, ctx, stream, h = eng.lib, eng.ctx, eng._stream_handle(None), 5
+    one = torch.zeros(4, dtype=torch.float32, device="cuda")
+    p = ctypes.c_void_p(one.data_ptr())
+
+    def refused(rc, text):
+        return rc == FLM_EINVAL and text in lib.flm_last_error(ctx)
+
+    # the host form asks the L2 rule, which wants a row: N = 0 is no early return there
+    for N in (-1, 0):
+        assert refused(lib.flm_rotate_clip(ctx, None, N, L, h, None, 1.0, None, None, None, None), b"N must be at least 1")
+    # ... after the rotation's own rule: a bad block and a bad radius give the block's message
+    assert refused(lib.flm_rotate_clip(ctx, None, 1, L, 3, None, 0.0, None, None, None, None), b"log2_block outside 4..12")
+    assert refused(lib.flm_rotate_clip(ctx, None, 1, L, h, None, 0.0, None, None, None, None), b"clip_norm must be finite")
+    # the device form takes its factors from elsewhere and asks no L2 rule: N = 0 is nothing to do, N < 0 the rotation's
+    assert lib.flm_rotate_clip_dev(ctx, None, 0, 0, L, h, None, None, None, 0, None, stream) == 0
+    assert refused(lib.flm_rotate_clip_dev(ctx, None, 0, -1, L, h, None, None, None, 0, None, stream), b"negative N")
+    # ... and its factors are an array like the rows: NULL is refused, behind the rotation's rule
+    assert refused(lib.flm_rotate_clip_dev(ctx, p, 104, 1, L, h, p, None, p, 128, None, stream), b"NULL argument")
+    assert refused(lib.flm_rotate_clip_dev(ctx, p, 104, 1, L, 3, p, None, p, 128, None, stream), b"log2_block outside 4..12")
 
 
 def test_dev_call_returns_before_its_stream_drains(eng):

@@ -4,6 +4,7 @@ poisoned padding and guards, in place, non-finite and overflowing inputs, the ho
 rotation composed with the codec's calls around a whole round.  NaN compares as NaN, everything else by its bits."""
 from __future__ import annotations
 
+import ctypes
 import hashlib
 
 import numpy as np
@@ -15,6 +16,7 @@ import rotate_cases as R
 pytestmark = pytest.mark.gpu
 
 GUARD = np.float32(-123456.75)
+FLM_EINVAL = -1   # include/flamingo_hip.h
 N_ROWS = 3
 
 
@@ -115,6 +117,35 @@ def test_nonfinite_inputs_are_zeroed_and_counted(eng):
     assert _same(got, np.stack([w[0] for w in want])) and list(counts) == [3, 2, 0]
     with pytest.raises(RuntimeError):                                        # the inverse counts nothing
         eng.rotate_dev(out, out, L, h, _signs(L_rot), inverse=True, nonfinite=cnt)
+
+
+def test_refusals_on_the_device(eng):
+    """What flm_rotate and flm_rotate_dev answer to N <= 0, by code and text (tests/test_l2_gpu.py has the calls with
+    the clip, which differ).  Every case returns before a launch: one-element arrays and NULL stand in for the rows."""
+    import torch
+    from flamingo_amd._lib import p_u32
+    lib, ctx, stream, L, h = eng.lib, eng.ctx, eng._stream_handle(None), 100, 5
+    cnt_host = np.full(1, 77, np.uint32)
+    cnt_dev = torch.full((1,), 77, dtype=torch.int32, device="cuda")
+    cnt = ctypes.c_void_p(cnt_dev.data_ptr())
+
+    def refused(rc, text):
+        return rc == FLM_EINVAL and text in lib.flm_last_error(ctx)
+
+    # N = 0: nothing to do, whatever the arrays; N < 0 is refused
+    assert lib.flm_rotate(ctx, None, 0, L, h, None, 0, None, None) == 0
+    assert lib.flm_rotate_dev(ctx, None, 0, 0, L, h, None, 0, None, 0, None, stream) == 0
+    assert refused(lib.flm_rotate(ctx, None, -1, L, h, None, 0, None, None), b"negative N")
+    assert refused(lib.flm_rotate_dev(ctx, None, 0, -1, L, h, None, 0, None, 0, None, stream), b"negative N")
+    # counts asked of the inverse: refused before the N = 0 return, and the counts stay as they were
+    text = b"the inverse rotation counts nothing: nonfinite must be NULL"
+    for N in (0, 1):
+        assert refused(lib.flm_rotate(ctx, None, N, L, h, None, 1, None, p_u32(cnt_host)), text)
+        assert refused(lib.flm_rotate_dev(ctx, None, 0, N, L, h, None, 1, None, 0, cnt, stream), text)
+    # ... while the forward direction at N = 0 takes them and touches nothing
+    assert lib.flm_rotate_dev(ctx, None, 0, 0, L, h, None, 0, None, 0, cnt, stream) == 0
+    torch.cuda.synchronize()
+    assert cnt_host[0] == 77 and int(cnt_dev.cpu()[0]) == 77
 
 
 @pytest.mark.parametrize("h", (4, 7, 12))

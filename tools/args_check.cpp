@@ -153,21 +153,23 @@ static void check_round_lists() {
                     bool range = false;
                     uint64_t L_rot = 0;
                     CHECK(!rotate_error(L, h, &range, &L_rot) && L_rot % (1u << h) == 0 && L_rot >= L && L_rot - L < (1u << h));
-                    through_bounce(rotate_args(N, L, L_rot, opt));
-                    if (!opt) through_bounce(rotate_args(N, L_rot, L, false));
+                    through_bounce(rotate_args(N, L, L_rot, opt, false, false));
+                    if (!opt) through_bounce(rotate_args(N, L_rot, L, false, false, false));
                     // flm_rotate_clip and flm_l2_clip: the optional outputs together or none of them
-                    through_bounce(rotate_clip_args(N, L, L_rot, opt, opt, opt));
+                    through_bounce(rotate_args(N, L, L_rot, opt, opt, opt));
                     through_bounce(l2_clip_args(N, L, opt, !opt));
                 }
-    const ArgList rc = rotate_clip_args(3, 5, 16, true, true, false), lc = l2_clip_args(3, 5, false, true);
+    const ArgList rc = rotate_args(3, 5, 16, true, true, false), lc = l2_clip_args(3, 5, false, true);
     CHECK(rc.n == 6 && rc.a[0].width == 20 && rc.a[1].width == 64 && rc.a[1].is_out && rc.a[3].present && rc.a[4].present &&
           rc.a[4].is_out && rc.a[4].width == 12 && rc.a[4].slot == ec_flags && !rc.a[5].present && !names_slot_twice(rc));
     CHECK(lc.n == 4 && lc.a[0].slot == rows && lc.a[1].slot == out && lc.a[1].in_place && lc.a[1].width == 20 && !lc.a[2].present &&
           lc.a[3].present && lc.a[3].is_out && lc.a[3].width == 24 && lc.a[3].slot == ec_dig && !names_slot_twice(lc));
-    const ArgList ro = rotate_args(3, 5, 16, true), ri = rotate_args(3, 16, 5, false);
-    CHECK(ro.n == 4 && ro.a[0].slot == rows && ro.a[0].width == 20 && ro.a[0].rows == 3 && ro.a[0].in_place && !ro.a[0].is_out &&
+    // the plain rotation: the clip's two outputs are in the list and absent
+    const ArgList ro = rotate_args(3, 5, 16, true, false, false), ri = rotate_args(3, 16, 5, false, false, false);
+    CHECK(ro.n == 6 && ro.a[0].slot == rows && ro.a[0].width == 20 && ro.a[0].rows == 3 && ro.a[0].in_place && !ro.a[0].is_out &&
           ro.a[1].slot == out && ro.a[1].width == 64 && ro.a[1].is_out && ro.a[1].in_place && ro.a[2].width == 32 &&
           ro.a[2].slot == seeds && ro.a[3].present && ro.a[3].is_out && ro.a[3].width == 12);
+    CHECK(!ro.a[4].present && !ro.a[5].present && !ri.a[4].present && !ri.a[5].present && !names_slot_twice(ro));
     CHECK(ri.a[0].width == 64 && ri.a[1].width == 20 && !ri.a[3].present);
     // rows travel at the host forms' pitch; what is optional is exactly what the flags name
     const ArgList m = client_mask_args(3, 7, 5, false), e = client_encode_mask_args(3, 7, 5, 5, false, false, true);
@@ -218,6 +220,12 @@ static void check_round_rules() {
     CHECK(!align16_error({buf, buf + 16, nullptr}) && align16_error({buf + 8}) && align16_error({buf, buf + 1}) &&
           align16_error({nullptr, buf + 24}) && !align16_error({}));
     CHECK(std::strstr(align16_error({buf + 8}), "16-byte aligned"));
+    // the L2 calls' doubles at 8 bytes and factors at 4; NULL passes; without doubles the text names the factors alone
+    CHECK(!l2_factors_align_error(buf + 8, nullptr, buf + 4) && !align4_error(buf + 12) && !align4_error(nullptr) &&
+          l2_factors_align_error(buf, buf + 4, buf) && l2_factors_align_error(buf, nullptr, buf + 2) && align4_error(buf + 1));
+    CHECK(!std::strcmp(l2_factors_align_error(buf + 4, nullptr, buf),
+                       "work and sumsq must be 8-byte aligned, factors 4-byte aligned"));
+    CHECK(!std::strcmp(align4_error(buf + 2), "factors must be 4-byte aligned"));
     // frac_bits 0, 30, 31; the clip; n ceil(clip 2^f) exactly 2^31 - 1 and one more
     bool range = true;
     CHECK(!unpacked_rule(0, 1.0f, 1, &range) && !range && !unpacked_rule(30, 1.0f, 1, &range) && !range);
