@@ -18,6 +18,7 @@ _u32p = ctypes.POINTER(ctypes.c_uint32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _f32p = ctypes.POINTER(ctypes.c_float)
 _f64p = ctypes.POINTER(ctypes.c_double)
+_u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _u64 = ctypes.c_uint64
@@ -70,6 +71,10 @@ SIGNATURES = {
     "flm_rotate_clip_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _vp, _vp, _sz, _vp, _vp]),
     "flm_l2_clip": (_int, [_vp, _f32p, _int, _sz, ctypes.c_float, _f32p, _f32p, _f64p]),
     "flm_rotate_clip": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, ctypes.c_float, _f32p, _u32p, _f32p, _f64p]),
+    "flm_round_check": (_int, [_u64, _int, ctypes.c_float, _int]),
+    "flm_round_bound": (_int, [ctypes.c_float, _int, _u64, ctypes.c_double, ctypes.POINTER(_u64)]),
+    "flm_round_select_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, ctypes.c_float, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "flm_round_select": (_int, [_vp, _f32p, _int, _sz, _int, ctypes.c_float, _u8p, _int, _u64, _u64p, _u8p, _u32p]),
     "flm_prg_expand_dev": (_int, [_vp, _vp, _int, _sz, _u64, _vp, _sz, _vp]),
     "flm_check_signs": (_int, [_vp, ctypes.POINTER(_int)]),
     "flm_last_plan": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
@@ -190,6 +195,10 @@ def p_f32(a):
 
 def p_f64(a):
     return a.ctypes.data_as(_f64p)
+
+
+def p_u64(a):
+    return a.ctypes.data_as(_u64p)
 
 
 def p_i64(a):

@@ -93,6 +93,12 @@ def parse(argv):
     # sensitivity --dp_noise is measured against; turning C into a privacy statement is the caller's business; needs
     # --float_inputs; off by default
     ap.add_argument("--l2_clip", type=float, default=0.0, metavar="C")
+    # conditional stochastic rounding: every client draws ATTEMPTS (1..8, default 4) candidate dither seeds a batch and
+    # rounds with the first whose integer row has a sum of squares within Delta^2 = MaskEngine.round_bound(C, F, d,
+    # TAIL), TAIL = k = sqrt(2 ln(1 / beta)) for a per-draw failure probability beta (protocol.configure(round_bound=
+    # ...)): Delta / 2^F is then the L2 sensitivity of the sum to one client after rounding, where C is the one before
+    # it; needs --float_inputs F,CLIP,sr and --l2_clip; 0 turns it off; off by default
+    ap.add_argument("--round_bound", default=None, metavar="TAIL[,ATTEMPTS]")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -110,6 +116,17 @@ def parse_float_inputs(spec):
         raise ValueError("--float_inputs takes F,CLIP[,sr][,pack2|pack4]")
     codec = (int(parts[0]), float(parts[1]), "stochastic" if len(parts) == 3 else "nearest")
     return codec if pack is None else codec + (pack,)
+
+
+def parse_round_bound(spec):
+    """"TAIL" or "TAIL,ATTEMPTS" -> (tail, attempts), attempts 4 when left out; None, "" or a TAIL of 0 -> None."""
+    if not spec:
+        return None
+    parts = [s.strip() for s in str(spec).split(",")]
+    if len(parts) not in (1, 2):
+        raise ValueError("--round_bound takes TAIL[,ATTEMPTS]")
+    tail, attempts = float(parts[0]), int(parts[1]) if len(parts) == 2 else 4
+    return (tail, attempts) if tail != 0.0 else None
 
 
 def offline_schedule(n: int, iterations: int, always=(), dropout: float = 0.0) -> dict:
@@ -180,7 +197,8 @@ def _run(args):
                     gpu_verify=True if args.gpu_verify else None,
                     authenticate_shares=True if args.authenticate_shares else None,
                     dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs),
-                    dp_noise=args.dp_noise, rotate=args.rotate, l2_clip=args.l2_clip)
+                    dp_noise=args.dp_noise, rotate=args.rotate, l2_clip=args.l2_clip,
+                    round_bound=parse_round_bound(args.round_bound) or False)
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -256,6 +274,11 @@ def _run(args):
             if param.l2_clip() is not None:
                 scaled = (f", {sum(agents[i].l2_factor < 1.0 for i in server.online_ids[it])} of {len(server.online_ids[it])} "
                           f"clients scaled to norm {param.l2_clip():g}")
+                if param.round_bound() is not None:   # the sensitivity after rounding beside the one before it
+                    redrawn = sum(agents[i].round_attempts[it] > 0 for i in server.online_ids[it])
+                    scaled += (f", rounded within Delta = sqrt({server.round_max_sumsq}) / 2^{param.codec()[0]} = "
+                               f"{float(np.sqrt(server.round_max_sumsq)) / 2.0 ** param.codec()[0]:g}, {redrawn} clients "
+                               f"needed a redraw")
             print(f"    iteration {it}: float inputs {param.codec()}{packed}{rotated}: largest |final_mean - mean of the clients' floats| = "
                   f"{float(np.max(np.abs(diff))):.3e}{noised}, "
                   f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped{nonfinite}{scaled}")

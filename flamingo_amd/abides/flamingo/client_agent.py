@@ -99,6 +99,9 @@ class SA_ClientAgent(Agent):
         self.l2_factor = None        # float inputs with --l2_clip: the factor the last update was scaled by (1.0: within
         self.l2_norm = None          # the norm), and the update's own L2 norm, sqrt of the library's sum of squares
         self.dither_seed = None      # float inputs, stochastic rounding: the last iteration's dither seed
+        self.round_attempt = None    # ... with --round_bound: the overall index of the candidate seed that was accepted
+        self.rounded_sumsq = None    # (0: the first drawn), and the rounded update's sum of squares under it
+        self.round_attempts = {}     # ... iteration -> round_attempt, for the run's report
         self.noise_seed = None       # float inputs with --dp_noise: the last iteration's noise seed
         pki = param.pki(num_clients)
         self.secret_key = pki.client_sk[id]
@@ -255,8 +258,27 @@ class SA_ClientAgent(Agent):
                                                                          clip_norm=norm)
                     self.l2_factor, self.l2_norm = float(factors[0]), float(np.sqrt(sumsq[0]))
                 L, self.nonfinite = param.rotated_len(), int(nonfinite[0])
-            dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
-                if rounding == "stochastic" else None
+            bound = param.round_bound()
+            if bound is None:
+                dither = [bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))] \
+                    if rounding == "stochastic" else None
+            else:
+                # conditional rounding: batches of candidate seeds where the one seed is drawn, the first whose rounded
+                # row keeps its sum of squares within the bound is the dither seed; a row outside it is never sent
+                attempts, max_sumsq = bound[1], param.round_max_sumsq()
+                dither = None
+                for batch in range(param.ROUND_BATCHES):
+                    cands = self.random_state.randint(0, 256, size=(1, attempts, 32), dtype=np.uint8)
+                    picked, chosen, sumsq = param.engine().round_select(x, frac_bits, clip, cands, max_sumsq)
+                    if int(chosen[0]) < attempts:
+                        dither = [picked[0].tobytes()]
+                        self.round_attempt = batch * attempts + int(chosen[0])
+                        self.rounded_sumsq = int(sumsq[0, int(chosen[0])])
+                        self.round_attempts[self.current_iteration] = self.round_attempt
+                        break
+                if dither is None:
+                    raise RuntimeError(f"client {self.id}: none of {param.ROUND_BATCHES * attempts} dither seeds kept the "
+                                       f"rounded update's sum of squares within {max_sumsq}")
             seg = np.array([0, len(seeds)], np.int64)
             noise_bits = param.codec_noise_bits()
             if noise_bits:   # distributed DP: the noise seed is drawn after every other draw, the dither seed included

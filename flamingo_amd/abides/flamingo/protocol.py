@@ -85,13 +85,20 @@ _rotate: int = 0
 # client moves the sum by at most C in L2.  It needs the float inputs.  Off (None) by default, so a run calls what it
 # always called, sends what it always sent and draws what it always drew.
 _l2_clip: float | None = None
+# Conditional stochastic rounding (config_flamingo's --round_bound TAIL[,ATTEMPTS]): every client draws ATTEMPTS
+# candidate dither seeds where it draws one today and encodes with the first whose rounded row has a sum of squares
+# within round_max_sumsq() (MaskEngine.round_select), so that Delta / 2^f bounds the L2 norm of what one client adds
+# to the ring.  It needs stochastic float inputs and the L2 clip.  Off (None) by default, so a run calls what it
+# always called, sends what it always sent and draws what it always drew.
+_round_bound: tuple | None = None      # (tail k, attempts)
+ROUND_BATCHES = 8                       # batches of candidates a client draws before it gives up
 
 
 def configure(root: bytes | None = None, L: int | None = None, committee: int | None = None,
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
               authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None,
-              dp_noise: int | None = None, rotate: int | None = None, l2_clip: float | None = None):
+              dp_noise: int | None = None, rotate: int | None = None, l2_clip: float | None = None, round_bound=None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
     "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
     many parameters into a ring word, False turns them off, None leaves them as they are.  dp_noise: the coin
@@ -100,12 +107,14 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
     Hadamard rotation in front of the codec (4..12; 0 turns it off, None leaves it as it is); it needs the float
     inputs, and turning those off turns it off.  l2_clip: the L2 norm every client scales its update down to (finite
     and positive; 0 turns it off, None leaves it as it is); it needs the float inputs, and turning those off turns it
-    off."""
+    off.  round_bound: (tail, attempts) or a bare tail (attempts = 4) turns conditional stochastic rounding on: tail =
+    k >= 0 of the bound, attempts in 1..8 candidate dither seeds per batch; 0 or False turns it off, None leaves it as
+    it is; it needs stochastic float inputs and the L2 clip, and turning either off turns it off."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
-    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate, _l2_clip
+    global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate, _l2_clip, _round_bound
     if codec is not None:
         if codec is False:
-            _codec, _codec_pack, _dp_noise, _rotate, _l2_clip = None, 1, 0, 0, None
+            _codec, _codec_pack, _dp_noise, _rotate, _l2_clip, _round_bound = None, 1, 0, 0, None, None
         else:
             f, c, mode = codec[:3]
             pack = int(codec[3]) if len(codec) == 4 else 1
@@ -139,6 +148,24 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
         if c and _codec is None:
             raise ValueError("l2_clip needs the float inputs (codec=...)")
         _l2_clip = c if c else None
+    if round_bound is not None:
+        import math
+        if round_bound is False or (not isinstance(round_bound, (tuple, list)) and float(round_bound) == 0.0):
+            _round_bound = None
+        else:
+            tail, attempts = round_bound if isinstance(round_bound, (tuple, list)) else (round_bound, 4)
+            tail = float(tail)
+            if not (math.isfinite(tail) and tail >= 0.0):
+                raise ValueError("round_bound's tail must be finite and not negative")
+            if int(attempts) != attempts or not 1 <= int(attempts) <= 8:
+                raise ValueError("round_bound's attempts must be in 1..8")
+            if _codec is None or _codec[2] != "stochastic":
+                raise ValueError("round_bound needs stochastic float inputs (codec=(f, clip, 'stochastic'))")
+            if _l2_clip is None:
+                raise ValueError("round_bound needs the L2 clip (l2_clip=...)")
+            _round_bound = (tail, int(attempts))
+    if _round_bound is not None and (_codec is None or _codec[2] != "stochastic" or _l2_clip is None):
+        _round_bound = None                   # what it stands on was turned off
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -327,6 +354,18 @@ def rotate_bits() -> int:
 def l2_clip() -> float | None:
     """The L2 norm the clients scale their updates down to, or None when that is off (or the float inputs are)."""
     return _l2_clip if _codec is not None else None
+
+
+def round_bound() -> tuple | None:
+    """(tail, attempts) of conditional stochastic rounding, or None when it is off."""
+    return _round_bound if _codec is not None else None
+
+
+def round_max_sumsq() -> int:
+    """Delta^2, the bound on the sum of squares of a client's rounded row: MaskEngine.round_bound of the L2 clip, the
+    codec's frac_bits, the coordinates encoded (rotated_len()) and the tail.  The server and every client compute it
+    with this one call, so they agree."""
+    return engine().round_bound(_l2_clip, _codec[0], rotated_len(), tail=_round_bound[0])
 
 
 def rotated_len() -> int:

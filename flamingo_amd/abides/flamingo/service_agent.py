@@ -90,6 +90,12 @@ class SA_ServiceAgent(Agent):
             if param.codec_noise_bits():
                 kw.update(noise_bits=param.codec_noise_bits(), L=param.rotated_len())
             param.engine().codec_check(param.codec()[0], param.codec()[1], n, **kw)
+        # conditional rounding: the bound every client holds its rounded update's sum of squares to, computed here by
+        # the clients' own call; sqrt(round_max_sumsq) / 2^f is the L2 sensitivity of the sum to one client
+        self.round_max_sumsq = None
+        if param.codec() is not None and param.round_bound() is not None:
+            param.engine().round_check(param.rotated_len(), param.codec()[0], param.codec()[1], param.round_bound()[1])
+            self.round_max_sumsq = param.round_max_sumsq()
         self.online_counts = {}      # iteration -> |U|
         self.pairs_per_iteration = {}  # iteration -> D dropout pairs recovered
         self.aggProcessingMap = {0: self.initialize, 1: self.report, 2: self.forward_signatures,

@@ -193,6 +193,54 @@ inline const char *l2_clip_error(uint64_t L, float clip_norm, int N, bool *range
     return nullptr;
 }
 
+// flm_round_check, flm_round_select[_dev]: conditional stochastic rounding's one rule.  A row of L > 0 parameters,
+// `attempts` candidate dither seeds in 1..8, the codec's own rule at pack = 1 with n = 1 (its code: FLM_ERANGE when
+// ceil(clip 2^f) alone passes 2^31 - 1).  Then, FLM_ERANGE (*range set): Q = sum q^2 <= L B^2 must fit a uint64,
+// B = ceil(clip 2^f) as the codec computes it; and ceil(L / 16) <= 2^32 blocks of the dither stream, whose block
+// counter has no high word.
+inline const char *round_error(uint64_t L, int frac_bits, float clip, int attempts, bool *range) {
+    *range = false;
+    if (L == 0) return "a row of no parameters";
+    if (attempts < 1 || attempts > 8) return "attempts outside 1..8";
+    uint32_t B = 0;
+    if (const char *why = codec_error(frac_bits, clip, 1, true, 0, 1, 0, range, &B)) return why;
+    *range = true;
+    if (L > ~uint64_t(0) / ((uint64_t)B * (uint64_t)B))  // B >= 1, B^2 < 2^62
+        return "that many squares of up to ceil(clip 2^frac_bits)^2 can wrap the 64-bit sum";
+    if (L / 16 + (L % 16 ? 1 : 0) > (uint64_t(1) << 32))
+        return "the dither stream of a row that long ends beyond 2^32 blocks (its block counter has no high word)";
+    *range = false;
+    return nullptr;
+}
+// round_sumsq_kernel's grid of a workgroup per (row, tile): FLM_ERANGE
+inline const char *round_launch_error(int N, uint64_t L) {
+    return N > 0 && flm::float_tiles(L) > 0x7fffffffull / (uint64_t)N ? kTooManyFloatTiles : nullptr;
+}
+
+// flm_round_bound: the bound on Q of conditional rounding (Kairouz et al., Algorithm 1), in float64 and in this order,
+// every operation rounded on its own (no contraction): s = ((double)C 2^f) (1 + 2^-19), r = sqrt((double)d),
+// b1 = (s + r) (s + r), b2 = (s s + (double)d 0.25) + tail (s + r 0.5), *max_sumsq = (uint64)floor(min(b1, b2)).
+// No log, no exp: only sqrt, which IEEE rounds correctly.  FLM_ERANGE (*range set) for a result >= 2^63.
+inline const char *round_bound_error(float clip_norm, int frac_bits, uint64_t d, double tail, bool *range, uint64_t *max_sumsq) {
+#pragma clang fp contract(off)
+    *range = false;
+    if (!(clip_norm > 0.0f) || !std::isfinite(clip_norm)) return "clip_norm must be finite and positive";
+    if (const char *why = frac_bits_error(frac_bits)) return why;
+    if (d == 0) return "a row of no parameters";
+    if (!(tail >= 0.0) || !std::isfinite(tail)) return "tail must be finite and not negative";
+    const double s = ((double)clip_norm * std::ldexp(1.0, frac_bits)) * (1.0 + std::ldexp(1.0, -19));
+    const double r = std::sqrt((double)d);
+    const double b1 = (s + r) * (s + r);
+    const double b2 = (s * s + (double)d * 0.25) + tail * (s + r * 0.5);
+    const double b = std::floor(b1 < b2 ? b1 : b2);
+    if (!(b < 9223372036854775808.0)) {
+        *range = true;
+        return "a bound of 2^63 or more";
+    }
+    *max_sumsq = (uint64_t)b;
+    return nullptr;
+}
+
 // flm_aggregate_dev, flm_aggregate_unmask_dev: the rows, the mask window and its PRG slots, the output.
 // *range: the refusal is the slot range's (FLM_ERANGE).
 inline const char *aggregate_error(const void *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
@@ -413,6 +461,13 @@ inline ArgList l2_clip_args(size_t N, size_t L, bool factors, bool sumsq) {
     return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))),
              in_place(pitched(arg_out(L * 4, out), N, host_row_pitch(L))), arg_out(N * 4, ec_flags, factors),
              arg_out(N * 8, ec_dig, sumsq)}, 4};
+}
+// flm_round_select: x (N rows of L floats, in place as the rotation's: read only), candidates (N A seeds), sumsq
+// (N A uint64: the kernel's atomics land in device memory, never in the bounce buffer), dither (N seeds), chosen (N
+// words)
+inline ArgList round_select_args(size_t N, size_t L, size_t A) {
+    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(N * A * 32, seeds),
+             arg_out(N * A * 8, ec_dig), arg_out(N * 32, bytes_out), arg_out(N * 4, ec_flags)}, 5};
 }
 // seeds, out (K rows)
 inline ArgList prg_expand_args(size_t K, size_t L) {

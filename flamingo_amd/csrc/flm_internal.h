@@ -86,6 +86,12 @@ hipError_t launch_l2_factors(const float *d_x, uint64_t x_pitch, int N, uint64_t
                              float *d_factors, double *d_sumsq, hipStream_t stream);
 hipError_t launch_scale_rows(const float *d_x, uint64_t x_pitch, int N, uint64_t L, const float *d_factors, float *d_out,
                              uint64_t out_pitch, hipStream_t stream);
+// Conditional stochastic rounding (round_sumsq_kernel, round_select_kernel): d_sumsq[row A + a] += Q(candidate a of the
+// row) over N rows of L > 0 floats (the caller zeroes d_sumsq on the stream first), then d_chosen and d_dither from
+// them; two launches, one workgroup per (row, tile) and one thread per row.  A = attempts in 1..8.
+hipError_t launch_round_select(const float *d_x, uint64_t x_pitch, int N, uint64_t L, int frac_bits, float clip,
+                               const uint8_t *d_candidates, int attempts, uint64_t max_sumsq, uint64_t *d_sumsq,
+                               uint8_t *d_dither, uint32_t *d_chosen, hipStream_t stream);
 uint32_t pair_units_count(int K, uint64_t L, uint32_t *n_tiles);
 hipError_t launch_pair_units(bool side, const SeedRec *d_recs, int K, uint32_t *d_dst, uint64_t L, uint32_t *d_ws,
                              int groups, hipStream_t stream);

@@ -1533,6 +1533,83 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(const float *x, uint64_
     }
 }
 
+// ------------------------------------------------------------ conditional stochastic rounding
+// The pass in front of the stochastic encode (include/flamingo_hip.h has the rule, tests/round_cases.py restates it):
+// for each of A candidate dither seeds a row, Q = the sum of q^2 over the row, q the integers encode_mask_kernel
+// would round to under that seed; then the first candidate whose Q is within the bound.  Integer sums: exact in
+// any order, atomics included.  Nothing of q is stored.
+
+// a <- a + a[lane ^ off] for off = 1 .. 32, as l2_wave_sum, on 64-bit integers
+__device__ __forceinline__ uint64_t round_wave_sum(uint64_t a) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) a += (uint64_t)__shfl_xor((unsigned long long)a, off);
+    return a;
+}
+
+// sumsq[row A + a] += the tile's share of Q(candidate a of the row), a < A <= 8; sumsq zeroed by the call.  Workgroup
+// g = (row, 4096-parameter tile) and thread t of it takes parameters 16 t .. 16 t + 15 of the tile through
+// rot_read16, once, and keeps them; they are block 256 tile + t of every candidate's dither stream, words in
+// parameter order, which is the block and the order encode_mask_kernel draws for them in every pack mode.  Per
+// candidate: one ChaCha block from the key at its wave-uniform address (chacha_raw_add), the 16 q through
+// codec_encode<true> itself -- the codec's NaN and clip rule, not rot_nonfinite: +-Inf clips to +-c -- squared as
+// int64 and summed in uint64 (L B^2 <= 2^64 - 1, the call's rule: no sum wraps).  A parameter at or past L reads as
+// +0.0, which encodes to 0 under any dither word; a thread with none below L skips the ChaCha.  The wave's sums meet
+// by shuffles, the four waves' in LDS, and thread a adds the tile's total with one 64-bit atomic.
+__global__ __launch_bounds__(256) void round_sumsq_kernel(const float *__restrict__ x, uint64_t x_pitch, uint64_t L,
+                                                          uint32_t tiles, const uint8_t *__restrict__ candidates, int A,
+                                                          float clip, float scale,
+                                                          unsigned long long *__restrict__ sumsq) {
+    __shared__ uint64_t wave_sums[4][8];
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const uint32_t row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+    const uint64_t p0 = (uint64_t)tile * kFloatTile + 16u * (uint64_t)t;
+    float v[16];
+    rot_read16(x + (uint64_t)row * x_pitch, p0, L, v);
+    // ceil(L / 16) <= 2^32 (the call's length rule): the counter of a block the row has stays below 2^32
+    const uint32_t blk = tile * 256u + (uint32_t)t;
+    const uint8_t *keys = candidates + 32 * (size_t)row * (size_t)A;
+#pragma unroll 1
+    for (int a = 0; a < A; ++a) {
+        uint64_t acc = 0;
+        if (p0 < L) {
+            uint32_t r[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) r[j] = 0u;
+            chacha_raw_add(keys + 32 * (size_t)a, blk, kAbcd, r);
+            uint32_t nclip = 0;  // thrown away: the encode counts
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int64_t q = (int64_t)(int32_t)codec_encode<true>(v[j], clip, scale, r[j], nclip);
+                acc += (uint64_t)(q * q);
+            }
+        }
+        acc = round_wave_sum(acc);
+        if (lane == 0) wave_sums[w][a] = acc;
+    }
+    __syncthreads();
+    if (t < A)
+        atomicAdd(sumsq + (uint64_t)row * (uint64_t)A + (uint64_t)t,
+                  (unsigned long long)(wave_sums[0][t] + wave_sums[1][t] + wave_sums[2][t] + wave_sums[3][t]));
+}
+
+// One thread per row: chosen[row] = the smallest a < A with sumsq[row A + a] <= max_sumsq, or A when there is none,
+// and dither[row] = that candidate's 32 bytes (candidate 0's when there is none), copied byte by byte: no alignment
+// is asked of either array.
+__global__ __launch_bounds__(64) void round_select_kernel(const unsigned long long *__restrict__ sumsq,
+                                                          const uint8_t *__restrict__ candidates, int N, int A,
+                                                          unsigned long long max_sumsq, uint8_t *__restrict__ dither,
+                                                          uint32_t *__restrict__ chosen) {
+    const int row = blockIdx.x * 64 + threadIdx.x;
+    if (row >= N) return;
+    int pick = A;
+    for (int a = A - 1; a >= 0; --a)
+        if (sumsq[(size_t)row * (size_t)A + (size_t)a] <= max_sumsq) pick = a;
+    chosen[row] = (uint32_t)pick;
+    const uint8_t *src = candidates + 32 * ((size_t)row * (size_t)A + (size_t)(pick < A ? pick : 0));
+    for (int b = 0; b < 32; ++b) dither[32 * (size_t)row + b] = src[b];
+}
+
 #undef FLM_QR
 #undef FLM_ROTL
 
@@ -1630,6 +1707,22 @@ hipError_t launch_scale_rows(const float *d_x, uint64_t x_pitch, int N, uint64_t
     if (N < 1 || tiles == 0 || tiles > 0x7fffffffull / (uint64_t)N) return hipErrorInvalidValue;
     hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)(tiles * (uint64_t)N)), dim3(256), 0, stream, d_x, x_pitch, L,
                        (uint32_t)tiles, d_factors, d_out, out_pitch);
+    return hipGetLastError();
+}
+
+hipError_t launch_round_select(const float *d_x, uint64_t x_pitch, int N, uint64_t L, int frac_bits, float clip,
+                               const uint8_t *d_candidates, int attempts, uint64_t max_sumsq, uint64_t *d_sumsq,
+                               uint8_t *d_dither, uint32_t *d_chosen, hipStream_t stream) {
+    const uint64_t tiles = float_tiles(L);
+    if (N < 1 || tiles == 0 || tiles > 0x7fffffffull / (uint64_t)N || attempts < 1 || attempts > 8 || frac_bits < 0 ||
+        frac_bits > 30)
+        return hipErrorInvalidValue;
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_sumsq);
+    hipLaunchKernelGGL(round_sumsq_kernel, dim3((unsigned)(tiles * (uint64_t)N)), dim3(256), 0, stream, d_x, x_pitch, L,
+                       (uint32_t)tiles, d_candidates, attempts, clip, (float)(1u << frac_bits), sums);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(round_select_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, stream, sums, d_candidates, N,
+                       attempts, (unsigned long long)max_sumsq, d_dither, d_chosen);
     return hipGetLastError();
 }
 

@@ -1056,7 +1056,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip + round_bound"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1639,6 +1639,67 @@ int flm_l2_clip(flm_ctx *ctx, const float *x, int N, size_t L, float clip_norm, 
         return rc;
     if (int rc = flm_scale_rows_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, d_factors, hc.dev<float>(1), hc.pitch(1) / 4,
                                     ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
+// ---- conditional stochastic rounding in front of the encode (flm_call_args.h has the rules)
+
+namespace {
+int check_round(flm_ctx *ctx, uint64_t L, int frac_bits, float clip, int attempts) {
+    bool range = false;
+    const char *why = flm::rt::round_error(L, frac_bits, clip, attempts, &range);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
+}  // namespace
+
+int flm_round_check(uint64_t L, int frac_bits, float clip, int attempts) {
+    return check_round(nullptr, L, frac_bits, clip, attempts);
+}
+
+int flm_round_bound(float clip_norm, int frac_bits, uint64_t d, double tail, uint64_t *max_sumsq) {
+    bool range = false;
+    uint64_t b = 0;
+    const char *why = flm::rt::round_bound_error(clip_norm, frac_bits, d, tail, &range, &b);
+    if (int rc = refuse(nullptr, why, range ? FLM_ERANGE : FLM_EINVAL)) return rc;
+    if (max_sumsq) *max_sumsq = b;
+    return 0;
+}
+
+int flm_round_select_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int frac_bits, float clip,
+                         const uint8_t *d_candidates, int attempts, uint64_t max_sumsq, uint64_t *d_sumsq,
+                         uint8_t *d_dither, uint32_t *d_chosen, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_round(ctx, L, frac_bits, clip, attempts)) return rc;
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (N == 0) return 0;
+    if (!d_x || !d_candidates || !d_sumsq || !d_dither || !d_chosen) return fail(ctx, FLM_EINVAL, "NULL argument");
+    if (int rc = refuse(ctx, flm::rt::row_pitch_error(x_pitch, L))) return rc;
+    if (int rc = refuse(ctx, flm::rt::align16_error({d_x}))) return rc;
+    if ((uintptr_t)d_sumsq & 7 || (uintptr_t)d_chosen & 3)
+        return fail(ctx, FLM_EINVAL, "sumsq must be 8-byte aligned, chosen 4-byte aligned");
+    if (int rc = refuse(ctx, flm::rt::round_launch_error(N, L), FLM_ERANGE)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+    FLM_ON_DEVICE(ctx);
+    FLM_HIP(ctx, hipMemsetAsync(d_sumsq, 0, (size_t)N * (size_t)attempts * sizeof(uint64_t), s));  // the kernel adds into it
+    FLM_HIP(ctx, flm::launch_round_select(d_x, x_pitch, N, L, frac_bits, clip, d_candidates, attempts, max_sumsq, d_sumsq,
+                                          d_dither, d_chosen, s));
+    return 0;
+}
+
+int flm_round_select(flm_ctx *ctx, const float *x, int N, size_t L, int frac_bits, float clip, const uint8_t *candidates,
+                     int attempts, uint64_t max_sumsq, uint64_t *sumsq, uint8_t *dither, uint32_t *chosen) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_round(ctx, L, frac_bits, clip, attempts)) return rc;
+    if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
+    if (N == 0) return 0;
+    if (!x || !candidates || !sumsq || !dither || !chosen) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::round_select_args(N, L, attempts), {x, candidates, sumsq, dither, chosen});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = flm_round_select_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, L, frac_bits, clip, hc.dev<uint8_t>(1), attempts,
+                                      max_sumsq, hc.dev<uint64_t>(2), hc.dev<uint8_t>(3), hc.dev<uint32_t>(4), ctx->stream))
         return rc;
     return hc.finish();
 }

@@ -26,11 +26,12 @@ reference's own guards (SA_ServiceAgent.py:349, 502).
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
 from . import _lib
-from ._lib import p_f32, p_f64, p_i8, p_i64, p_u8, p_u32
+from ._lib import p_f32, p_f64, p_i8, p_i64, p_u8, p_u32, p_u64
 
 NONCE = b"\x00" * 8
 
@@ -460,6 +461,55 @@ class MaskEngine:
         self._check(rc, "flm_l2_clip")
         return (out[0] if one else out), factors, sumsq
 
+    # ------------------------------------- conditional stochastic rounding
+    def round_check(self, L: int, frac_bits: int, clip: float, attempts: int = 1):
+        """Raise unless round_select can take rows of L parameters at (frac_bits, clip) with `attempts` candidates:
+        L > 0, attempts in 1..8, the codec's rule for one client, L ceil(clip 2^frac_bits)^2 <= 2^64 - 1 and
+        ceil(L / 16) <= 2^32.  No device call.  flm_round_check."""
+        self._check(self.lib.flm_round_check(int(L), int(frac_bits), float(clip), int(attempts)), "flm_round_check")
+
+    def round_bound(self, clip_norm: float, frac_bits: int, d: int, tail: float | None = None, beta: float | None = None) -> int:
+        """max_sumsq = Delta^2, the bound on the sum of squares of a rounded row of d coordinates whose float norm the
+        L2 clip held to clip_norm (flm_round_bound; Kairouz et al., Algorithm 1).  One of tail = k >= 0 or beta in
+        (0, 1], a draw's failure probability, which is turned into k = sqrt(2 ln(1 / beta)) here, in Python: the
+        library takes k.  No device call."""
+        if (tail is None) == (beta is None):
+            raise RuntimeError("round_bound takes exactly one of tail and beta")
+        if beta is not None:
+            if not 0.0 < float(beta) <= 1.0:
+                raise RuntimeError("beta must be in (0, 1]")
+            tail = math.sqrt(2.0 * math.log(1.0 / float(beta)))
+        out = ctypes.c_uint64(0)
+        self._check(self.lib.flm_round_bound(float(clip_norm), int(frac_bits), int(d), float(tail), ctypes.byref(out)),
+                    "flm_round_bound")
+        return int(out.value)
+
+    def round_select(self, x: np.ndarray, frac_bits: int, clip: float, candidates, max_sumsq: int):
+        """For float32 rows x (N, L) or (L,) and candidates (N, A, 32) uint8 (or A 32-byte seeds for one row), A in
+        1..8: (dither_seeds (N, 32) uint8, chosen (N,) uint32, sumsq (N, A) uint64).  sumsq[i, a] is the sum of the
+        squares of the integers the stochastic encode rounds row i to under candidate a; chosen[i] the first a with
+        sumsq <= max_sumsq and dither_seeds[i] that candidate, to be handed to client_encode_*mask as its dither
+        seed.  chosen[i] == A: no candidate passed, dither_seeds[i] is candidate 0 and the row must not be sent.
+        flm_round_select."""
+        x, _ = _float_rows_array(x)
+        N, L = x.shape
+        if isinstance(candidates, (list, tuple)):
+            candidates = _seeds_array(candidates)
+        cand = np.ascontiguousarray(candidates, dtype=np.uint8)
+        if cand.ndim == 2 and N == 1:
+            cand = cand[None]
+        if cand.ndim != 3 or cand.shape[0] != N or cand.shape[2] != 32:
+            raise RuntimeError("candidates must be (N, A, 32) bytes")
+        A = cand.shape[1]
+        self.round_check(L, frac_bits, clip, A)
+        sumsq = np.empty((N, A), dtype=np.uint64)
+        dither = np.empty((N, 32), dtype=np.uint8)
+        chosen = np.empty(N, dtype=np.uint32)
+        rc = self.lib.flm_round_select(self.ctx, p_f32(x), N, L, int(frac_bits), float(clip), p_u8(cand), A, int(max_sumsq),
+                                       p_u64(sumsq), p_u8(dither), p_u32(chosen))
+        self._check(rc, "flm_round_select")
+        return dither, chosen, sumsq
+
     def decode_sum(self, total: np.ndarray, frac_bits: int, count: int = 1) -> np.ndarray:
         """float32(int32(total) / (count * 2^frac_bits)): the ring sum as the mean of `count` contributors."""
         total = np.ascontiguousarray(total, dtype=np.uint32)
@@ -732,6 +782,27 @@ class MaskEngine:
                                           _vp(out), op, _vp(nonfinite), self._stream_handle(stream))
         self._check(rc, "flm_rotate_clip_dev")
         return out
+
+    def round_select_dev(self, x, L: int, frac_bits: int, clip: float, candidates, max_sumsq: int, sumsq, dither, chosen,
+                         stream=None):
+        """Device round_select: x (N, >= L) float32 rows at their own stride; candidates a contiguous (N, A, 32) uint8
+        tensor; sumsq >= N A 64-bit words, dither a contiguous (N, 32) uint8 tensor and chosen (>= N,) 32-bit are
+        written.  Two launches enqueued on `stream`; nothing is synchronised, and dither may go straight into
+        client_encode_*mask_dev on the same stream.  flm_round_select_dev."""
+        N = x.shape[0] if x.dim() == 2 else -1
+        pitch = self._float_rows("x", x, N, L)
+        if candidates.dim() != 3 or candidates.shape[0] != N or candidates.shape[2] != 32 or candidates.element_size() != 1 \
+                or not candidates.is_contiguous():
+            raise RuntimeError(f"candidates must be a contiguous ({N}, A, 32) uint8 tensor")
+        A = candidates.shape[1]
+        self.round_check(L, frac_bits, clip, A)
+        _dev_vector("sumsq", sumsq, N * A, 8, "64-bit", flat=True)
+        _dev_bytes(dither, "dither", 32, N)
+        _dev_vector("chosen", chosen, N, 4, "32-bit")
+        rc = self.lib.flm_round_select_dev(self.ctx, _vp(x), pitch, N, int(L), int(frac_bits), float(clip), _vp(candidates), A,
+                                           int(max_sumsq), _vp(sumsq), _vp(dither), _vp(chosen), self._stream_handle(stream))
+        self._check(rc, "flm_round_select_dev")
+        return dither
 
     def prg_expand_dev(self, seeds_dev, out, L: int, slot0: int = 0, stream=None):
         K = seeds_dev.shape[0]

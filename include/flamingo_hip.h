@@ -353,8 +353,10 @@ int flm_rotate(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, co
 /* ------------------------------ L2 clip of float updates, in front of the rotation */
 
 /* The first step of the same recipe (cpSGD; Kairouz et al., above): every client scales its update to an L2 norm
- * of at most C before it rotates, rounds and adds noise, so that one client moves the sum by at most C in L2 --
- * the sensitivity the noise of flm_client_encode_noise_mask is measured against.  The codec's `clip` alone bounds
+ * of at most C before it rotates, rounds and adds noise.  C is the sensitivity *before* rounding: it bounds the float
+ * vector, and what enters the ring is the rounded integer vector, whose norm stochastic rounding can grow by up to
+ * sqrt(d) over d coordinates.  The sensitivity after rounding, the one the noise of flm_client_encode_noise_mask is
+ * measured against, is Delta / 2^f of the conditional rounding below.  The codec's `clip` alone bounds
  * coordinates, which bounds the L2 norm only by clip sqrt(L).  Turning C into a privacy statement is the caller's
  * business.  It stands where the reference says "For machine learning, replace it with model weights"
  * (agent/flamingo/SA_ClientAgent.py:300-304).  Normative, per row of L float32 parameters, clip radius C (float32,
@@ -407,6 +409,51 @@ int flm_rotate_clip_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, s
 int flm_l2_clip(flm_ctx *ctx, const float *x, int N, size_t L, float clip_norm, float *out, float *factors, double *sumsq);
 int flm_rotate_clip(flm_ctx *ctx, const float *x, int N, size_t L, int log2_block, const uint8_t key[32], float clip_norm,
                     float *out, uint32_t *nonfinite, float *factors, double *sumsq);
+
+/* ------------------------------ conditional stochastic rounding: a bound on the rounded update's L2 norm */
+
+/* The step between the rotation and the stochastic encode of the same recipe (Kairouz et al., above, Algorithm 1):
+ * the rounding randomness is redrawn until the rounded integer vector q satisfies ||q||_2^2 <= Delta^2, so that
+ * Delta / 2^f, which depends on the data through C alone, is a sensitivity the caller can hand to an accountant.
+ * It stands where the reference says "For machine learning, replace it with model weights"
+ * (agent/flamingo/SA_ClientAgent.py:300-304).  The pass picks the dither seed; the encode calls above then take
+ * that seed unchanged, in every pack and noise mode.  Normative, per row of L float32 parameters, codec parameters
+ * (f, c) and a 32-byte dither seed:
+ *   q_l = int32 of the codec's stochastic encode(x_l) under that seed, r = PRG(seed)[l] indexed by parameter:
+ *     exactly the integer flm_client_encode_mask rounds parameter l to, in every pack mode, before any noise;
+ *   Q(seed) = sum_{l < L} q_l^2, an exact integer in uint64.  Parameters >= L and the padding of a row are never
+ *     read as input.  Integer addition is associative: any order of summing gives the same bits.
+ *   Of A candidate seeds the choice is the smallest a with Q(candidate a) <= max_sumsq.
+ * The bound (flm_round_bound), all in float64, each operation rounded on its own, in this order:
+ *   s = ((double)C * 2^f) * (1 + 2^-19); r = sqrt((double)d); b1 = (s + r) * (s + r);
+ *   b2 = (s * s + (double)d * 0.25) + tail * (s + r * 0.5); *max_sumsq = (uint64)floor(min(b1, b2)).
+ *   C is the L2 clip radius, d the number of coordinates encoded (L_rot behind a rotation), tail = k =
+ *   sqrt(2 ln(1 / beta)) >= 0 for a per-draw failure probability of at most beta = exp(-k^2 / 2); the caller passes
+ *   k, so the library calls no log.  The factor 1 + 2^-19 covers the clip's 2^-22 and the rotation's
+ *   (h + 1) 2^-24 <= 13 * 2^-24.  E||q||^2 is about ||t||^2 + d / 6 while b2 carries d / 4, so few draws fail.
+ *
+ * flm_round_check (SA_ClientAgent.py:300-304): FLM_EINVAL for L = 0, attempts outside 1..8, and what flm_codec_check
+ * refuses with n = 1 (with its code: FLM_ERANGE when ceil(c * 2^f) alone passes 2^31 - 1); FLM_ERANGE when
+ * L * B^2 > 2^64 - 1, B = ceil(c * 2^f) in exact integers (Q could wrap), or ceil(L / 16) > 2^32 (the dither
+ * stream's block counter).  No context, no device.
+ * flm_round_bound (SA_ClientAgent.py:300-304): FLM_EINVAL for C not finite and positive, f outside 0..30, d = 0, or
+ * tail negative or not finite; FLM_ERANGE for a result >= 2^63.  No context, no device. */
+int flm_round_check(uint64_t L, int frac_bits, float clip, int attempts);
+int flm_round_bound(float clip_norm, int frac_bits, uint64_t d, double tail, uint64_t *max_sumsq);
+/* The pass on device rows (SA_ClientAgent.py:300-304): d_candidates is N x attempts x 32 bytes, candidate a of row i
+ * at (i * attempts + a) * 32; d_sumsq[i * attempts + a] = Q(that candidate) (N x attempts uint64, 8-byte aligned,
+ * zeroed on the stream first: the kernel adds into it); d_chosen[i] (N uint32) the choice, and d_dither[i] (N x 32
+ * bytes) that candidate's bytes.  When no candidate passes d_chosen[i] = attempts and d_dither[i] holds candidate
+ * 0's bytes: the row is unusable and the caller must look at d_chosen.  flm_client_encode_mask_dev's rules for d_x,
+ * x_pitch and alignment.  Two launches enqueued on `stream`; nothing is synchronised, and d_dither may be handed
+ * straight to flm_client_encode_*_mask_dev on the same stream.  FLM_ERANGE when N ceil(L / 4096) passes 2^31 - 1
+ * workgroups; N = 0 does nothing. */
+int flm_round_select_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, size_t L, int frac_bits, float clip,
+                         const uint8_t *d_candidates, int attempts, uint64_t max_sumsq, uint64_t *d_sumsq,
+                         uint8_t *d_dither, uint32_t *d_chosen, void *stream);
+/* The host-pointer form, synchronous (SA_ClientAgent.py:300-304): x N x L packed, the other arrays as above. */
+int flm_round_select(flm_ctx *ctx, const float *x, int N, size_t L, int frac_bits, float clip, const uint8_t *candidates,
+                     int attempts, uint64_t max_sumsq, uint64_t *sumsq, uint8_t *dither, uint32_t *chosen);
 
 /* Device-resident PRG expansion: d_out[k*pitch + l] = PRG(seed k)[slot0 + l]. */
 int flm_prg_expand_dev(flm_ctx *ctx, const uint8_t *d_seeds, int K, size_t L, uint64_t slot0,

@@ -158,7 +158,12 @@ static void check_round_lists() {
                     // flm_rotate_clip and flm_l2_clip: the optional outputs together or none of them
                     through_bounce(rotate_args(N, L, L_rot, opt, opt, opt));
                     through_bounce(l2_clip_args(N, L, opt, !opt));
+                    through_bounce(round_select_args(N, L, opt ? 8 : 1));   // flm_round_select: nothing optional
                 }
+    const ArgList rs = round_select_args(3, 5, 4);
+    CHECK(rs.n == 5 && rs.a[0].slot == rows && rs.a[0].in_place && !rs.a[0].is_out && rs.a[0].width == 20 && rs.a[0].rows == 3 &&
+          rs.a[1].width == 3 * 4 * 32 && !rs.a[1].is_out && rs.a[2].is_out && rs.a[2].width == 3 * 4 * 8 && !rs.a[2].in_place &&
+          rs.a[3].is_out && rs.a[3].width == 96 && rs.a[4].is_out && rs.a[4].width == 12 && !names_slot_twice(rs));
     const ArgList rc = rotate_args(3, 5, 16, true, true, false), lc = l2_clip_args(3, 5, false, true);
     CHECK(rc.n == 6 && rc.a[0].width == 20 && rc.a[1].width == 64 && rc.a[1].is_out && rc.a[3].present && rc.a[4].present &&
           rc.a[4].is_out && rc.a[4].width == 12 && rc.a[4].slot == ec_flags && !rc.a[5].present && !names_slot_twice(rc));
@@ -297,6 +302,26 @@ static void check_round_rules() {
     CHECK(l2_clip_error(4096ull * 0x7fffffffull + 1, 1.0f, 1, &range, &work) && range);
     CHECK(l2_clip_error(~0ull, 1.0f, 1, &range, &work) && range && l2_clip_error(~0ull, 1.0f, 0, &range, &work) && !range);
     CHECK(l2_clip_error(4096ull << 20, 1.0f, 2048, &range, &work) && range);
+    // conditional rounding's rule: L > 0, attempts in 1..8, the codec's rule for one client, L B^2 <= 2^64 - 1 and
+    // ceil(L / 16) <= 2^32 (both FLM_ERANGE)
+    CHECK(!round_error(4096, 7, 1.0f, 4, &range) && !range && !round_error(1, 0, 1000.0f, 1, &range) && !round_error(5, 30, 1.0f, 8, &range));
+    CHECK(round_error(0, 7, 1.0f, 4, &range) && !range && round_error(5, 7, 1.0f, 0, &range) && !range && round_error(5, 7, 1.0f, 9, &range) && !range);
+    CHECK(round_error(5, 31, 1.0f, 1, &range) && !range && round_error(5, 7, NAN, 1, &range) && !range && round_error(5, 30, 4.0f, 1, &range) && range);
+    CHECK(!round_error(15, 30, 1.0f, 1, &range) && round_error(16, 30, 1.0f, 1, &range) && range);            // 16 2^60 = 2^64
+    CHECK(!round_error(1ull << 36, 13, 1.0f, 1, &range) && round_error(1ull << 36, 14, 1.0f, 1, &range) && range);
+    CHECK(!round_error(1ull << 36, 0, 1.0f, 8, &range) && round_error((1ull << 36) + 1, 0, 1.0f, 8, &range) && range);
+    CHECK(round_error(~0ull, 0, 1.0f, 1, &range) && range);                                                  // B = 1: the block counter's
+    CHECK(!round_launch_error(1, 4096ull * 0x7fffffffull) && round_launch_error(1, 4096ull * 0x7fffffffull + 1) &&
+          round_launch_error(2048, 4096ull << 20) && !round_launch_error(0, ~0ull));
+    // ... and its bound: float64 in a fixed order, FLM_ERANGE from 2^63
+    uint64_t bound = 7;
+    CHECK(!round_bound_error(1.0f, 0, 1, 0.0, &range, &bound) && bound == 1);       // s = 1 + 2^-19: min(4.000004, 1.250004)
+    CHECK(!round_bound_error(2.28125f, 7, 4096, 1.0, &range, &bound) && bound > 292ull * 292 && bound < 356ull * 356);
+    for (float c : {0.0f, -1.0f, INFINITY, NAN}) CHECK(round_bound_error(c, 7, 16, 1.0, &range, &bound) && !range);
+    CHECK(round_bound_error(1.0f, -1, 16, 1.0, &range, &bound) && round_bound_error(1.0f, 31, 16, 1.0, &range, &bound) &&
+          round_bound_error(1.0f, 7, 0, 1.0, &range, &bound) && round_bound_error(1.0f, 7, 16, -1.0, &range, &bound) &&
+          round_bound_error(1.0f, 7, 16, NAN, &range, &bound) && round_bound_error(1.0f, 7, 16, INFINITY, &range, &bound) && !range);
+    CHECK(round_bound_error(4.0f, 30, 1, 0.0, &range, &bound) && range && !round_bound_error(2.0f, 30, 1, 0.0, &range, &bound) && !range);
     CHECK(!slot0_error(0) && !slot0_error(16) && slot0_error(8) && slot0_error(1) && !slot0_error(1ull << 36));
     CHECK(!slot_range_error(0, 1ull << 36) && slot_range_error(16, 1ull << 36) && slot_range_error(1ull << 36, 1) &&
           !slot_range_error(1ull << 36, 0) && slot_range_error(~0ull, 2));
