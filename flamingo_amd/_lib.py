@@ -62,6 +62,12 @@ SIGNATURES = {
                                                 _vp, _int, _vp, _vp, _sz, _vp, _vp]),
     "flm_decode_unpack_noise": (_int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _f32p]),
     "flm_decode_unpack_noise_dev": (_int, [_vp, _vp, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _vp, _vp]),
+    "flm_codec_check_gauss": (_int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64, _u64]),
+    "flm_dgauss_check_table": (_int, [_u64p, _int]),
+    "flm_client_encode_gauss_mask": (_int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _int, _u8p,
+                                            _int, _u64p, _u8p, _u32p, _u32p]),
+    "flm_client_encode_gauss_mask_dev": (_int, [_vp, _vp, _sz, _int, _i64p, _vp, _i8p, _sz, _int, ctypes.c_float, _int,
+                                                _vp, _int, _vp, _vp, _vp, _sz, _vp, _vp]),
     "flm_rotate_check": (_int, [_u64, _int, ctypes.POINTER(_u64)]),
     "flm_rotate_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _int, _vp, _sz, _vp, _vp]),
     "flm_rotate": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, _int, _f32p, _u32p]),

@@ -83,6 +83,11 @@ def parse(argv):
     # --float_inputs, and headroom for n (ceil(CLIP 2^F) + BITS / 2); turning BITS into an (epsilon, delta) is the
     # caller's business; off by default
     ap.add_argument("--dp_noise", type=int, default=0, metavar="BITS")
+    # ... or a share of discrete Gaussian noise of parameter SIGMA truncated to +-TAIL (an integer in 1..512, default
+    # ceil(10 SIGMA)), sampled from a cumulative table inside the same kernel (protocol.configure(dp_gauss=...)); needs
+    # --float_inputs and headroom for n (ceil(CLIP 2^F) + TAIL); not together with --dp_noise; the accounting (SIGMA, the
+    # sensitivity of --round_bound, dgauss.tail_mass for delta) is the caller's business; off by default
+    ap.add_argument("--dp_gauss", default=None, metavar="SIGMA[,TAIL]")
     # every client rotates its float update by a randomised Hadamard transform in blocks of 2^LOG2BLOCK parameters
     # (4..12) before the encode, under a public key per iteration, and the server rotates the decoded mean back
     # (protocol.configure(rotate=...)): CLIP then bounds the rotated coordinates, about ||x||_2 / 2^(LOG2BLOCK / 2)
@@ -127,6 +132,22 @@ def parse_round_bound(spec):
         raise ValueError("--round_bound takes TAIL[,ATTEMPTS]")
     tail, attempts = float(parts[0]), int(parts[1]) if len(parts) == 2 else 4
     return (tail, attempts) if tail != 0.0 else None
+
+
+def parse_dp_gauss(spec):
+    """"SIGMA" or "SIGMA,TAIL" -> (sigma, tail), tail ceil(10 sigma) when left out; None, "" or a SIGMA of 0 -> None."""
+    if not spec:
+        return None
+    from .. import dgauss
+    parts = [s.strip() for s in str(spec).split(",")]
+    try:
+        if len(parts) not in (1, 2):
+            raise ValueError
+        sigma = float(parts[0])
+        tail = int(parts[1]) if len(parts) == 2 else dgauss.default_tail(sigma)
+    except ValueError:
+        raise SystemExit("--dp_gauss takes SIGMA[,TAIL], TAIL an integer")
+    return (sigma, tail) if sigma != 0.0 else None
 
 
 def offline_schedule(n: int, iterations: int, always=(), dropout: float = 0.0) -> dict:
@@ -198,7 +219,8 @@ def _run(args):
                     authenticate_shares=True if args.authenticate_shares else None,
                     dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs),
                     dp_noise=args.dp_noise, rotate=args.rotate, l2_clip=args.l2_clip,
-                    round_bound=parse_round_bound(args.round_bound) or False)
+                    round_bound=parse_round_bound(args.round_bound) or False,
+                    dp_gauss=parse_dp_gauss(args.dp_gauss) or False)
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -266,6 +288,13 @@ def _run(args):
                 b, f = param.codec_noise_bits(), param.codec()[0]
                 noised = (f", noise of {b} coins: standard deviation of the difference {float(np.std(diff)):.3e}, "
                           f"expected sqrt(|U| b) / (2 |U| 2^f) = {np.sqrt(u * b) / (2.0 * u * 2.0 ** f):.3e}")
+            if param.dp_gauss() is not None:   # the sum of |U| table-sampled shares: |U| times the table's own variance
+                from .. import dgauss
+                (sigma, tail), f = param.dp_gauss(), param.codec()[0]
+                var = float(dgauss.moments(param.dp_gauss_table())[1])
+                noised = (f", discrete Gaussian noise sigma = {sigma:g}, tail = {tail}: standard deviation of the difference "
+                          f"{float(np.std(diff)):.3e}, expected sqrt(|U| Var) / (|U| 2^f) = "
+                          f"{np.sqrt(u * var) / (u * 2.0 ** f):.3e}")
             rotated = nonfinite = ""
             if param.rotate_bits():
                 rotated = f", rotated in blocks of 2^{param.rotate_bits()}"

@@ -102,7 +102,7 @@ class SA_ClientAgent(Agent):
         self.round_attempt = None    # ... with --round_bound: the overall index of the candidate seed that was accepted
         self.rounded_sumsq = None    # (0: the first drawn), and the rounded update's sum of squares under it
         self.round_attempts = {}     # ... iteration -> round_attempt, for the run's report
-        self.noise_seed = None       # float inputs with --dp_noise: the last iteration's noise seed
+        self.noise_seed = None       # float inputs with --dp_noise or --dp_gauss: the last iteration's noise seed
         pki = param.pki(num_clients)
         self.secret_key = pki.client_sk[id]
         self.public_key = pki.client_pk[id]
@@ -286,6 +286,12 @@ class SA_ClientAgent(Agent):
                 vec, clipped = param.engine().client_encode_noise_mask(seg, seeds, signs, L, x, frac_bits,
                                                                        clip, param.codec_pack(), dither=dither,
                                                                        noise_bits=noise_bits, noise=[self.noise_seed],
+                                                                       return_clipped=True)
+            elif param.dp_gauss() is not None:   # the discrete Gaussian share: the same one draw, the table built in configure
+                self.noise_seed = bytes(self.random_state.randint(0, 256, size=32, dtype=np.uint8))
+                vec, clipped = param.engine().client_encode_gauss_mask(seg, seeds, signs, L, x, frac_bits, clip,
+                                                                       param.dp_gauss_table(), [self.noise_seed],
+                                                                       pack=param.codec_pack(), dither=dither,
                                                                        return_clipped=True)
             elif param.codec_pack() == 1:
                 vec, clipped = param.engine().client_encode_mask(seg, seeds, signs, L, x, frac_bits, clip,

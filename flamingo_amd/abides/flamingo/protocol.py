@@ -75,6 +75,13 @@ _codec_pack: int = 1
 # (MaskEngine.client_encode_noise_mask); only the sum of the shares appears in what the server unmasks.  It needs
 # the float inputs.  Off by default, so a run sends what it always sent and draws what it always drew.
 _dp_noise: int = 0
+# ... or of discrete Gaussian noise (config_flamingo's --dp_gauss SIGMA[,TAIL]): the share is sampled from a cumulative
+# table of the discrete Gaussian of parameter SIGMA truncated to +-TAIL (flamingo_amd.dgauss.table, built once here),
+# inside the same kernel (MaskEngine.client_encode_gauss_mask); rows decode as binomial rows of 2 TAIL coins do.  It
+# needs the float inputs and excludes --dp_noise.  Off (None) by default, so a run calls what it always called, sends
+# what it always sent and draws what it always drew.
+_dp_gauss: tuple | None = None          # (sigma, tail)
+_dp_gauss_table = None                  # the (2 tail,) uint64 table of _dp_gauss
 # Randomised block Hadamard rotation (config_flamingo's --rotate LOG2BLOCK): every client rotates its float update
 # in blocks of 2^LOG2BLOCK parameters under the iteration's public key before the encode (MaskEngine.rotate), the
 # server rotates the decoded mean back; the clip then bounds rotated coordinates.  It needs the float inputs.  Off
@@ -98,7 +105,8 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
               gpu_deal: bool | None = None, check_signatures: bool | None = None,
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
               authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None,
-              dp_noise: int | None = None, rotate: int | None = None, l2_clip: float | None = None, round_bound=None):
+              dp_noise: int | None = None, rotate: int | None = None, l2_clip: float | None = None, round_bound=None,
+              dp_gauss=None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
     "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
     many parameters into a ring word, False turns them off, None leaves them as they are.  dp_noise: the coin
@@ -109,12 +117,17 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
     and positive; 0 turns it off, None leaves it as it is); it needs the float inputs, and turning those off turns it
     off.  round_bound: (tail, attempts) or a bare tail (attempts = 4) turns conditional stochastic rounding on: tail =
     k >= 0 of the bound, attempts in 1..8 candidate dither seeds per batch; 0 or False turns it off, None leaves it as
-    it is; it needs stochastic float inputs and the L2 clip, and turning either off turns it off."""
+    it is; it needs stochastic float inputs and the L2 clip, and turning either off turns it off.  dp_gauss: (sigma,
+    tail) or a bare sigma (tail = ceil(10 sigma)) turns the discrete Gaussian noise share on, tail in 1..512; 0 or False
+    turns it off, None leaves it as it is; it needs the float inputs (turning those off turns it off) and is refused
+    together with dp_noise."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
     global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate, _l2_clip, _round_bound
+    global _dp_gauss, _dp_gauss_table
     if codec is not None:
         if codec is False:
             _codec, _codec_pack, _dp_noise, _rotate, _l2_clip, _round_bound = None, 1, 0, 0, None, None
+            _dp_gauss, _dp_gauss_table = None, None
         else:
             f, c, mode = codec[:3]
             pack = int(codec[3]) if len(codec) == 4 else 1
@@ -125,13 +138,32 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
             if pack not in (1, 2, 4):
                 raise ValueError("codec pack must be 1, 2 or 4")
             _codec, _codec_pack = (int(f), float(c), mode), pack
+    gauss_off = dp_gauss is False or (dp_gauss is not None and not isinstance(dp_gauss, (tuple, list)) and float(dp_gauss) == 0.0)
     if dp_noise is not None:
         b = int(dp_noise)
         if b < 0 or b > 1024 or b % 2:
             raise ValueError("dp_noise must be even and in 0..1024")
         if b and _codec is None:
             raise ValueError("dp_noise needs the float inputs (codec=...)")
+        if b and not gauss_off and (dp_gauss is not None or _dp_gauss is not None):
+            raise ValueError("dp_noise and dp_gauss exclude each other")
         _dp_noise = b
+    if dp_gauss is not None:
+        if gauss_off:
+            _dp_gauss, _dp_gauss_table = None, None
+        else:
+            from ... import dgauss
+            sigma = float(dp_gauss[0] if isinstance(dp_gauss, (tuple, list)) else dp_gauss)
+            tail = dp_gauss[1] if isinstance(dp_gauss, (tuple, list)) and len(dp_gauss) > 1 and dp_gauss[1] is not None \
+                else dgauss.default_tail(sigma) if sigma > 0.0 else 0
+            if _codec is None:
+                raise ValueError("dp_gauss needs the float inputs (codec=...)")
+            if _dp_noise:
+                raise ValueError("dp_noise and dp_gauss exclude each other")
+            if int(tail) != tail or not 1 <= int(tail) <= dgauss.MAX_TAIL:
+                raise ValueError(f"dp_gauss's tail must be an integer in 1..{dgauss.MAX_TAIL} (the default is ceil(10 sigma))")
+            table = dgauss.table(sigma, int(tail))      # refuses a sigma that is not finite and positive
+            _dp_gauss, _dp_gauss_table = (sigma, int(tail)), table
     if rotate is not None:
         h = int(rotate)
         if h != 0 and not 4 <= h <= 12:
@@ -344,6 +376,22 @@ def codec_pack() -> int:
 def codec_noise_bits() -> int:
     """Coin flips per parameter of every client's binomial noise share: 0 when off (or the float inputs are)."""
     return _dp_noise if _codec is not None else 0
+
+
+def dp_gauss() -> tuple | None:
+    """(sigma, tail) of the clients' discrete Gaussian noise share, or None when it is off."""
+    return _dp_gauss if _codec is not None else None
+
+
+def dp_gauss_table():
+    """The cumulative table of dp_gauss() (2 tail uint64 entries, built once by configure), or None."""
+    return _dp_gauss_table if _codec is not None else None
+
+
+def decode_noise_bits() -> int:
+    """What the packed decode and the headroom rule take for noise_bits: the binomial share's coins, or 2 tail of the
+    discrete Gaussian one (the same bias B + tail); 0 without noise."""
+    return 2 * _dp_gauss[1] if dp_gauss() is not None else codec_noise_bits()
 
 
 def rotate_bits() -> int:

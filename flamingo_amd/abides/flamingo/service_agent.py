@@ -89,7 +89,11 @@ class SA_ServiceAgent(Agent):
             kw = {"pack": param.codec_pack()} if param.codec_pack() != 1 else {}
             if param.codec_noise_bits():
                 kw.update(noise_bits=param.codec_noise_bits(), L=param.rotated_len())
-            param.engine().codec_check(param.codec()[0], param.codec()[1], n, **kw)
+            if param.dp_gauss() is not None:   # the table-sampled share: tail where noise_bits / 2 stands, its own length rule
+                param.engine().codec_check_gauss(param.codec()[0], param.codec()[1], param.dp_gauss()[1], n,
+                                                 pack=param.codec_pack(), L=param.rotated_len())
+            else:
+                param.engine().codec_check(param.codec()[0], param.codec()[1], n, **kw)
         # conditional rounding: the bound every client holds its rounded update's sum of squares to, computed here by
         # the clients' own call; sqrt(round_max_sumsq) / 2^f is the L2 sensitivity of the sum to one client
         self.round_max_sumsq = None
@@ -377,9 +381,10 @@ class SA_ServiceAgent(Agent):
     def _mean(self, count, on, unpacked, packed, *head):
         """The final sum as the mean over `count` clients, by a method of `on` (the store, or the engine for a sum on
         the host): unpacked(*head, frac_bits, count) at pack 1 (in place), else packed(*head, L, frac_bits, clip, pack,
-        count), every device unpacking its word shard into its floats; with noise the bias carries noise_bits / 2.
+        count), every device unpacking its word shard into its floats; with noise the bias carries noise_bits / 2 (the discrete
+        Gaussian share's tail: noise_bits = 2 tail).
         L is param.rotated_len(): with the rotation on the codec's parameters are the rotated ones."""
-        (frac_bits, clip), pack, noise_bits = param.codec()[:2], param.codec_pack(), param.codec_noise_bits()
+        (frac_bits, clip), pack, noise_bits = param.codec()[:2], param.codec_pack(), param.decode_noise_bits()
         if pack == 1:
             return getattr(on, unpacked)(*head, frac_bits, count)
         kw = {"noise_bits": noise_bits} if noise_bits else {}

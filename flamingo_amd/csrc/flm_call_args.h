@@ -122,6 +122,44 @@ inline const char *codec_error(int frac_bits, float clip, int pack, bool unpacke
     return nullptr;
 }
 
+// flm_codec_check_gauss, flm_client_encode_gauss_mask[_dev]: the codec's rule with the table mode of the noise, each
+// client adding Z in [-tail, tail] sampled from a cumulative table of T = 2 tail entries.  tail in 1..512 (the table is
+// at most 8 KiB, and 2 tail <= 1024 is a noise_bits the decodes accept); tail = 0 is not "off": the calls without noise
+// exist.  Then the codec's own rule at any pack, and, FLM_ERANGE (*range set): headroom with B_n = B + tail in B's place
+// (unpacked n B_n <= 2^31 - 1, packed n 2 B_n <= 2^W - 1); for a row of L_params > 0 parameters 2 ceil(L_params / 16)
+// <= 2^32 blocks of the noise stream (two per parameter block), whose block counter has no high word.
+inline const char *codec_gauss_error(int frac_bits, float clip, int pack, int tail, int64_t n, uint64_t L_params, bool *range,
+                                     uint32_t *bias = nullptr, uint32_t *bias_n = nullptr) {
+    *range = false;
+    if (tail < 1 || tail > 512) return "tail must be in 1..512";
+    uint32_t B = 0;
+    if (const char *why = codec_error(frac_bits, clip, pack, true, 0, n, 0, range, &B)) return why;
+    *range = true;
+    const uint64_t Bn = (uint64_t)B + (uint64_t)tail, each = pack == 1 ? Bn : 2 * Bn;
+    const uint64_t top = pack == 1 ? 2147483647ull : (uint64_t(1) << (32 / pack)) - 1;
+    if (each > top || (uint64_t)n > top / each)
+        return "that many contributors of magnitude up to ceil(clip 2^frac_bits) + tail have no headroom";
+    if (L_params / 16 + (L_params % 16 ? 1 : 0) > (uint64_t(1) << 31))
+        return "the noise stream of a row that long ends beyond 2^32 blocks (its block counter has no high word)";
+    *range = false;
+    if (bias) *bias = B;
+    if (bias_n) *bias_n = (uint32_t)Bn;
+    return nullptr;
+}
+// flm_dgauss_check_table, and the host form of the call: T = 2 tail entries that never decrease.  (The device form
+// cannot see its table: whatever it holds, the kernel's count stays in [0, T] and no field leaves its headroom.)
+inline const char *dgauss_table_error(const uint64_t *cdt, int tail) {
+    if (!cdt) return "NULL argument";
+    if (tail < 1 || tail > 512) return "tail must be in 1..512";
+    for (int j = 1; j < 2 * tail; ++j)
+        if (cdt[j] < cdt[j - 1]) return "the table must be non-decreasing";
+    return nullptr;
+}
+// the kernel copies the table to LDS with 8-byte loads (NULL passes: refused as an absent array)
+inline const char *cdt_align_error(const void *d_cdt) {
+    return (uintptr_t)d_cdt & 7 ? "cdt must be 8-byte aligned" : nullptr;
+}
+
 // words of a row of L parameters
 constexpr size_t packed_words(size_t L, int pack) { return (L + (size_t)pack - 1) / (size_t)pack; }
 
@@ -439,6 +477,13 @@ inline ArgList client_encode_mask_args(size_t N, size_t K, size_t L, size_t Lw, 
     return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
              arg_in(N * 32, bytes_in, dither), arg_in(N * 32, ec_scal, noise),
              in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))), arg_out(N * 4, bytes_out, clipped)}, 6};
+}
+// flm_client_encode_gauss_mask: client_encode_mask_args with the noise seeds always there and the table's T = 2 tail
+// uint64 entries after them, in ec_dig
+inline ArgList client_encode_gauss_mask_args(size_t N, size_t K, size_t L, size_t Lw, bool dither, size_t T, bool clipped) {
+    return {{in_place(pitched(arg_in(L * 4, rows), N, host_row_pitch(L))), arg_in(K * 32, seeds),
+             arg_in(N * 32, bytes_in, dither), arg_in(N * 32, ec_scal), arg_in(T * 8, ec_dig),
+             in_place(pitched(arg_out(Lw * 4, out), N, host_row_pitch(Lw))), arg_out(N * 4, bytes_out, clipped)}, 7};
 }
 // sum (Lw words), out (L floats); Lw = L: the unpacked decode, which may then run in place
 inline ArgList decode_unpack_args(size_t L, size_t Lw) {

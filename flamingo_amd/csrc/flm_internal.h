@@ -60,6 +60,13 @@ hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const i
                               const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise, uint64_t L,
                               const CodecParams &c, uint32_t *d_out, uint64_t out_pitch, uint32_t *d_clipped,
                               hipStream_t stream);
+// launch_encode_mask with the noise of the table mode (encode_gauss_mask_kernel), tail in 1..512: d_noise N x 32 bytes
+// and d_cdt 2 tail uint64 entries, 8-byte aligned, both read; c.noise_bits is not.  The launch asks 16 tail bytes of
+// dynamic LDS for the table.
+hipError_t launch_encode_gauss_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                                    const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise,
+                                    const uint64_t *d_cdt, int tail, uint64_t L, const CodecParams &c, uint32_t *d_out,
+                                    uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream);
 // d_out[l] = float32(float64(int32(d_sum[l])) / denom), l < n; d_out may be d_sum; both 16-byte aligned
 hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, float *d_out, hipStream_t stream);
 // d_out[pack l' + j] = float32(float64(field j of d_sum[l'] - count_bias) / denom) for the L parameters; d_out is

@@ -1019,6 +1019,69 @@ __device__ __forceinline__ void noise_block_add(const uint8_t *__restrict__ key,
     }
 }
 
+// The discrete Gaussian mechanism's share, sampled from a cumulative table (tests/dgauss_cases.py):
+// cdt[0 .. T - 1] uint64, non-decreasing, T = 2 tau; parameter l draws u = hi 2^32 + lo, hi word 16 (2 beta) + l % 16
+// and lo word 16 (2 beta + 1) + l % 16 of PRG(noise_i), beta = l / 16; z = #{j < T : cdt[j] <= u} - tau; q' = q + z.
+// Unpacked the ring word is uint32(q'); packed the field is q' + B + tau = q + B + the count.
+
+// The count of table entries <= u: a bisection without a branch on data.  The trip count depends on T alone (wave-
+// uniform, host-known).  Whatever the table holds, every index read is below T and the count is in [0, T]: base + len
+// never grows, and the last probe is tab[base] with len = 1.  The compare is a 64-bit unsigned one.  G draws go
+// through the loop together (hi[g .. g + G) become their counts), so that G LDS reads are in flight at a time.
+template <int G>
+__device__ __forceinline__ void cdt_counts(const uint64_t *tab, uint32_t T, uint32_t (&hi)[16], const uint32_t (&lo)[16],
+                                           int g) {
+    uint64_t u[G];
+    uint32_t base[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) u[j] = ((uint64_t)hi[g + j] << 32) | lo[g + j], base[j] = 0u;
+#pragma unroll 1
+    for (uint32_t len = T; len > 1u;) {
+        const uint32_t h = len >> 1;
+#pragma unroll
+        for (int j = 0; j < G; ++j) base[j] += tab[base[j] + h - 1u] <= u[j] ? h : 0u;
+        len -= h;
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j) hi[g + j] = base[j] + (tab[base[j]] <= u[j] ? 1u : 0u);
+}
+
+// One noise unit of the table mode: ChaCha blocks 2 blk (high words) and 2 blk + 1 (low words) of the client's noise
+// stream are the 16 draws of parameter block blk, at par..par + 15; their counts add as noise_block_add's popcounts do.
+// The high words stay in registers across the second block.
+template <int P>
+__device__ __forceinline__ void gauss_block_add(const uint8_t *__restrict__ key, uint32_t blk, const uint64_t *tab,
+                                                uint32_t T, uint64_t par, uint64_t L, uint32_t (&m)[16], u32x4 *Q) {
+    uint32_t hi[16], lo[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) hi[j] = lo[j] = 0u;
+    chacha_raw_add(key, 2u * blk, kAbcd, hi);
+    chacha_raw_add(key, 2u * blk + 1u, kAbcd, lo);
+#pragma unroll
+    for (int g = 0; g < 16; g += 4) cdt_counts<4>(tab, T, hi, lo, g);
+    if constexpr (P == 1) {
+        // parameters past L are never stored, so their noise needs no predicate here
+#pragma unroll
+        for (int j = 0; j < 16; ++j) m[j] += hi[j];
+    } else {
+        constexpr int W = 32 / P;
+        // a stored word's upper fields may lie past L: those parameters get no noise
+        const uint32_t have = par < L ? (uint32_t)(L - par < 16 ? L - par : 16) : 0u;
+        uint32_t e[16 / P];
+#pragma unroll
+        for (int q = 0; q < 16 / P; ++q) {
+            e[q] = 0u;
+#pragma unroll
+            for (int jj = 0; jj < P; ++jj) {
+                const int j = P * q + jj;
+                e[q] += ((uint32_t)j < have ? hi[j] : 0u) << (W * jj);
+            }
+        }
+        Q[0] += u32x4{e[0], e[1], e[2], e[3]};
+        if constexpr (P == 2) Q[1] += u32x4{e[4], e[5], e[6], e[7]};
+    }
+}
+
 // ------------------------------------------------------------ the encode-mask kernel
 // The parts of encode_mask_kernel below that stand on their own.
 
@@ -1214,6 +1277,107 @@ void encode_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
         clipped_add(clipped, i, nclip, lane);
     }
     tile_meet_store<OWN, FIFTH ? 5 : 4>(lds, R, m, nneg, out + (uint64_t)i * out_pitch, tile, Lw);
+}
+
+// encode_mask_kernel's sibling for the table mode of the noise (gauss_block_add): the same workgroup, units, dealing,
+// encoding pass and meet as encode_mask_kernel<P, STOCHASTIC, true>, over the same helpers, in a kernel of its own so
+// that encode_mask_kernel's twelve instantiations keep their arguments and their instructions.  What differs:
+// the workgroup first copies the T = 2 tau table entries to LDS, behind the waves' regions (dynamic LDS of 8 T bytes:
+// the launch sizes it by T, not by the largest table); a client has P noise units, one per parameter block of the
+// lane, each two ChaCha blocks and 16 counts; at P = 1 the encoding wave subtracts tau where it subtracts b / 2 there.
+// No waves-per-SIMD pin: the allocator's own choice stands (profiles/dgauss_resources.txt).  Nothing spills.
+template <int P, bool STOCHASTIC>
+__global__ __launch_bounds__(256) void encode_gauss_mask_kernel(const float *__restrict__ x, uint64_t x_pitch,
+                                                                const int64_t *__restrict__ seg,
+                                                                const uint8_t *__restrict__ seeds,
+                                                                const int8_t *__restrict__ signs,
+                                                                const uint8_t *__restrict__ dither,
+                                                                const uint8_t *__restrict__ noise,
+                                                                const uint64_t *__restrict__ cdt, uint32_t T, uint64_t L,
+                                                                uint64_t Lw, uint32_t tiles, float clip, float scale,
+                                                                uint32_t bias, uint32_t *__restrict__ out,
+                                                                uint64_t out_pitch, uint32_t *__restrict__ clipped) {
+    static_assert(P == 1 || P == 2 || P == 4, "one, two or four fields per word");
+    constexpr int E = STOCHASTIC ? P : 1;
+    constexpr bool OWN = P > 1;  // packed words add into the wave's own region
+    __shared__ u32x4 lds[4 * 256];  // one 4 KiB region per wave
+    extern __shared__ __attribute__((aligned(8))) uint64_t tab[];  // the table: T entries
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x - i * tiles;
+    const uint32_t ctr = tile * 64u + (uint32_t)lane;
+    const uint64_t par0 = (uint64_t)P * ((uint64_t)tile * 1024u + 16u * (uint64_t)lane);  // the lane's first parameter
+    const int64_t k_lo = seg[i];
+    const int64_t n_noise = P, n_units = n_noise + (seg[i + 1] - k_lo);
+
+    u32x4 *R = lds + w * 256 + 4 * lane;  // the lane's 16 words of its wave's partial
+    if constexpr (OWN) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) R[j] = u32x4{0u, 0u, 0u, 0u};
+    }
+    for (uint32_t t = threadIdx.x; t < T; t += 256u) tab[t] = cdt[t];
+    __syncthreads();
+    uint32_t m[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m[j] = 0u;
+    uint32_t nneg = 0;
+    const int rank = 3 - w;
+#pragma unroll 1
+    for (int64_t u = first_unit<E>(rank); u < n_units; u = next_unit<E>(u)) {  // two bodies in the loop: kept rolled
+        if (u < n_noise) {
+            // 2 ceil(L / 16) <= 2^32 (the call's length rule): both counters of a parameter block the row has stay
+            // below 2^32; a block past L may wrap, and is predicated away or never stored
+            gauss_block_add<P>(noise + 32 * (size_t)i, (uint32_t)P * ctr + (uint32_t)u, tab, T, par0 + 16u * (uint32_t)u, L,
+                               m, R + (4 / P) * (uint32_t)u);
+            continue;
+        }
+        const int64_t k = k_lo + (u - n_noise);
+        const bool neg = signs[k] < 0;
+        nneg += neg ? 1u : 0u;
+        chacha_raw_add(seeds + 32 * (size_t)k, ctr, neg ? ~kAbcd : kAbcd, m);  // -(ks ^ C) = (ks ^ ~C) + 1
+    }
+    if (rank == 0) {
+        const float *xr = x + (uint64_t)i * x_pitch;
+        const uint32_t half = T >> 1;  // tau
+        uint32_t nclip = 0;
+#pragma unroll 1
+        for (int d = 0; d < P; ++d) {
+            constexpr int W = 32 / P;
+            uint32_t r[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) r[j] = 0u;
+            // parameters below 2^36 (the call's range rule): the dither block counter stays below 2^32
+            if constexpr (STOCHASTIC) chacha_raw_add(dither + 32 * (size_t)i, (uint32_t)P * ctr + (uint32_t)d, kAbcd, r);
+            uint32_t e[16 / P];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint64_t s = par0 + 16u * (uint32_t)d + 4u * j;
+                // a quad that straddles L stays inside the row (x_pitch >= round_up(L, 4))
+                const float4 v = s < L ? *reinterpret_cast<const float4 *>(xr + s) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const uint32_t u0 = codec_field<STOCHASTIC>(s + 0 < L, v.x, clip, scale, r[4 * j + 0], bias, nclip);
+                const uint32_t u1 = codec_field<STOCHASTIC>(s + 1 < L, v.y, clip, scale, r[4 * j + 1], bias, nclip);
+                const uint32_t u2 = codec_field<STOCHASTIC>(s + 2 < L, v.z, clip, scale, r[4 * j + 2], bias, nclip);
+                const uint32_t u3 = codec_field<STOCHASTIC>(s + 3 < L, v.w, clip, scale, r[4 * j + 3], bias, nclip);
+                if constexpr (P == 1) {  // bias is 0: the words themselves, less tau (words past L are not stored)
+                    m[4 * j + 0] += u0 - half;
+                    m[4 * j + 1] += u1 - half;
+                    m[4 * j + 2] += u2 - half;
+                    m[4 * j + 3] += u3 - half;
+                } else if constexpr (P == 4) {
+                    e[j] = u0 | (u1 << W) | (u2 << 2 * W) | (u3 << 3 * W);
+                } else {
+                    e[2 * j + 0] = u0 | (u1 << W);
+                    e[2 * j + 1] = u2 | (u3 << W);
+                }
+            }
+            if constexpr (OWN) {
+                R[(4 / P) * d] += u32x4{e[0], e[1], e[2], e[3]};
+                if constexpr (P == 2) R[2 * d + 1] += u32x4{e[4], e[5], e[6], e[7]};
+            }
+        }
+        clipped_add(clipped, i, nclip, lane);
+    }
+    tile_meet_store<OWN, 4>(lds, R, m, nneg, out + (uint64_t)i * out_pitch, tile, Lw);
 }
 
 // One field of a summed word as the mean of `count` contributors; cb = count B.
@@ -1638,6 +1802,29 @@ hipError_t launch_encode_mask(const float *d_x, uint64_t x_pitch, int N, const i
     hipLaunchKernelGGL(kernels[c.pack / 2][d_dither != nullptr][c.noise_bits != 0], dim3((unsigned)groups), dim3(256), 0,
                        stream, d_x, x_pitch, d_seg, d_seeds, d_signs, d_dither, d_noise, draws, last_mask, half, L, Lw, tiles,
                        c.clip, scale, c.pack == 1 ? 0u : c.bias, d_out, out_pitch, d_clipped);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_gauss_mask(const float *d_x, uint64_t x_pitch, int N, const int64_t *d_seg, const uint8_t *d_seeds,
+                                    const int8_t *d_signs, const uint8_t *d_dither, const uint8_t *d_noise,
+                                    const uint64_t *d_cdt, int tail, uint64_t L, const CodecParams &c, uint32_t *d_out,
+                                    uint64_t out_pitch, uint32_t *d_clipped, hipStream_t stream) {
+    if (c.pack != 1 && c.pack != 2 && c.pack != 4) return hipErrorInvalidValue;
+    if (tail < 1 || tail > 512 || !d_noise || !d_cdt || ((uintptr_t)d_cdt & 7)) return hipErrorInvalidValue;
+    const uint64_t Lw = (L + (uint64_t)c.pack - 1) / (uint64_t)c.pack;
+    const uint64_t groups = encode_mask_groups(N, Lw);
+    if (groups == 0) return hipSuccess;
+    if (groups > 0x7fffffffull || c.frac_bits < 0 || c.frac_bits > 30) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)((Lw + 1023) / 1024), T = 2u * (uint32_t)tail;
+    const float scale = (float)(1u << c.frac_bits);
+    // [pack / 2][stochastic], as launch_encode_mask's
+    static constexpr decltype(&encode_gauss_mask_kernel<1, false>) kernels[3][2] = {
+        {encode_gauss_mask_kernel<1, false>, encode_gauss_mask_kernel<1, true>},
+        {encode_gauss_mask_kernel<2, false>, encode_gauss_mask_kernel<2, true>},
+        {encode_gauss_mask_kernel<4, false>, encode_gauss_mask_kernel<4, true>}};
+    hipLaunchKernelGGL(kernels[c.pack / 2][d_dither != nullptr], dim3((unsigned)groups), dim3(256), 8u * T, stream, d_x,
+                       x_pitch, d_seg, d_seeds, d_signs, d_dither, d_noise, d_cdt, T, L, Lw, tiles, c.clip, scale,
+                       c.pack == 1 ? 0u : c.bias, d_out, out_pitch, d_clipped);
     return hipGetLastError();
 }
 

@@ -291,6 +291,12 @@ int check_codec(flm_ctx *ctx, flm::CodecParams &c, bool unpacked_ok, int64_t n, 
                                            &c.bias, bias_n);
     return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
 }
+// the same for the table mode of the noise (tail, and the stream of two blocks per parameter block)
+int check_codec_gauss(flm_ctx *ctx, flm::CodecParams &c, int tail, int64_t n, uint64_t L_params) {
+    bool range = false;
+    const char *why = flm::rt::codec_gauss_error(c.frac_bits, c.clip, c.pack, tail, n, L_params, &range, &c.bias);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
 int check_aggregate_args(flm_ctx *ctx, const uint32_t *d_rows, size_t row_pitch, int N, int K, size_t L, size_t mask_lo,
                          size_t mask_hi, uint64_t prg_slot0, const uint32_t *d_out) {
     bool range = false;
@@ -1056,7 +1062,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip + round_bound"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip + round_bound + dp_gauss"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1249,12 +1255,23 @@ int flm_client_mask_dev(flm_ctx *ctx, const uint32_t *d_x, size_t pitch, int N, 
 
 namespace {
 
+// The table mode of the noise (flm_client_encode_gauss_mask[_dev]): the tail and the table, on the host or the device
+// as the call's other arrays are.  The calls without it pass none.
+struct GaussNoise {
+    int tail;
+    const uint64_t *cdt;
+};
+
 int encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg, const uint8_t *d_seeds,
                     const int8_t *signs, size_t L, flm::CodecParams c, bool unpacked_ok, const uint8_t *d_dither,
-                    const uint8_t *d_noise, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped, void *stream) {
+                    const uint8_t *d_noise, const GaussNoise *gauss, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
+                    void *stream) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = check_codec(ctx, c, unpacked_ok, 1, L)) return rc;
+    if (int rc = gauss ? check_codec_gauss(ctx, c, gauss->tail, 1, L) : check_codec(ctx, c, unpacked_ok, 1, L)) return rc;
     if (c.noise_bits && !d_noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
+    if (gauss && (!d_noise || !gauss->cdt)) return fail(ctx, FLM_EINVAL, "the table mode needs the clients' noise seeds and the table");
+    if (gauss)
+        if (int rc = refuse(ctx, flm::rt::cdt_align_error(gauss->cdt))) return rc;
     if (N <= 0 || L == 0) return 0;
     const size_t Lw = flm::rt::packed_words(L, c.pack);
     int64_t K = 0;
@@ -1269,36 +1286,50 @@ int encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const
     Staged up;  // seg and signs in one host-to-device copy, as flm_client_mask_dev's
     if (int rc = stage_put(ctx, {{seg, (size_t)(N + 1) * sizeof(int64_t), 0}, {signs, (size_t)K, 0}}, s, &up)) return rc;
     hipError_t e = d_clipped ? hipMemsetAsync(d_clipped, 0, (size_t)N * sizeof(uint32_t), s) : hipSuccess;
+    const int64_t *d_seg = reinterpret_cast<const int64_t *>(up.dev[0]);
+    const int8_t *d_signs = reinterpret_cast<const int8_t *>(up.dev[1]);
     if (e == hipSuccess)
-        e = flm::launch_encode_mask(d_x, x_pitch, N, reinterpret_cast<const int64_t *>(up.dev[0]), d_seeds,
-                                    reinterpret_cast<const int8_t *>(up.dev[1]), d_dither, d_noise, L, c, d_out, out_pitch,
-                                    d_clipped, s);
+        e = gauss ? flm::launch_encode_gauss_mask(d_x, x_pitch, N, d_seg, d_seeds, d_signs, d_dither, d_noise, gauss->cdt,
+                                                  gauss->tail, L, c, d_out, out_pitch, d_clipped, s)
+                  : flm::launch_encode_mask(d_x, x_pitch, N, d_seg, d_seeds, d_signs, d_dither, d_noise, L, c, d_out,
+                                            out_pitch, d_clipped, s);
     if (int rc = stage_done(ctx, up, s, 0)) return rc;
     FLM_HIP(ctx, e);
     return 0;
 }
 
 // the codec before N < 0 (the plain and packed entry points refuse a negative N first, themselves); the noise
-// seeds are wanted, and travel, only when noise_bits > 0
+// seeds are wanted, and travel, only when noise_bits > 0; in the table mode they and the table always do, the table
+// checked here, where it can be seen
 int encode_mask_host(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds, const int8_t *signs,
                      size_t L, flm::CodecParams c, bool unpacked_ok, const uint8_t *dither, const uint8_t *noise,
-                     uint32_t *out, uint32_t *clipped) {
+                     const GaussNoise *gauss, uint32_t *out, uint32_t *clipped) {
     if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
-    if (int rc = check_codec(ctx, c, unpacked_ok, 1, L)) return rc;
+    if (int rc = gauss ? check_codec_gauss(ctx, c, gauss->tail, 1, L) : check_codec(ctx, c, unpacked_ok, 1, L)) return rc;
     if (N < 0) return fail(ctx, FLM_EINVAL, "negative N");
     if (c.noise_bits && !noise) return fail(ctx, FLM_EINVAL, "noise_bits > 0 needs the clients' noise seeds");
+    if (gauss && !noise) return fail(ctx, FLM_EINVAL, "the table mode needs the clients' noise seeds and the table");
+    if (gauss)
+        if (int rc = refuse(ctx, flm::rt::dgauss_table_error(gauss->cdt, gauss->tail))) return rc;
     if (N == 0 || L == 0) return 0;
     int64_t K = 0;
     if (int rc = refuse(ctx, flm::rt::client_args_error(x && out, N, seg, seeds, signs, &K))) return rc;
     if (int rc = check_range(ctx, 0, L)) return rc;
     FLM_ON_DEVICE(ctx);
     HostCopies hc(ctx, ctx->stream);
-    hc.declare(flm::rt::client_encode_mask_args(N, K, L, flm::rt::packed_words(L, c.pack), dither, c.noise_bits, clipped),
-               {x, seeds, dither, noise, out, clipped});
+    const size_t Lw = flm::rt::packed_words(L, c.pack);
+    if (gauss)
+        hc.declare(flm::rt::client_encode_gauss_mask_args(N, K, L, Lw, dither, 2 * (size_t)gauss->tail, clipped),
+                   {x, seeds, dither, noise, gauss->cdt, out, clipped});
+    else
+        hc.declare(flm::rt::client_encode_mask_args(N, K, L, Lw, dither, c.noise_bits, clipped),
+                   {x, seeds, dither, noise, out, clipped});
     if (int rc = hc.begin()) return rc;
+    const int o = gauss ? 5 : 4;  // out's place in the list: behind the table where there is one
+    const GaussNoise d_gauss = {gauss ? gauss->tail : 0, gauss ? hc.dev<uint64_t>(4) : nullptr};
     if (int rc = encode_mask_dev(ctx, hc.dev<float>(0), hc.pitch(0) / 4, N, seg, hc.dev<uint8_t>(1), signs, L, c, unpacked_ok,
-                                 hc.dev<uint8_t>(2), hc.dev<uint8_t>(3), hc.dev<uint32_t>(4), hc.pitch(4) / 4,
-                                 hc.dev<uint32_t>(5), ctx->stream))
+                                 hc.dev<uint8_t>(2), hc.dev<uint8_t>(3), gauss ? &d_gauss : nullptr, hc.dev<uint32_t>(o),
+                                 hc.pitch(o) / 4, hc.dev<uint32_t>(o + 1), ctx->stream))
         return rc;
     return hc.finish();
 }
@@ -1359,40 +1390,61 @@ int flm_client_encode_mask(flm_ctx *ctx, const float *x, int N, const int64_t *s
                            const int8_t *signs, size_t L, int frac_bits, float clip, const uint8_t *dither,
                            uint32_t *out, uint32_t *clipped) {
     if (ctx && N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, 1, 0, 0}, true, dither, nullptr, out, clipped);
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, 1, 0, 0}, true, dither, nullptr, nullptr, out, clipped);
 }
 int flm_client_encode_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
                                const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
                                const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
                                void *stream) {
     return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, 1, 0, 0}, true, d_dither, nullptr,
-                           d_out, out_pitch, d_clipped, stream);
+                           nullptr, d_out, out_pitch, d_clipped, stream);
 }
 int flm_client_encode_pack_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
                                 const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
                                 uint32_t *out, uint32_t *clipped) {
     if (ctx && N < 0) return fail(ctx, FLM_EINVAL, "negative N");
-    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, 0, 0}, false, dither, nullptr, out, clipped);
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, 0, 0}, false, dither, nullptr, nullptr, out, clipped);
 }
 int flm_client_encode_pack_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
                                     const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
                                     int pack, const uint8_t *d_dither, uint32_t *d_out, size_t out_pitch,
                                     uint32_t *d_clipped, void *stream) {
     return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, pack, 0, 0}, false, d_dither, nullptr,
-                           d_out, out_pitch, d_clipped, stream);
+                           nullptr, d_out, out_pitch, d_clipped, stream);
 }
 int flm_client_encode_noise_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
                                  const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
                                  int noise_bits, const uint8_t *noise, uint32_t *out, uint32_t *clipped) {
-    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, noise_bits, 0}, true, dither, noise, out,
-                            clipped);
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, noise_bits, 0}, true, dither, noise, nullptr,
+                            out, clipped);
 }
 int flm_client_encode_noise_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
                                      const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
                                      int pack, const uint8_t *d_dither, int noise_bits, const uint8_t *d_noise,
                                      uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped, void *stream) {
     return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, pack, noise_bits, 0}, true, d_dither,
-                           d_noise, d_out, out_pitch, d_clipped, stream);
+                           d_noise, nullptr, d_out, out_pitch, d_clipped, stream);
+}
+
+int flm_codec_check_gauss(int frac_bits, float clip, int pack, int tail, int64_t n_clients, uint64_t L_params) {
+    flm::CodecParams c{frac_bits, clip, pack, 0, 0};
+    return check_codec_gauss(nullptr, c, tail, n_clients, L_params);
+}
+int flm_dgauss_check_table(const uint64_t *cdt, int tail) { return refuse(nullptr, flm::rt::dgauss_table_error(cdt, tail)); }
+int flm_client_encode_gauss_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                 const int8_t *signs, size_t L, int frac_bits, float clip, int pack, const uint8_t *dither,
+                                 int tail, const uint64_t *cdt, const uint8_t *noise, uint32_t *out, uint32_t *clipped) {
+    const GaussNoise g = {tail, cdt};
+    return encode_mask_host(ctx, x, N, seg, seeds, signs, L, {frac_bits, clip, pack, 0, 0}, true, dither, noise, &g, out, clipped);
+}
+int flm_client_encode_gauss_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                                     const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits, float clip,
+                                     int pack, const uint8_t *d_dither, int tail, const uint64_t *d_cdt,
+                                     const uint8_t *d_noise, uint32_t *d_out, size_t out_pitch, uint32_t *d_clipped,
+                                     void *stream) {
+    const GaussNoise g = {tail, d_cdt};
+    return encode_mask_dev(ctx, d_x, x_pitch, N, seg, d_seeds, signs, L, {frac_bits, clip, pack, 0, 0}, true, d_dither, d_noise,
+                           &g, d_out, out_pitch, d_clipped, stream);
 }
 
 int flm_decode_sum(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, int64_t count, float *out) {

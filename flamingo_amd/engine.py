@@ -367,6 +367,28 @@ class MaskEngine:
         return self._encode_mask("flm_client_encode_noise_mask", lambda d, z: (pack, d, int(noise_bits), z), seg, seeds,
                                  signs, L, x, frac_bits, clip, pack, dither, noise, return_clipped)
 
+    def codec_check_gauss(self, frac_bits: int, clip: float, tail: int, n_clients: int = 1, pack: int = 1, L: int = 0):
+        """codec_check with every client's table-sampled noise share in [-tail, tail] (flm_codec_check_gauss: tail in
+        1..512, ceil(clip * 2^frac_bits) + tail in the bound's place, and for L > 0 parameters the noise stream's
+        length rule 2 * ceil(L / 16) <= 2^32); no device call."""
+        rc = self.lib.flm_codec_check_gauss(int(frac_bits), float(clip), int(pack), int(tail), int(n_clients), int(L))
+        self._check(rc, "flm_codec_check_gauss")
+
+    def client_encode_gauss_mask(self, seg, seeds, signs, L: int, x: np.ndarray, frac_bits: int, clip: float, table,
+                                 noise, pack: int = 1, dither=None, return_clipped: bool = False):
+        """client_encode_noise_mask with the noise share sampled from a cumulative table (flamingo_amd.dgauss.table):
+        table 2 * tail uint64 entries, non-decreasing; Z = #{j : table[j] <= u} - tail on each parameter's quantised
+        value, u the parameter's 64-bit draw of PRG(noise_i).  noise: N 32-byte seeds, secret and fresh per
+        iteration.  Rows decode as rows of client_encode_noise_mask with noise_bits = 2 * tail.
+        flm_client_encode_gauss_mask."""
+        pack = int(pack)
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        if table.ndim != 1 or table.shape[0] % 2:
+            raise RuntimeError("table must hold 2 * tail uint64 entries")
+        tail = table.shape[0] // 2
+        return self._encode_mask("flm_client_encode_gauss_mask", lambda d, z: (pack, d, tail, p_u64(table), z), seg, seeds,
+                                 signs, L, x, frac_bits, clip, pack, dither, noise, return_clipped)
+
     def decode_unpack(self, total: np.ndarray, L: int, frac_bits: int, clip: float, pack: int, count: int = 1,
                       noise_bits: int = 0) -> np.ndarray:
         """The L float32 means of `count` contributors held in the ceil(L / pack) summed packed words `total`:
@@ -685,6 +707,21 @@ class MaskEngine:
         contiguous (N, 32) uint8 tensor of the clients' noise seeds.  Enqueued on `stream`; nothing is synchronised."""
         pack = int(pack)
         return self._encode_mask_dev("flm_client_encode_noise_mask_dev", lambda d, z: (pack, d, int(noise_bits), z), seg,
+                                     seeds_dev, signs, out, L, x, frac_bits, clip, pack, dither_dev, noise_dev, clipped,
+                                     stream)
+
+    def client_encode_gauss_mask_dev(self, seg, seeds_dev, signs, out, L: int, x, frac_bits: int, clip: float, table_dev,
+                                     noise_dev, pack: int = 1, dither_dev=None, clipped=None, stream=None):
+        """Device client_encode_gauss_mask: as client_encode_noise_mask_dev, with table_dev a one-dimensional 64-bit
+        tensor of 2 * tail entries (8-byte aligned; its contents are not looked at: whatever they are, every field
+        stays inside its headroom).  Enqueued on `stream`; nothing is synchronised."""
+        pack = int(pack)
+        if table_dev is None or table_dev.dim() != 1 or table_dev.element_size() != 8 or table_dev.shape[0] % 2 \
+                or table_dev.stride(0) != 1:
+            raise RuntimeError("table_dev must be a contiguous tensor of 2 * tail 64-bit entries")
+        tail = table_dev.shape[0] // 2
+        return self._encode_mask_dev("flm_client_encode_gauss_mask_dev",
+                                     lambda d, z: (pack, d, tail, ctypes.c_void_p(table_dev.data_ptr()), z), seg,
                                      seeds_dev, signs, out, L, x, frac_bits, clip, pack, dither_dev, noise_dev, clipped,
                                      stream)
 

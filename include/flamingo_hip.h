@@ -297,6 +297,60 @@ int flm_decode_unpack_noise(flm_ctx *ctx, const uint32_t *sum, size_t L, int fra
 int flm_decode_unpack_noise_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
                                 int noise_bits, int64_t count, float *d_out, void *stream);
 
+/* ------------------------------ discrete Gaussian noise shares, sampled from a cumulative table */
+
+/* The noise share of the distributed discrete Gaussian mechanism (Kairouz, Liu, Steinke, ICML 2021, Algorithm 1)
+ * in the place of the binomial one above (SA_ClientAgent.py:300-324; PPFL_ClientAgent.py:219-221, 274-285): the
+ * client's share Z is sampled inside the encode-mask kernel from a cumulative table the caller built.  A fixed
+ * number of table probes per parameter: nothing loops on data, and the result is a function of the seed.  Normative:
+ *   tail tau: an integer, 1 <= tau <= 512; Z lies in [-tau, tau].  tau = 0 is not "off": it is refused
+ *     (FLM_EINVAL); the calls without noise exist.
+ *   cdt[0 .. T - 1]: uint64, non-decreasing, T = 2 tau (at most 8 KiB).  cdt[j] stands for 2^64 P(Z <= j - tau):
+ *     a draw below it gives a sample <= j - tau.  The sample is defined by the count alone (below); with it
+ *     P(Z = -tau) = cdt[0] / 2^64, P(Z = tau) = 1 - cdt[T - 1] / 2^64, and cdt[0] = 0 means "-tau never occurs".
+ *     For a discrete Gaussian of parameter sigma truncated to |Z| <= tau, cdt[j] = floor(2^64 sum_{k = -tau}^{j -
+ *     tau} w(k) / sum_{k = -tau}^{tau} w(k)), w(k) = exp(-k^2 / (2 sigma^2)); tau = 1 with cdt = {2^63, 2^63} gives
+ *     -1 and +1 with probability 1/2 each and never 0.  The library takes the table and does not build it
+ *     (flamingo_amd/dgauss.py does).
+ *   noise: one 32-byte seed per client, as above.  With beta = l / 16, the draw of parameter l is
+ *     u(l) = PRG(noise_i)[16 * (2 beta) + l % 16] * 2^32 + PRG(noise_i)[16 * (2 beta + 1) + l % 16]: ChaCha
+ *     block 2 beta holds the high words of parameter block beta, block 2 beta + 1 the low words (the binomial
+ *     stream's layout at m = 2).  Indexed by parameter in every pack mode.
+ *   z(l) = #{ j < T : cdt[j] <= u(l) } - tau, the compare a 64-bit unsigned one.
+ *   q' = q + z, q the codec's encode in either rounding (what flm_round_select counts).  pack = 1: the ring word is
+ *     uint32(q').  pack = 2, 4: the field is q + B + (z + tau), bias B_n = B + tau.  Parameters >= L get no noise:
+ *     their fields hold 0 and they are never stored.  The clipped count is that of the call without noise.
+ *   decode: rows of these calls decode as rows of flm_client_encode_noise_mask with noise_bits = 2 tau do:
+ *     pack = 1 with flm_decode_sum[_dev], packed with flm_decode_unpack_noise[_dev] or
+ *     flm_store_unmask_unpack_noise_f32 at noise_bits = 2 * tail.  There are no decode calls of its own.
+ * Headroom, worst case, in exact integers, FLM_ERANGE outside it: the rule above with B_n = B + tau: pack = 1:
+ * n * B_n <= 2^31 - 1; packed: n * 2 * B_n <= 2^W - 1.  Length: 2 * ceil(L / 16) <= 2^32, else FLM_ERANGE.
+ * The host form refuses a table that decreases anywhere (FLM_EINVAL).  The device form cannot see its table:
+ * whatever the table holds, every probe reads inside it and the count stays in [0, T], so no field leaves its
+ * headroom.  Privacy accounting (sigma, the mass beyond tau, the sensitivity flm_round_bound gives) is the caller's.
+ *
+ * flm_codec_check_gauss: FLM_EINVAL for tail outside 1..512 and the refusals of flm_codec_check_noise's codec
+ * (pack 1, 2 or 4); FLM_ERANGE outside the headroom and, when L_params > 0, the length rule.  No context. */
+int flm_codec_check_gauss(int frac_bits, float clip, int pack, int tail, int64_t n_clients, uint64_t L_params);
+/* FLM_EINVAL for cdt NULL, tail outside 1..512 or cdt[j] < cdt[j - 1] for some 0 < j < 2 tail
+ * (PPFL_ClientAgent.py:219-221, 274-285: the noise a client adds).  No context, no device. */
+int flm_dgauss_check_table(const uint64_t *cdt, int tail);
+/* flm_client_encode_noise_mask with the table in the place of noise_bits (SA_ClientAgent.py:300-324;
+ * PPFL_ClientAgent.py:219-221, 274-285): cdt 2 * tail entries, checked as flm_dgauss_check_table does; noise
+ * N x 32 bytes; either NULL is FLM_EINVAL.  The rule above with n = 1 and L, refused before anything is launched. */
+int flm_client_encode_gauss_mask(flm_ctx *ctx, const float *x, int N, const int64_t *seg, const uint8_t *seeds,
+                                 const int8_t *signs, size_t L, int frac_bits, float clip, int pack,
+                                 const uint8_t *dither, int tail, const uint64_t *cdt, const uint8_t *noise,
+                                 uint32_t *out, uint32_t *clipped);
+/* The same on device buffers (SA_ClientAgent.py:300-324; PPFL_ClientAgent.py:219-221, 274-285), as
+ * flm_client_encode_noise_mask_dev; d_cdt: 2 * tail uint64 on the device, 8-byte aligned ("cdt must be 8-byte
+ * aligned", FLM_EINVAL, otherwise), not looked at by the host. */
+int flm_client_encode_gauss_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pitch, int N, const int64_t *seg,
+                                     const uint8_t *d_seeds, const int8_t *signs, size_t L, int frac_bits,
+                                     float clip, int pack, const uint8_t *d_dither, int tail, const uint64_t *d_cdt,
+                                     const uint8_t *d_noise, uint32_t *d_out, size_t out_pitch,
+                                     uint32_t *d_clipped, void *stream);
+
 /* ------------------------------ randomised block Hadamard rotation of float updates */
 
 /* A float -> float step in front of the codec's encode and behind its decode, the flattening the

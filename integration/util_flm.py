@@ -67,6 +67,9 @@ for _name, _res, _args in (
         ("flm_decode_unpack_noise", _int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _f32p]),
         ("flm_store_unmask_unpack_noise_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
                                                      ctypes.c_int64, _f32p]),
+        ("flm_codec_check_gauss", _int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64, ctypes.c_uint64]),
+        ("flm_client_encode_gauss_mask", _int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _int, _u8p,
+                                                _int, ctypes.POINTER(ctypes.c_uint64), _u8p, _u32p, _u32p]),
         ("flm_rotate_check", _int, [ctypes.c_uint64, _int, ctypes.POINTER(ctypes.c_uint64)]),
         ("flm_rotate", _int, [_vp, _f32p, _int, _sz, _int, _u8p, _int, _f32p, _u32p]),
         ("flm_l2_clip_check", _int, [ctypes.c_uint64, ctypes.c_float, _int, ctypes.POINTER(ctypes.c_uint64)]),
@@ -462,6 +465,29 @@ def client_encode_noise_mask(seeds, signs, L, x, frac_bits, clip, pack=1, dither
         raise RuntimeError("pack must be 1, 2 or 4")
     return _encode_mask(_lib.flm_client_encode_noise_mask, lambda d, z: (int(pack), d, int(noise_bits), z), seeds, signs, L,
                         x, frac_bits, clip, pack, dither, noise)
+
+
+def codec_check_gauss(frac_bits, clip, pack, tail, n_clients, L=0):
+    """codec_check_noise for table-sampled noise shares in [-tail, tail] (tail in 1..512): ceil(clip 2^frac_bits) +
+    tail in the bound's place; with L > 0 also 2 ceil(L / 16) <= 2^32.  The server's check at set-up, with the real n."""
+    _check(_lib.flm_codec_check_gauss(int(frac_bits), float(clip), int(pack), int(tail), int(n_clients), int(L)))
+
+
+def client_encode_gauss_mask(seeds, signs, L, x, frac_bits, clip, table, noise, pack=1, dither=None):
+    """client_encode_noise_mask with the client's noise share sampled from a cumulative table inside the masking kernel
+    ("replace it with model weights", SA_ClientAgent.py:300-324; the local noise of
+    agent/examples/crypto/PPFL_ClientAgent.py:219-221, 274-285): table 2 tail non-decreasing uint64 thresholds
+    (flamingo_amd.dgauss.table builds a discrete Gaussian's), every parameter's quantised value gets (entries <= its
+    64-bit draw of PRG(noise)) - tail.  noise: 32 secret bytes, fresh per iteration.  The rows decode with decode_sum
+    (pack 1) or decode_unpack at noise_bits = 2 tail.  Returns (uint32 words, clipped elements)."""
+    if pack not in (1, 2, 4):
+        raise RuntimeError("pack must be 1, 2 or 4")
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    if table.ndim != 1 or table.shape[0] % 2:
+        raise RuntimeError("table must hold 2 tail uint64 entries")
+    cdt = table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    return _encode_mask(_lib.flm_client_encode_gauss_mask, lambda d, z: (int(pack), d, table.shape[0] // 2, cdt, z), seeds,
+                        signs, L, x, frac_bits, clip, pack, dither, noise)
 
 
 def l2_clip_check(L, clip_norm, N=1):

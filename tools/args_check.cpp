@@ -137,6 +137,9 @@ static void check_round_lists() {
                     }
                     for (int pack : {1, 2, 4})
                         through_bounce(client_encode_mask_args(N, K, L, packed_words(L, pack), opt & 1, true, opt & 2));
+                    for (int pack : {1, 2, 4})   // flm_client_encode_gauss_mask: the table after the noise seeds
+                        for (size_t T : {size_t(2), size_t(74), size_t(1024)})
+                            through_bounce(client_encode_gauss_mask_args(N, K, L, packed_words(L, pack), opt & 1, T, opt & 2));
                     if (opt < 2) through_bounce(client_mask_args(N, K, L, opt & 1));
                     if (opt < 2) through_bounce(aggregate_unmask_args(K, L, opt & 1));
                     if (opt) continue;
@@ -279,6 +282,27 @@ static void check_round_rules() {
     CHECK(!noise_rule(4, 1.0f, 1, 0, 1, ~0ull, &range, &B, &Bn));                    // no noise: no length rule
     const ArgList ne = client_encode_mask_args(3, 7, 5, 2, false, true, true);
     CHECK(ne.n == 6 && ne.a[3].present && ne.a[3].width == 96 && !ne.a[2].present && ne.a[4].is_out && ne.a[4].width == 8);
+    // the table mode: tail 1..512, the codec's own refusals, B_n = B + tail (the binomial edges at tail = b / 2), the
+    // stream of two blocks per parameter block, the table's order and the device pointer's alignment
+    for (int t : {0, -1, 513}) CHECK(!std::strcmp(codec_gauss_error(4, 1.0f, 2, t, 1, 0, &range), "tail must be in 1..512") && !range);
+    for (int pack : {0, 3, 8}) CHECK(codec_gauss_error(4, 1.0f, pack, 1, 1, 0, &range) && !range);
+    CHECK(codec_gauss_error(31, 1.0f, 2, 1, 1, 0, &range) && !range && codec_gauss_error(4, 0.0f, 2, 1, 1, 0, &range) && !range);
+    CHECK(!codec_gauss_error(4, 1.0f, 2, 15, 1057, 0, &range, &B, &Bn) && B == 16 && Bn == 31 && !range);
+    CHECK(codec_gauss_error(4, 1.0f, 2, 15, 1058, 0, &range) && range);
+    CHECK(!codec_gauss_error(2, 1.0f, 4, 1, 25, 0, &range, &B, &Bn) && Bn == 5 && codec_gauss_error(2, 1.0f, 4, 1, 26, 0, &range) && range);
+    CHECK(codec_gauss_error(7, 1.0f, 2, 1, 255, 0, &range) && range);
+    CHECK(!codec_gauss_error(16, 4.0f, 1, 512, 8176, 0, &range, &B, &Bn) && Bn == 262656);
+    CHECK(codec_gauss_error(16, 4.0f, 1, 512, 8177, 0, &range) && range);
+    CHECK(!codec_gauss_error(4, 1.0f, 1, 1, 1, 1ull << 35, &range) && !codec_gauss_error(4, 1.0f, 1, 512, 1, 1ull << 35, &range));
+    CHECK(codec_gauss_error(4, 1.0f, 1, 1, 1, (1ull << 35) + 1, &range) && range);
+    const uint64_t up[4] = {0, 5, 5, ~0ull}, down[4] = {0, 5, 4, 9};
+    CHECK(!dgauss_table_error(up, 2) && !dgauss_table_error(up, 1) && !dgauss_table_error(down, 1));
+    CHECK(!std::strcmp(dgauss_table_error(down, 2), "the table must be non-decreasing"));
+    CHECK(dgauss_table_error(nullptr, 2) && dgauss_table_error(up, 0) && dgauss_table_error(up, 513));
+    CHECK(!cdt_align_error(buf + 8) && !cdt_align_error(nullptr) && !std::strcmp(cdt_align_error(buf + 4), "cdt must be 8-byte aligned"));
+    const ArgList ge = client_encode_gauss_mask_args(3, 7, 5, 2, false, 64, true);
+    CHECK(ge.n == 7 && ge.a[3].present && ge.a[3].width == 96 && ge.a[4].width == 512 && ge.a[4].slot == ec_dig && !ge.a[4].is_out &&
+          !ge.a[2].present && ge.a[5].is_out && ge.a[5].in_place && ge.a[5].width == 8 && ge.a[6].is_out && !names_slot_twice(ge));
     CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
     // the rotation's rule: h in 4..12, L > 0, L_rot = round_up(L, 2^h), L_rot / 32 sign words within 2^36 PRG slots
     uint64_t L_rot = 0;
