@@ -68,6 +68,11 @@ SIGNATURES = {
                                             _int, _u64p, _u8p, _u32p, _u32p]),
     "flm_client_encode_gauss_mask_dev": (_int, [_vp, _vp, _sz, _int, _i64p, _vp, _i8p, _sz, _int, ctypes.c_float, _int,
                                                 _vp, _int, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "flm_codec_check_modular": (_int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64]),
+    "flm_decode_unpack_mod": (_int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _int, _f32p,
+                                     _u32p]),
+    "flm_decode_unpack_mod_dev": (_int, [_vp, _vp, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _int, _vp, _vp,
+                                         _vp]),
     "flm_rotate_check": (_int, [_u64, _int, ctypes.POINTER(_u64)]),
     "flm_rotate_dev": (_int, [_vp, _vp, _sz, _int, _sz, _int, _vp, _int, _vp, _sz, _vp, _vp]),
     "flm_rotate": (_int, [_vp, _f32p, _int, _sz, _int, _u8p, _int, _f32p, _u32p]),
@@ -147,6 +152,8 @@ SIGNATURES = {
     "flm_store_unmask": (_int, [_vp, _u8p, _i8p, _int, _u32p]),
     "flm_store_unmask_f32": (_int, [_vp, _u8p, _i8p, _int, _int, ctypes.c_int64, _f32p]),
     "flm_store_unmask_unpack_f32": (_int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, ctypes.c_int64, _f32p]),
+    "flm_store_unmask_unpack_mod_f32": (_int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
+                                               ctypes.c_int64, _int, _f32p, _u32p]),
     "flm_store_unmask_unpack_noise_f32": (_int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
                                                  ctypes.c_int64, _f32p]),
     "flm_store_unmask_ms": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),

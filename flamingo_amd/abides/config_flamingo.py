@@ -104,6 +104,12 @@ def parse(argv):
     # ...)): Delta / 2^F is then the L2 sensitivity of the sum to one client after rounding, where C is the one before
     # it; needs --float_inputs F,CLIP,sr and --l2_clip; 0 turns it off; off by default
     ap.add_argument("--round_bound", default=None, metavar="TAIL[,ATTEMPTS]")
+    # the server decodes the packed sum modulo the field, following the carries from one field into the next
+    # (protocol.configure(modular=...)): it admits n by MaskEngine.codec_check_modular where the worst-case headroom rule
+    # refuses it, and reports how many centred sums reached ceil(FRACTION H), H = 2^(32/pack - 1), and the largest;
+    # FRACTION in (0, 1]; the library bounds no wrap probability: that and any (epsilon, delta) are the caller's business;
+    # needs --float_inputs with pack2 or pack4; the clients are unchanged; off by default
+    ap.add_argument("--modular", type=float, default=0.0, metavar="FRACTION")
     args, _ = ap.parse_known_args(argv)
     return ap, args
 
@@ -220,7 +226,7 @@ def _run(args):
                     dkg=True if args.dkg else None, codec=parse_float_inputs(args.float_inputs),
                     dp_noise=args.dp_noise, rotate=args.rotate, l2_clip=args.l2_clip,
                     round_bound=parse_round_bound(args.round_bound) or False,
-                    dp_gauss=parse_dp_gauss(args.dp_gauss) or False)
+                    dp_gauss=parse_dp_gauss(args.dp_gauss) or False, modular=args.modular or False)
     if param.dkg_on():
         committee_dkg(n, seed, args.latency, gpu_dkg=not args.host_dkg)
     offline = {int(x) for x in args.offline.split(",") if x.strip()}
@@ -308,9 +314,20 @@ def _run(args):
                     scaled += (f", rounded within Delta = sqrt({server.round_max_sumsq}) / 2^{param.codec()[0]} = "
                                f"{float(np.sqrt(server.round_max_sumsq)) / 2.0 ** param.codec()[0]:g}, {redrawn} clients "
                                f"needed a redraw")
+            modular = ""
+            if param.modular() is not None:    # the near-wrap evidence the server kept, and the margin in noise deviations
+                from .. import modular as M
+                near, most = server.near_wrap[it]
+                var = param.codec_noise_bits() / 4.0
+                if param.dp_gauss() is not None:
+                    from .. import dgauss
+                    var = float(dgauss.moments(param.dp_gauss_table())[1])
+                modular = (f", decoded modulo the field: H = {M.half_modulus(param.codec_pack())}, guard = {param.modular_guard()}, "
+                           f"{near} sums at or beyond the guard, max |Qh| = {most}, margin (H - max |Qh|) / sqrt(|U| Var) = "
+                           f"{M.margin_sigmas(param.codec_pack(), u, most, var):.3g} noise standard deviations (no probability)")
             print(f"    iteration {it}: float inputs {param.codec()}{packed}{rotated}: largest |final_mean - mean of the clients' floats| = "
                   f"{float(np.max(np.abs(diff))):.3e}{noised}, "
-                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped{nonfinite}{scaled}")
+                  f"{sum(agents[i].clipped for i in server.online_ids[it])} elements clipped{nonfinite}{scaled}{modular}")
     print()
     results["server"] = server
     results["clients"] = agents[:n]

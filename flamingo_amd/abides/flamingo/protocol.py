@@ -98,6 +98,13 @@ _l2_clip: float | None = None
 # to the ring.  It needs stochastic float inputs and the L2 clip.  Off (None) by default, so a run calls what it
 # always called, sends what it always sent and draws what it always drew.
 _round_bound: tuple | None = None      # (tail k, attempts)
+# Decode modulo the field (config_flamingo's --modular FRACTION): the server admits the cohort by
+# MaskEngine.codec_check_modular (one contributor's field fits; n times the bias is not bounded) where it applies the
+# worst-case headroom rule, decodes the packed sum with the carry-aware decode (MaskEngine.decode_unpack_mod,
+# VectorStore.unmask_unpack_mod_f32) and keeps the near-wrap evidence at the guard ceil(FRACTION H).  It needs packed float
+# inputs; the clients are unchanged.  Off (None) by default, so a run calls what it always called and refuses what it
+# always refused.
+_modular: float | None = None          # the guard's fraction of H, in (0, 1]
 ROUND_BATCHES = 8                       # batches of candidates a client draws before it gives up
 
 
@@ -106,7 +113,7 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
               signature_quorum: float | None = None, gpu_verify: bool | None = None,
               authenticate_shares: bool | None = None, dkg: bool | None = None, codec=None,
               dp_noise: int | None = None, rotate: int | None = None, l2_clip: float | None = None, round_bound=None,
-              dp_gauss=None):
+              dp_gauss=None, modular=None):
     """Reset the protocol parameters (between simulations / in tests).  codec: (frac_bits, clip, "nearest" or
     "stochastic") turns the float inputs on, (frac_bits, clip, rounding, pack) with pack 1, 2 or 4 also packs that
     many parameters into a ring word, False turns them off, None leaves them as they are.  dp_noise: the coin
@@ -120,14 +127,16 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
     it is; it needs stochastic float inputs and the L2 clip, and turning either off turns it off.  dp_gauss: (sigma,
     tail) or a bare sigma (tail = ceil(10 sigma)) turns the discrete Gaussian noise share on, tail in 1..512; 0 or False
     turns it off, None leaves it as it is; it needs the float inputs (turning those off turns it off) and is refused
-    together with dp_noise."""
+    together with dp_noise.  modular: a fraction in (0, 1] turns the decode modulo the field on, with the guard
+    ceil(fraction H) of its near-wrap count; 0 or False turns it off, None leaves it as it is; it needs a packed codec
+    (pack 2 or 4), and turning the float inputs off turns it off."""
     global root_seed, vector_len, committee_size, _h2c_table, _gpu_deal, _check_signatures, _signature_quorum, _gpu_verify
     global _authenticate_shares, _dkg, _dkg_result, _codec, _codec_pack, _dp_noise, _rotate, _l2_clip, _round_bound
-    global _dp_gauss, _dp_gauss_table
+    global _dp_gauss, _dp_gauss_table, _modular
     if codec is not None:
         if codec is False:
             _codec, _codec_pack, _dp_noise, _rotate, _l2_clip, _round_bound = None, 1, 0, 0, None, None
-            _dp_gauss, _dp_gauss_table = None, None
+            _dp_gauss, _dp_gauss_table, _modular = None, None, None
         else:
             f, c, mode = codec[:3]
             pack = int(codec[3]) if len(codec) == 4 else 1
@@ -198,6 +207,19 @@ def configure(root: bytes | None = None, L: int | None = None, committee: int | 
             _round_bound = (tail, int(attempts))
     if _round_bound is not None and (_codec is None or _codec[2] != "stochastic" or _l2_clip is None):
         _round_bound = None                   # what it stands on was turned off
+    if modular is not None:
+        import math
+        if modular is False or float(modular) == 0.0:
+            _modular = None
+        else:
+            fr = float(modular)
+            if not (math.isfinite(fr) and 0.0 < fr <= 1.0):
+                raise ValueError("modular must be a fraction in (0, 1] (0 turns it off)")
+            if _codec is None or _codec_pack not in (2, 4):
+                raise ValueError("modular needs a packed codec (codec=(f, clip, rounding, 2 or 4))")
+            _modular = fr
+    if _modular is not None and (_codec is None or _codec_pack not in (2, 4)):
+        raise ValueError("modular needs a packed codec (codec=(f, clip, rounding, 2 or 4))")
     if dkg is not None:
         _dkg = bool(dkg)
     _dkg_result = None
@@ -392,6 +414,17 @@ def decode_noise_bits() -> int:
     """What the packed decode and the headroom rule take for noise_bits: the binomial share's coins, or 2 tail of the
     discrete Gaussian one (the same bias B + tail); 0 without noise."""
     return 2 * _dp_gauss[1] if dp_gauss() is not None else codec_noise_bits()
+
+
+def modular() -> float | None:
+    """The guard's fraction of H of the decode modulo the field, or None when it is off (or the float inputs are)."""
+    return _modular if _codec is not None else None
+
+
+def modular_guard() -> int:
+    """The integer guard of the decode modulo the field: flamingo_amd.modular.guard(pack, fraction)."""
+    from ...modular import guard
+    return guard(_codec_pack, _modular)
 
 
 def rotate_bits() -> int:

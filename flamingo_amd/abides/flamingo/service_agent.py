@@ -80,6 +80,7 @@ class SA_ServiceAgent(Agent):
         self.final_mean = None       # float inputs: final_sum decoded as the mean over the online clients
         self.means = {}              # float inputs: iteration -> final_mean
         self.online_ids = {}         # float inputs: iteration -> the clients whose vectors were summed
+        self.near_wrap = {}          # decode modulo the field: iteration -> (sums at or beyond the guard, max |Qh|)
         if param.codec() is not None:
             # n updates of magnitude up to clip must fit the 32-bit ring: refuse the run, never wrap (FLM_ERANGE)
             # (packed: no field of the sum may carry into its neighbour, n 2 ceil(clip 2^f) <= 2^(32/pack) - 1)
@@ -89,7 +90,12 @@ class SA_ServiceAgent(Agent):
             kw = {"pack": param.codec_pack()} if param.codec_pack() != 1 else {}
             if param.codec_noise_bits():
                 kw.update(noise_bits=param.codec_noise_bits(), L=param.rotated_len())
-            if param.dp_gauss() is not None:   # the table-sampled share: tail where noise_bits / 2 stands, its own length rule
+            if param.modular() is not None:
+                # the sum is decoded modulo the field: one contributor's field must fit and n B_n may be anything; the
+                # noise stream's length rule is each client's own (its encode call applies it)
+                param.engine().codec_check_modular(param.codec()[0], param.codec()[1], n, pack=param.codec_pack(),
+                                                   noise_bits=param.decode_noise_bits())
+            elif param.dp_gauss() is not None:   # the table-sampled share: tail where noise_bits / 2 stands, its own length rule
                 param.engine().codec_check_gauss(param.codec()[0], param.codec()[1], param.dp_gauss()[1], n,
                                                  pack=param.codec_pack(), L=param.rotated_len())
             else:
@@ -388,6 +394,10 @@ class SA_ServiceAgent(Agent):
         if pack == 1:
             return getattr(on, unpacked)(*head, frac_bits, count)
         kw = {"noise_bits": noise_bits} if noise_bits else {}
+        if param.modular() is not None:   # the _mod form of the same method: the floats and (near, max_abs)
+            mean, self.near_wrap[self.current_iteration] = getattr(on, packed.replace("unpack", "unpack_mod"))(
+                *head, param.rotated_len(), frac_bits, clip, pack, count, guard=param.modular_guard(), **kw)
+            return mean
         return getattr(on, packed)(*head, param.rotated_len(), frac_bits, clip, pack, count, **kw)
 
     def recordTime(self, startTime, categoryName):

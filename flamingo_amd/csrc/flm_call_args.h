@@ -122,6 +122,33 @@ inline const char *codec_error(int frac_bits, float clip, int pack, bool unpacke
     return nullptr;
 }
 
+// flm_codec_check_modular, flm_decode_unpack_mod[_dev], flm_store_unmask_unpack_mod_f32: the packed codec's rule for a
+// sum decoded modulo the field, where carries between the fields are followed instead of excluded.  The codec's own
+// refusals (pack 2 or 4 only, noise_bits, frac_bits, clip, n >= 1), then, FLM_ERANGE (*range set): one contributor's
+// field must fit, 2 B_n <= 2^W - 1, which is the codec's rule at n = 1, and n <= 2^31 - 1.  Nothing bounds n B_n: the
+// decode takes it mod 2^32.  *bias_n: B_n = B + noise_bits / 2 (the table mode passes noise_bits = 2 tail).
+inline const char *modular_error(int frac_bits, float clip, int pack, int noise_bits, int64_t n, bool *range,
+                                 uint32_t *bias_n = nullptr) {
+    if (const char *why = codec_error(frac_bits, clip, pack, false, noise_bits, n < 1 ? n : 1, 0, range, nullptr, bias_n))
+        return why;
+    if (n > 2147483647ll) return *range = true, "a count of contributors must be at most 2^31 - 1";
+    return nullptr;
+}
+// ... and the decode's own: guard in 1..H = 2^(W - 1) (FLM_EINVAL; pack already 2 or 4), L <= 2^32 - 1 parameters
+// (FLM_ERANGE, *range set: the near count is a 32-bit word)
+inline const char *modular_decode_error(int pack, int64_t guard, uint64_t L, bool *range) {
+    *range = false;
+    if (guard < 1 || guard > (int64_t(1) << (32 / pack - 1))) return "guard must be in 1..2^(32 / pack - 1)";
+    if (L > 0xFFFFFFFFull) return *range = true, "the near count of that many parameters does not fit 32 bits";
+    return nullptr;
+}
+// d_out may not alias d_sum: the ceil(L / pack) words and the L floats are disjoint ranges
+inline const char *modular_alias_error(const void *d_sum, const void *d_out, uint64_t L, int pack) {
+    const uintptr_t s = (uintptr_t)d_sum, o = (uintptr_t)d_out;
+    const uint64_t Lw = (L + (uint64_t)pack - 1) / (uint64_t)pack;
+    return s < o + 4 * L && o < s + 4 * Lw ? "out must not overlap sum" : nullptr;
+}
+
 // flm_codec_check_gauss, flm_client_encode_gauss_mask[_dev]: the codec's rule with the table mode of the noise, each
 // client adding Z in [-tail, tail] sampled from a cumulative table of T = 2 tail entries.  tail in 1..512 (the table is
 // at most 8 KiB, and 2 tail <= 1024 is a noise_bits the decodes accept); tail = 0 is not "off": the calls without noise
@@ -488,6 +515,11 @@ inline ArgList client_encode_gauss_mask_args(size_t N, size_t K, size_t L, size_
 // sum (Lw words), out (L floats); Lw = L: the unpacked decode, which may then run in place
 inline ArgList decode_unpack_args(size_t L, size_t Lw) {
     return {{in_place(arg_in(Lw * 4, rows)), in_place(arg_out(L * 4, out))}, 2};
+}
+// flm_decode_unpack_mod: the packed decode's sum and out, and stats (two words: the kernel's atomics land in device
+// memory, never in the bounce buffer)
+inline ArgList decode_unpack_mod_args(size_t L, size_t Lw, bool stats) {
+    return {{in_place(arg_in(Lw * 4, rows)), in_place(arg_out(L * 4, out)), arg_out(8, ec_flags, stats)}, 3};
 }
 // flm_rotate, flm_rotate_clip: x (N rows of L_in floats), out (N rows of L_out floats), key, nonfinite, and the clip's
 // factors and sumsq as flm_l2_clip's (absent for the plain rotation); forward L_in = L and L_out = L_rot, the inverse

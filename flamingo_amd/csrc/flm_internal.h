@@ -73,6 +73,11 @@ hipError_t launch_decode_sum(const uint32_t *d_sum, uint64_t n, double denom, fl
 // not d_sum; both 16-byte aligned
 hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int64_t count_bias, double denom, float *d_out,
                                 hipStream_t stream);
+// The same of a sum taken modulo the field (decode_unpack_mod_kernel): d_out[pack l' + j] = float32(float64(Qh_j) / denom),
+// Qh_j the centred residue of the carry-aware cascade with count_bias = count B_n mod 2^32; guard in 1..2^(32/pack - 1);
+// d_stats two words zeroed by the caller (the kernel adds #{|Qh| >= guard} into [0] and takes max |Qh| into [1]), or NULL
+hipError_t launch_decode_unpack_mod(const uint32_t *d_sum, uint64_t L, int pack, uint32_t count_bias, double denom,
+                                    uint32_t guard, float *d_out, uint32_t *d_stats, hipStream_t stream);
 // Randomised block Hadamard rotation (rotate_kernel): rows of L parameters taken as L_rot = round_up(L, 2^log2_block),
 // log2_block in 4..12; forward reads L floats a row (up to round_up(L, 4) of them, 16 bytes at a time) and writes L_rot,
 // inverse reads L_rot and writes L; d_sign_bits ceil(L_rot / 32) words; d_out may be d_x at equal pitches; d_nonfinite

@@ -1424,6 +1424,92 @@ __global__ __launch_bounds__(256) void decode_unpack_kernel(const uint32_t *__re
     if (l < L) out[l] = unpack_field<P>(sum[l / P], (int)(l % P), cb, denom);
 }
 
+// One step of the modular decode's cascade (include/flamingo_hip.h, "decode modulo the field"): r is the summed word
+// less the fields already done, cb = count B_n mod 2^32.  d = r - cb mod 2^32; Qh, returned, is d's low W bits centred
+// into [-H, H - 1] (a sign extension); r becomes (d - Qh) >> W, whose dropped low W bits are 0, so the field's carry or
+// borrow goes up with it.
+template <int P>
+__device__ __forceinline__ int32_t unpack_mod_step(uint32_t &r, uint32_t cb) {
+    constexpr int W = 32 / P;
+    const uint32_t d = r - cb;
+    const int32_t q = (int32_t)(d << (32 - W)) >> (32 - W);
+    r = (d - (uint32_t)q) >> W;
+    return q;
+}
+
+// Qh as the mean of `count` contributors (denom = count 2^f: decode_unpack_kernel's division and single rounding), with
+// |Qh| taken into the thread's near count and maximum; |Qh| <= H = 2^(W - 1), so Qh = -H counts as H.
+__device__ __forceinline__ float unpack_mod_mean(int32_t q, double denom, uint32_t guard, uint32_t &near, uint32_t &most) {
+    const uint32_t a = (uint32_t)(q < 0 ? -q : q);
+    near += a >= guard ? 1u : 0u;
+    most = a > most ? a : most;
+    return (float)((double)q / denom);
+}
+
+// the four floats of one word (P = 4), or of two (P = 2), field 0 of each word first
+template <int P>
+__device__ __forceinline__ float4 unpack_mod_four(uint32_t S0, uint32_t S1, uint32_t cb, double denom, uint32_t guard,
+                                                  uint32_t &near, uint32_t &most) {
+    float o[4];
+    if constexpr (P == 4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = unpack_mod_mean(unpack_mod_step<4>(S0, cb), denom, guard, near, most);
+    } else {
+        o[0] = unpack_mod_mean(unpack_mod_step<2>(S0, cb), denom, guard, near, most);
+        o[1] = unpack_mod_mean(unpack_mod_step<2>(S0, cb), denom, guard, near, most);
+        o[2] = unpack_mod_mean(unpack_mod_step<2>(S1, cb), denom, guard, near, most);
+        o[3] = unpack_mod_mean(unpack_mod_step<2>(S1, cb), denom, guard, near, most);
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// decode_unpack_kernel's sibling for sums taken modulo the field (SA_ServiceAgent.py:538-540, 605: the final sum, as a
+// mean): out[P l' + j] = float32(float64(Qh_j) / denom), P l' + j < L, Qh_j by the cascade above, so a field of the sum
+// may have carried into the one above it.  The same traffic and launch as decode_unpack_kernel: a quad of words in, 4 P
+// floats out in 16-byte stores, the up to 4 P - 1 parameters behind the last whole quad one per thread (its word's
+// cascade run up to that field).  stats (or NULL): a thread keeps its near count and its maximum over its grid-stride
+// trips, a wave reduces them with __shfl_xor as clipped_add does, and lane 0 issues at most one atomicAdd (stats[0]) and
+// one atomicMax (stats[1]).  Every parameter below L is counted once, by the thread that writes it.
+template <int P>
+__global__ __launch_bounds__(256) void decode_unpack_mod_kernel(const uint32_t *__restrict__ sum, uint64_t L, uint32_t cb,
+                                                                double denom, uint32_t guard, float *__restrict__ out,
+                                                                uint32_t *__restrict__ stats) {
+    const uint64_t quads = L / (4 * P), stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t near = 0, most = 0;
+    for (uint64_t q = t0; q < quads; q += stride) {
+        const uint4 s = reinterpret_cast<const uint4 *>(sum)[q];
+        float4 *dst = reinterpret_cast<float4 *>(out) + P * q;
+        if constexpr (P == 4) {
+            dst[0] = unpack_mod_four<4>(s.x, 0u, cb, denom, guard, near, most);
+            dst[1] = unpack_mod_four<4>(s.y, 0u, cb, denom, guard, near, most);
+            dst[2] = unpack_mod_four<4>(s.z, 0u, cb, denom, guard, near, most);
+            dst[3] = unpack_mod_four<4>(s.w, 0u, cb, denom, guard, near, most);
+        } else {
+            dst[0] = unpack_mod_four<2>(s.x, s.y, cb, denom, guard, near, most);
+            dst[1] = unpack_mod_four<2>(s.z, s.w, cb, denom, guard, near, most);
+        }
+    }
+    const uint64_t l = 4 * P * quads + t0;  // the tail, per element: fewer than 4 P parameters
+    if (l < L) {
+        uint32_t r = sum[l / P];
+        int32_t q = 0;
+        for (int j = 0; j <= (int)(l % P); ++j) q = unpack_mod_step<P>(r, cb);  // the fields below are other threads'
+        out[l] = unpack_mod_mean(q, denom, guard, near, most);
+    }
+    if (!stats) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        near += __shfl_xor(near, off);
+        const uint32_t other = __shfl_xor(most, off);
+        most = other > most ? other : most;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (near) atomicAdd(stats, near);
+        if (most) atomicMax(stats + 1, most);
+    }
+}
+
 // ------------------------------------------------------------ randomised block Hadamard rotation
 // A float -> float step in front of the codec and behind its decode (include/flamingo_hip.h, DESIGN.md section 5,
 // tests/rotate_cases.py): per block of H = 2^h parameters, forward: non-finite -> +0.0 (counted), sign flips,
@@ -1838,6 +1924,21 @@ hipError_t launch_decode_unpack(const uint32_t *d_sum, uint64_t L, int pack, int
         hipLaunchKernelGGL(decode_unpack_kernel<2>, dim3(g), dim3(256), 0, stream, d_sum, L, count_bias, denom, d_out);
     else
         hipLaunchKernelGGL(decode_unpack_kernel<4>, dim3(g), dim3(256), 0, stream, d_sum, L, count_bias, denom, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_unpack_mod(const uint32_t *d_sum, uint64_t L, int pack, uint32_t count_bias, double denom,
+                                    uint32_t guard, float *d_out, uint32_t *d_stats, hipStream_t stream) {
+    if (L == 0) return hipSuccess;
+    if (pack != 2 && pack != 4) return hipErrorInvalidValue;
+    const uint64_t quads = L / (4 * (uint64_t)pack);
+    const unsigned g = (unsigned)std::min<uint64_t>(4096, (quads + 255) / 256 + 1);  // launch_decode_unpack's grid
+    if (pack == 2)
+        hipLaunchKernelGGL(decode_unpack_mod_kernel<2>, dim3(g), dim3(256), 0, stream, d_sum, L, count_bias, denom, guard,
+                           d_out, d_stats);
+    else
+        hipLaunchKernelGGL(decode_unpack_mod_kernel<4>, dim3(g), dim3(256), 0, stream, d_sum, L, count_bias, denom, guard,
+                           d_out, d_stats);
     return hipGetLastError();
 }
 

@@ -1062,7 +1062,7 @@ int flm_device_count(void) {
     return n;
 }
 
-const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip + round_bound + dp_gauss"; }
+const char *flm_version(void) { return "flamingo_hip 0.6 gfx950 items_kernel<S={1,4,16}> (0.4 + shamir_deal, aes_gcm_xor, aes_gcm_seal, aes_gcm_open) + feldman_verify + codec + pack{2,4} + dp_noise + rotate + l2_clip + round_bound + dp_gauss + modular"; }
 
 int flm_init(flm_ctx **out, int device) {
     if (!out) return fail(nullptr, FLM_EINVAL, "flm_init: out is NULL");
@@ -1371,6 +1371,60 @@ int decode_host(flm_ctx *ctx, const uint32_t *sum, size_t L, flm::CodecParams c,
     return hc.finish();
 }
 
+// The modular decode's rules (flm_call_args.h): the admission, then guard and L; *bias_n gets B_n.
+int check_modular(flm_ctx *ctx, const flm::CodecParams &c, int64_t count, uint32_t *bias_n = nullptr) {
+    bool range = false;
+    const char *why = flm::rt::modular_error(c.frac_bits, c.clip, c.pack, c.noise_bits, count, &range, bias_n);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
+int check_modular_decode(flm_ctx *ctx, const flm::CodecParams &c, int64_t count, int64_t guard, size_t L, uint32_t *bias_n) {
+    if (int rc = check_modular(ctx, c, count, bias_n)) return rc;
+    bool range = false;
+    const char *why = flm::rt::modular_decode_error(c.pack, guard, L, &range);
+    return refuse(ctx, why, range ? FLM_ERANGE : FLM_EINVAL);
+}
+
+// The packed decode of a sum taken modulo the field: count B_n mod 2^32 in the bias's place, and the two words of
+// near-wrap evidence, zeroed on the stream first, where the caller wants them.
+int decode_mod_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, flm::CodecParams c, int64_t count, int64_t guard,
+                   float *d_out, uint32_t *d_stats, void *stream) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    uint32_t bias_n = 0;
+    if (int rc = check_modular_decode(ctx, c, count, guard, L, &bias_n)) return rc;
+    if ((uintptr_t)d_stats & 3) return fail(ctx, FLM_EINVAL, "stats must be 4-byte aligned");
+    if (L > 0) {
+        if (!d_sum || !d_out) return fail(ctx, FLM_EINVAL, "NULL argument");
+        if (int rc = refuse(ctx, flm::rt::align16_error({d_sum, d_out}))) return rc;
+        if (int rc = refuse(ctx, flm::rt::modular_alias_error(d_sum, d_out, L, c.pack))) return rc;
+    }
+    if (L == 0 && !d_stats) return 0;
+    FLM_ON_DEVICE(ctx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (d_stats) FLM_HIP(ctx, hipMemsetAsync(d_stats, 0, 2 * sizeof(uint32_t), s));
+    const double denom = (double)count * std::ldexp(1.0, c.frac_bits);
+    const uint32_t cb = (uint32_t)((uint64_t)count * (uint64_t)bias_n);  // count < 2^31, B_n < 2^31: exact, then mod 2^32
+    FLM_HIP(ctx, flm::launch_decode_unpack_mod(d_sum, L, c.pack, cb, denom, (uint32_t)guard, d_out, d_stats, s));
+    return 0;
+}
+
+int decode_mod_host(flm_ctx *ctx, const uint32_t *sum, size_t L, flm::CodecParams c, int64_t count, int64_t guard, float *out,
+                    uint32_t *stats) {
+    if (!ctx) return fail(nullptr, FLM_EINVAL, "ctx is NULL");
+    if (int rc = check_modular_decode(ctx, c, count, guard, L, nullptr)) return rc;
+    if (L == 0) {
+        if (stats) stats[0] = stats[1] = 0;
+        return 0;
+    }
+    if (!sum || !out) return fail(ctx, FLM_EINVAL, "NULL argument");
+    FLM_ON_DEVICE(ctx);
+    HostCopies hc(ctx, ctx->stream);
+    hc.declare(flm::rt::decode_unpack_mod_args(L, flm::rt::packed_words(L, c.pack), stats != nullptr), {sum, out, stats});
+    if (int rc = hc.begin()) return rc;
+    if (int rc = decode_mod_dev(ctx, hc.dev<uint32_t>(0), L, c, count, guard, hc.dev<float>(1), hc.dev<uint32_t>(2), ctx->stream))
+        return rc;
+    return hc.finish();
+}
+
 }  // namespace
 
 int flm_codec_check(int frac_bits, float clip, int64_t n_clients) {
@@ -1472,6 +1526,18 @@ int flm_decode_unpack_noise_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, i
                                 int noise_bits, int64_t count, float *d_out, void *stream) {
     if (ctx && pack == 1) return fail(ctx, FLM_EINVAL, "pack must be 2 or 4");
     return decode_dev(ctx, d_sum, L, {frac_bits, clip, pack, noise_bits, 0}, true, count, d_out, stream);
+}
+
+int flm_codec_check_modular(int frac_bits, float clip, int pack, int noise_bits, int64_t n_clients) {
+    return check_modular(nullptr, {frac_bits, clip, pack, noise_bits, 0}, n_clients);
+}
+int flm_decode_unpack_mod(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int noise_bits,
+                          int64_t count, int guard, float *out, uint32_t *stats) {
+    return decode_mod_host(ctx, sum, L, {frac_bits, clip, pack, noise_bits, 0}, count, guard, out, stats);
+}
+int flm_decode_unpack_mod_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
+                              int noise_bits, int64_t count, int guard, float *d_out, uint32_t *d_stats, void *stream) {
+    return decode_mod_dev(ctx, d_sum, L, {frac_bits, clip, pack, noise_bits, 0}, count, guard, d_out, d_stats, stream);
 }
 
 int flm_prg_expand(flm_ctx *ctx, const uint8_t *seeds, int K, size_t L, uint64_t slot0, uint32_t *out) {

@@ -41,6 +41,7 @@ struct StoreRank {
     uint32_t *out = nullptr;      // unmask output (S words)
     float *fout = nullptr;        // packed codec: this rank's decoded floats (pack x its words), grown on demand
     size_t fout_cap = 0;          // bytes
+    uint32_t *stats = nullptr;    // modular decode: this rank's near count and maximum, allocated on first use
     uint8_t *seeds = nullptr;     // K x 32 + K signs, per unmask
     size_t seeds_cap = 0;
     void *stage[kStoreRing] = {};
@@ -72,6 +73,7 @@ struct flm_store {
     uint32_t *hout = nullptr;    // L words: every rank's shard lands at its offset lo
     float *hfout = nullptr;      // packed codec: L_params floats, every rank's at pack x lo; grown on demand
     size_t hfout_cap = 0;        // bytes
+    uint32_t *hstats = nullptr;  // modular decode: two words per rank, allocated on first use
     bool bounce_busy = false;    // a call that failed after enqueueing may have left DMAs reading them
     std::string err;
 };
@@ -144,6 +146,7 @@ void release(flm_store *st) {
         if (r.S) (void)hipFree(r.S);
         if (r.out) (void)hipFree(r.out);
         if (r.fout) (void)hipFree(r.fout);
+        if (r.stats) (void)hipFree(r.stats);
         if (r.seeds) (void)hipFree(r.seeds);
         if (r.uploaded) (void)hipEventDestroy(r.uploaded);
         if (r.consumed) (void)hipEventDestroy(r.consumed);
@@ -152,6 +155,7 @@ void release(flm_store *st) {
     if (st->hseeds) (void)hipHostFree(st->hseeds);
     if (st->hout) (void)hipHostFree(st->hout);
     if (st->hfout) (void)hipHostFree(st->hfout);
+    if (st->hstats) (void)hipHostFree(st->hstats);
     if (st->t0) (void)hipEventDestroy(st->t0);
     if (st->t1) (void)hipEventDestroy(st->t1);
     if (st->u0) (void)hipEventDestroy(st->u0);
@@ -366,6 +370,8 @@ struct StoreDecode {
     float clip = 0.0f;
     size_t L_params = 0;
     int noise_bits = 0;  // the clients' binomial noise: the packed decode's bias is B + noise_bits / 2
+    int guard = 0;       // > 0: the decode modulo the field (flm_decode_unpack_mod_dev), with this guard
+    uint32_t *stats = nullptr;  // ... and where its two words go: the ranks' counts added, the maximum of their maxima
 };
 
 // flm_store_unmask, and flm_store_unmask_f32 when count > 0: then every device decodes its shard in place
@@ -405,6 +411,9 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
         FLM_SHIP(st, hipHostMalloc(&st->hfout, want, hipHostMallocPortable));
         st->hfout_cap = want;
     }
+    if (dec.stats && !st->hstats)
+        FLM_SHIP(st, hipHostMalloc(&st->hstats, st->rk.size() * 2 * sizeof(uint32_t), hipHostMallocPortable));
+    if (dec.stats) std::memset(st->hstats, 0, st->rk.size() * 2 * sizeof(uint32_t));  // idle; a rank without words stays 0
     FLM_SHIP(st, hipSetDevice(st->rk[0].device));
     FLM_SHIP(st, hipEventRecord(st->u0, flm::rt::stream_of(st->rk[0].ctx)));
     st->bounce_busy = true;
@@ -442,9 +451,15 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
                 FLM_SHIP(st, hipMalloc(&k.fout, want));
                 k.fout_cap = want;
             }
-            if (int rc = flm_decode_unpack_noise_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, dec.noise_bits, count,
-                                                     k.fout, s))
+            if (dec.stats && !k.stats) FLM_SHIP(st, hipMalloc(&k.stats, 2 * sizeof(uint32_t)));
+            if (int rc = dec.guard > 0 ? flm_decode_unpack_mod_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack, dec.noise_bits,
+                                                                   count, dec.guard, k.fout, dec.stats ? k.stats : nullptr, s)
+                                       : flm_decode_unpack_noise_dev(k.ctx, k.out, np, frac_bits, dec.clip, dec.pack,
+                                                                     dec.noise_bits, count, k.fout, s))
                 return sfail(st, rc, std::string("store unmask: ") + flm_last_error(k.ctx));
+            if (dec.stats)
+                FLM_SHIP(st, hipMemcpyAsync(st->hstats + 2 * (&k - st->rk.data()), k.stats, 2 * sizeof(uint32_t),
+                                            hipMemcpyDeviceToHost, s));
             FLM_SHIP(st, hipMemcpyAsync(st->hfout + P * k.lo, k.fout, np * sizeof(float), hipMemcpyDeviceToHost, s));
             continue;
         }
@@ -462,6 +477,13 @@ static int store_unmask(flm_store *st, const uint8_t *seeds, const int8_t *signs
     st->bounce_busy = false;
     if (P > 1) flm::rt::host_copy(st->rk[0].ctx, out, st->hfout, dec.L_params * sizeof(float));
     else flm::rt::host_copy(st->rk[0].ctx, out, st->hout, st->L * sizeof(uint32_t));
+    if (dec.stats) {  // the ranks' near counts added, the maximum of their maxima
+        dec.stats[0] = dec.stats[1] = 0;
+        for (size_t r = 0; r < st->rk.size(); ++r) {
+            dec.stats[0] += st->hstats[2 * r];
+            dec.stats[1] = std::max(dec.stats[1], st->hstats[2 * r + 1]);
+        }
+    }
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, st->u0, st->u1) == hipSuccess) st->unmask_ms = ms;
     return 0;
@@ -504,6 +526,21 @@ int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const
         return flm_store_unmask_unpack_f32(st, seeds, signs, K, L_params, frac_bits, clip, pack, count, out);
     if (pack == 1) return sfail(st, FLM_EINVAL, "pack must be 2 or 4");  // the packed calls' refusal; others by the noise rule
     return store_unmask_unpack(st, seeds, signs, K, L_params, frac_bits, clip, pack, true, noise_bits, count, out);
+}
+
+int flm_store_unmask_unpack_mod_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                    int frac_bits, float clip, int pack, int noise_bits, int64_t count, int guard, float *out,
+                                    uint32_t *stats) {
+    bool range = false;
+    const char *why = flm::rt::modular_error(frac_bits, clip, pack, noise_bits, count, &range);
+    if (!why) why = flm::rt::modular_decode_error(pack, guard, L_params, &range);
+    if (why) return sfail(st, range ? FLM_ERANGE : FLM_EINVAL, why);
+    if (st && st->L != flm::rt::packed_words(L_params, pack))
+        return sfail(st, FLM_EINVAL, "the store's length must be ceil(L_params / pack)");
+    StoreDecode dec;
+    dec.frac_bits = frac_bits, dec.count = count, dec.pack = pack, dec.clip = clip, dec.L_params = L_params;
+    dec.noise_bits = noise_bits, dec.guard = guard, dec.stats = stats;
+    return store_unmask(st, seeds, signs, K, reinterpret_cast<uint32_t *>(out), dec);
 }
 
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms) {

@@ -405,6 +405,33 @@ class MaskEngine:
         self._check(rc, "flm_decode_unpack_noise")
         return out
 
+    def codec_check_modular(self, frac_bits: int, clip: float, n_clients: int = 1, pack: int = 2, noise_bits: int = 0):
+        """Raise unless a packed sum over n_clients can be decoded modulo the field (flm_codec_check_modular): pack 2 or
+        4, one contributor's field fits (2 (ceil(clip * 2^frac_bits) + noise_bits / 2) <= 2^(32/pack) - 1) and
+        n_clients <= 2^31 - 1; n_clients times the bias is not bounded.  The table mode of the noise passes noise_bits =
+        2 * tail.  No device call."""
+        rc = self.lib.flm_codec_check_modular(int(frac_bits), float(clip), int(pack), int(noise_bits), int(n_clients))
+        if rc != 0:     # a call without a context: its text is the library's, not this context's
+            raise RuntimeError(f"flm_codec_check_modular: {self.lib.flm_last_error(None).decode()} (code {rc})")
+
+    def decode_unpack_mod(self, total: np.ndarray, L: int, frac_bits: int, clip: float, pack: int, count: int = 1,
+                          noise_bits: int = 0, guard: int = 1, stats: bool = True):
+        """decode_unpack of a sum taken modulo the field: every field of `total` is read as a residue mod 2^(32/pack),
+        centred into [-H, H - 1], H = 2^(32/pack - 1), and its carry followed into the field above
+        (flm_decode_unpack_mod).  Returns (the L float32 means, (near, max_abs)): near the number of parameters whose
+        centred sum has magnitude >= guard (an integer in 1..H), max_abs the largest magnitude; stats=False asks for
+        neither and returns (means, None)."""
+        total = np.ascontiguousarray(total, dtype=np.uint32)
+        pack = int(pack)
+        if total.ndim != 1 or (pack > 0 and total.shape[0] != -(-L // pack)):
+            raise RuntimeError("total must be a vector of ceil(L / pack) words")
+        out = np.empty(L, dtype=np.float32)
+        st = np.zeros(2, dtype=np.uint32)
+        rc = self.lib.flm_decode_unpack_mod(self.ctx, p_u32(total), L, int(frac_bits), float(clip), pack, int(noise_bits),
+                                            int(count), int(guard), p_f32(out), p_u32(st) if stats else None)
+        self._check(rc, "flm_decode_unpack_mod")
+        return out, ((int(st[0]), int(st[1])) if stats else None)
+
     # ------------------------------------- randomised block Hadamard rotation
     def rotate_check(self, L: int, log2_block: int) -> int:
         """L_rot = round_up(L, 2^log2_block), the length a row of L parameters has once rotated; raises for
@@ -752,6 +779,28 @@ class MaskEngine:
                                                   self._stream_handle(stream))
         self._check(rc, "flm_decode_unpack_noise_dev")
         return out
+
+    def decode_unpack_mod_dev(self, total, out, L: int, frac_bits: int, clip: float, pack: int, count: int = 1, stream=None,
+                              noise_bits: int = 0, guard: int = 1, stats=None):
+        """decode_unpack_dev of a sum taken modulo the field (decode_unpack_mod) on CUDA tensors; out may not overlap
+        total.  stats: a contiguous CUDA tensor of >= 2 32-bit words, zeroed on the stream and then holding (near,
+        max_abs), or None.  Enqueued on `stream`; nothing is synchronised.  Returns (out, stats).
+        flm_decode_unpack_mod_dev."""
+        import torch
+        pack = int(pack)
+        Lw = -(-L // pack) if pack > 0 else L
+        if total.element_size() != 4 or total.numel() < Lw or out.dtype != torch.float32 or out.numel() < L \
+                or not total.is_contiguous() or not out.is_contiguous():
+            raise RuntimeError(f"total must hold >= {Lw} 32-bit words and out >= {L} float32, both contiguous")
+        if stats is not None and (stats.element_size() != 4 or stats.numel() < 2 or not stats.is_contiguous()):
+            raise RuntimeError("stats must hold >= 2 32-bit words, contiguous")
+        rc = self.lib.flm_decode_unpack_mod_dev(self.ctx, ctypes.c_void_p(total.data_ptr()), L, int(frac_bits), float(clip),
+                                                pack, int(noise_bits), int(count), int(guard),
+                                                ctypes.c_void_p(out.data_ptr()),
+                                                ctypes.c_void_p(stats.data_ptr()) if stats is not None else None,
+                                                self._stream_handle(stream))
+        self._check(rc, "flm_decode_unpack_mod_dev")
+        return out, stats
 
     def rotate_dev(self, x, out, L: int, log2_block: int, sign_bits, inverse: bool = False, nonfinite=None, stream=None):
         """Device rotate: x and out (>= N, >= row length) float32 CUDA tensors with unit column stride, rows at their

@@ -150,6 +150,24 @@ class VectorStore:
                     "flm_store_unmask_unpack_noise_f32")
         return out
 
+    def unmask_unpack_mod_f32(self, seeds, signs, L_params: int, frac_bits: int, clip: float, pack: int,
+                              count: int = 1, noise_bits: int = 0, guard: int = 1, stats: bool = True):
+        """unmask_unpack_f32 with the decode modulo the field (MaskEngine.decode_unpack_mod): every device decodes its
+        word shard, the host adds the devices' near counts and takes the maximum of their maxima.  Returns (the
+        L_params float32 means, (near, max_abs)); stats=False asks for no counts and returns (means, None).
+        flm_store_unmask_unpack_mod_f32."""
+        from .engine import _seeds_array, _signs_array
+        seeds = _seeds_array(seeds)
+        signs = _signs_array(signs, seeds.shape[0])
+        out = np.empty(int(L_params), np.float32)
+        st = np.zeros(2, np.uint32)
+        self._check(self.lib.flm_store_unmask_unpack_mod_f32(self.h, p_u8(seeds), p_i8(signs), seeds.shape[0],
+                                                             int(L_params), int(frac_bits), float(clip), int(pack),
+                                                             int(noise_bits), int(count), int(guard), p_f32(out),
+                                                             p_u32(st) if stats else None),
+                    "flm_store_unmask_unpack_mod_f32")
+        return out, ((int(st[0]), int(st[1])) if stats else None)
+
     def unmask_ms(self) -> float:
         """Device time (ms) of the last unmask, seed upload to the end of the D2H (flm_store_unmask_ms)."""
         ms = ctypes.c_float()

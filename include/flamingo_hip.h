@@ -258,7 +258,8 @@ int flm_decode_unpack_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int fra
  * Headroom, worst case, in exact integers, FLM_ERANGE outside it: pack = 1: n * B_n <= 2^31 - 1; packed:
  * n * 2 * B_n <= 2^W - 1, W = 32 / pack.  (f = 4, c = 1, P = 2, b = 30): B_n = 31, n <= 1057; (2, 1, 4, 2):
  * B_n = 5, n <= 25; (7, 1, 2) with n = 255 has no room for any noise.  The bound is worst case, every coin
- * of every client on one side; a probabilistic bound is out of scope.  Length: m * ceil(L / 16) <= 2^32,
+ * of every client on one side; a cohort it refuses decodes modulo the field instead ("decode modulo the field" below,
+ * which bounds no wrap probability either).  Length: m * ceil(L / 16) <= 2^32,
  * because the noise stream's block counter has no high word; else FLM_ERANGE.
  * The decoded mean over |U| contributors carries noise of standard deviation
  * sqrt(|U| * b) / (2 * |U| * 2^f); a dropped client's share is simply absent.  Converting b to an
@@ -350,6 +351,56 @@ int flm_client_encode_gauss_mask_dev(flm_ctx *ctx, const float *d_x, size_t x_pi
                                      float clip, int pack, const uint8_t *d_dither, int tail, const uint64_t *d_cdt,
                                      const uint8_t *d_noise, uint32_t *d_out, size_t out_pitch,
                                      uint32_t *d_clipped, void *stream);
+
+/* ------------------------------ decode modulo the field: centred, carry-aware unpacking of packed sums */
+
+/* The server's half of the distributed discrete Gaussian mechanism (Kairouz, Liu, Steinke, ICML 2021, Algorithm 1): the
+ * sum is taken modulo m and mapped back to [-m/2, m/2).  Here m = M = 2^W per packed field: a field of the summed word
+ * is a residue mod M, and a field that outgrew its W bits has carried into the one above it, which the decode follows
+ * (SA_ServiceAgent.py:538-540, 605: the final sum).  The encode calls, the wire format and the ring sum are untouched:
+ * every client still encodes under the rule with n = 1.  Normative:
+ *   pack P in {2, 4}, W = 32 / P, M = 2^W, H = 2^(W - 1).
+ *   B_n = ceil(c * 2^f) + noise_bits / 2, as above (the table mode passes noise_bits = 2 * tail).
+ *   count = n >= 1; cb = (n * B_n) mod 2^32.
+ *   For a summed word S the true field sums are T_j = Q_j + n * B_n, Q_j the signed sum of the clients' q' at
+ *     parameter P * l' + j, and S = sum_j T_j << (W * j) mod 2^32: carries between fields are allowed.
+ *   The decode works upward through the fields, field 0 first:
+ *     r_0 = S
+ *     for j = 0 .. P - 1:
+ *       d_j  = (r_j - cb) mod 2^32
+ *       v_j  = d_j mod M
+ *       Qh_j = v_j - M * [v_j >= H]                      in [-H, H - 1]
+ *       r_{j+1} = ((d_j - Qh_j) mod 2^32) >> W           logical shift; the low W bits of the difference are 0
+ *       out[P * l' + j] = float32(float64(Qh_j) / (float64(n) * 2^f))    for P * l' + j < L
+ *     the division and the single rounding are flm_decode_unpack's.
+ * Properties:
+ *   1. If every Q_j of the word lies in [-H, H - 1], then Qh_j = Q_j, whatever n * B_n is: also when T_j >= M, and when
+ *      n * B_n >= 2^32.
+ *   2. Whenever the worst-case rule n * 2 * B_n <= M - 1 holds, the output is flm_decode_unpack_noise's, bit for bit.
+ *   3. Wrapping is defined, not undefined: with k_{-1} = 0, Qh_j = centred((Q_j + k_{j-1}) mod M) and
+ *      k_j = (Q_j + k_{j-1} - Qh_j) / M.  A wrapped field is off by a multiple of M and hands k (a few units of
+ *      2^-f / n in the mean) to the field above it.  The sum cannot reveal a wrap: a wrapped Q_j and the in-range value
+ *      it is congruent to give the same word.  The library bounds nothing about the probability of a wrap; it reports
+ *      how close the decoded fields came (below), and the caller chooses the parameters.
+ * Near-wrap evidence: a caller-given integer guard in 1..H (any other value is FLM_EINVAL).  Over the parameters l < L,
+ *   stats[0] = #{ |Qh| >= guard } and stats[1] = max |Qh|, both uint32, Qh = -H counting as H; stats may be NULL.
+ *   L > 2^32 - 1 is FLM_ERANGE.
+ *
+ * flm_codec_check_modular (SA_ServiceAgent.py:538-540, 605: what the server asks before a run with the real n): FLM_EINVAL
+ * for the codec's own refusals (f outside 0..30, a clip not finite and positive), pack not 2 or 4, noise_bits odd, negative
+ * or above 1024, or n_clients < 1; FLM_ERANGE when one contributor's field does not fit (2 * B_n > M - 1, the packed rule
+ * at n = 1) or n_clients > 2^31 - 1.  n * B_n is not bounded.  No context, no device. */
+int flm_codec_check_modular(int frac_bits, float clip, int pack, int noise_bits, int64_t n_clients);
+/* out[0..L) = the decode above of sum[0..ceil(L / pack)) (SA_ServiceAgent.py:538-540, 605: the final sum, as the mean of
+ * `count` contributors), in the place of flm_decode_unpack_noise where the worst-case rule refuses the cohort.
+ * flm_codec_check_modular's rule with n = count, then guard and L as above.  stats: two words, written, or NULL. */
+int flm_decode_unpack_mod(flm_ctx *ctx, const uint32_t *sum, size_t L, int frac_bits, float clip, int pack, int noise_bits,
+                          int64_t count, int guard, float *out, uint32_t *stats);
+/* The same on device buffers (SA_ServiceAgent.py:538-540, 605), enqueued on `stream`; nothing is synchronised.  d_sum and
+ * d_out 16-byte aligned; d_out may not overlap d_sum (FLM_EINVAL); the padding of d_out behind L is not written.  d_stats:
+ * two words on the device, 4-byte aligned, zeroed on the stream first, or NULL. */
+int flm_decode_unpack_mod_dev(flm_ctx *ctx, const uint32_t *d_sum, size_t L, int frac_bits, float clip, int pack,
+                              int noise_bits, int64_t count, int guard, float *d_out, uint32_t *d_stats, void *stream);
 
 /* ------------------------------ randomised block Hadamard rotation of float updates */
 
@@ -892,6 +943,13 @@ int flm_store_unmask_unpack_f32(flm_store *st, const uint8_t *seeds, const int8_
 int flm_store_unmask_unpack_noise_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K,
                                       size_t L_params, int frac_bits, float clip, int pack, int noise_bits,
                                       int64_t count, float *out);
+/* flm_store_unmask_unpack_noise_f32 with the decode modulo the field (SA_ServiceAgent.py:538-540, 605 and "decode modulo
+ * the field" above; SA_ClientAgent.py:300-324 made the input): each device decodes its word shard with
+ * flm_decode_unpack_mod_dev, a word's cascade never leaving the word; the host adds the devices' near counts and takes
+ * the maximum of their maxima into stats (two words, or NULL).  flm_decode_unpack_mod's rules with n = count. */
+int flm_store_unmask_unpack_mod_f32(flm_store *st, const uint8_t *seeds, const int8_t *signs, int K, size_t L_params,
+                                    int frac_bits, float clip, int pack, int noise_bits, int64_t count, int guard,
+                                    float *out, uint32_t *stats);
 /* Device time (ms, rank 0's stream) of the last flm_store_unmask, from its seed upload to the end of
  * its copy of final_sum to the host: the part of the call's wall time the GPU accounts for. */
 int flm_store_unmask_ms(const flm_store *st, float *gpu_ms);

@@ -68,6 +68,11 @@ for _name, _res, _args in (
         ("flm_store_unmask_unpack_noise_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
                                                      ctypes.c_int64, _f32p]),
         ("flm_codec_check_gauss", _int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64, ctypes.c_uint64]),
+        ("flm_codec_check_modular", _int, [_int, ctypes.c_float, _int, _int, ctypes.c_int64]),
+        ("flm_decode_unpack_mod", _int, [_vp, _u32p, _sz, _int, ctypes.c_float, _int, _int, ctypes.c_int64, _int, _f32p,
+                                         _u32p]),
+        ("flm_store_unmask_unpack_mod_f32", _int, [_vp, _u8p, _i8p, _int, _sz, _int, ctypes.c_float, _int, _int,
+                                                   ctypes.c_int64, _int, _f32p, _u32p]),
         ("flm_client_encode_gauss_mask", _int, [_vp, _f32p, _int, _i64p, _u8p, _i8p, _sz, _int, ctypes.c_float, _int, _u8p,
                                                 _int, ctypes.POINTER(ctypes.c_uint64), _u8p, _u32p, _u32p]),
         ("flm_rotate_check", _int, [ctypes.c_uint64, _int, ctypes.POINTER(ctypes.c_uint64)]),
@@ -446,6 +451,30 @@ def decode_unpack(total, L, frac_bits, clip, pack, count=1, noise_bits=0):
     return out
 
 
+def codec_check_modular(frac_bits, clip, pack, noise_bits, n_clients):
+    """Raise unless a packed sum over n_clients can be decoded modulo the field (decode_unpack_mod): pack 2 or 4, one
+    contributor's field fits, 2 (ceil(clip 2^frac_bits) + noise_bits / 2) <= 2^(32 / pack) - 1, and n_clients <=
+    2^31 - 1.  The server's check at set-up in the place of codec_check_noise's worst case (SA_ServiceAgent.py:538-540,
+    605); the table mode of the noise passes noise_bits = 2 tail."""
+    _check(_lib.flm_codec_check_modular(int(frac_bits), float(clip), int(pack), int(noise_bits), int(n_clients)))
+
+
+def decode_unpack_mod(total, L, frac_bits, clip, pack, count=1, noise_bits=0, guard=1):
+    """decode_unpack of a final_sum taken modulo the field (SA_ServiceAgent.py:538-540, 605): every field a residue
+    mod 2^(32 / pack), centred into [-H, H - 1], its carry followed into the field above.  Returns (float32[L], (near,
+    max_abs)): the parameters whose centred sum has magnitude >= guard (an integer in 1..H), and the largest."""
+    if pack not in (2, 4):
+        raise RuntimeError("pack must be 2 or 4")
+    total = np.ascontiguousarray(total, dtype=np.uint32)
+    if total.shape != (-(-L // pack),):
+        raise RuntimeError("vector length error")
+    out, st = np.empty(L, np.float32), np.zeros(2, np.uint32)
+    _check(_lib.flm_decode_unpack_mod(_context(), total.ctypes.data_as(_u32p), L, int(frac_bits), float(clip), int(pack),
+                                      int(noise_bits), int(count), int(guard), out.ctypes.data_as(_f32p),
+                                      st.ctypes.data_as(_u32p)))
+    return out, (int(st[0]), int(st[1]))
+
+
 def codec_check_noise(frac_bits, clip, pack, noise_bits, n_clients, L=0):
     """Raise unless n_clients float updates of magnitude <= clip, each with its share of binomial noise
     (noise_bits fair coins per parameter: at most noise_bits / 2 either way), fit the ring at `pack` (1, 2 or 4)
@@ -615,6 +644,17 @@ class VectorStore:
                                                            int(L_params), int(frac_bits), float(clip), int(pack),
                                                            int(noise_bits), int(count), out.ctypes.data_as(_f32p)))
         return out
+
+    def unmask_unpack_mod_f32(self, seeds, signs, L_params, frac_bits, clip, pack, count=1, noise_bits=0, guard=1):
+        """unmask_unpack_f32 with the decode modulo the field (decode_unpack_mod; :538-540, :605): returns
+        (float32[L_params], (near, max_abs)), the devices' near counts added and the maximum of their maxima."""
+        sd, sg, K = _seed_arrays(seeds, signs)
+        out, st = np.empty(int(L_params), np.float32), np.zeros(2, np.uint32)
+        self._check(_lib.flm_store_unmask_unpack_mod_f32(self.h, sd.ctypes.data_as(_u8p), sg.ctypes.data_as(_i8p), K,
+                                                         int(L_params), int(frac_bits), float(clip), int(pack),
+                                                         int(noise_bits), int(count), int(guard),
+                                                         out.ctypes.data_as(_f32p), st.ctypes.data_as(_u32p)))
+        return out, (int(st[0]), int(st[1]))
 
     def reset(self):
         self._check(_lib.flm_store_reset(self.h))

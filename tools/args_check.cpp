@@ -134,6 +134,7 @@ static void check_round_lists() {
                     for (int pack : {2, 4}) {
                         through_bounce(client_encode_mask_args(N, K, L, packed_words(L, pack), opt & 1, false, opt & 2));
                         if (!opt) through_bounce(decode_unpack_args(L, packed_words(L, pack)));
+                        if (opt < 2) through_bounce(decode_unpack_mod_args(L, packed_words(L, pack), opt & 1));
                     }
                     for (int pack : {1, 2, 4})
                         through_bounce(client_encode_mask_args(N, K, L, packed_words(L, pack), opt & 1, true, opt & 2));
@@ -303,6 +304,33 @@ static void check_round_rules() {
     const ArgList ge = client_encode_gauss_mask_args(3, 7, 5, 2, false, 64, true);
     CHECK(ge.n == 7 && ge.a[3].present && ge.a[3].width == 96 && ge.a[4].width == 512 && ge.a[4].slot == ec_dig && !ge.a[4].is_out &&
           !ge.a[2].present && ge.a[5].is_out && ge.a[5].in_place && ge.a[5].width == 8 && ge.a[6].is_out && !names_slot_twice(ge));
+    // the decode modulo the field: the codec's own refusals, pack 2 or 4 alone, then one contributor's field and the
+    // count (both FLM_ERANGE); n B_n is free: every cohort the worst-case rule stops one short of is admitted
+    for (int pack : {0, 1, 3, 8, -2}) CHECK(modular_error(4, 1.0f, pack, 0, 1, &range) && !range);
+    for (int b : {-2, 1, 31, 1026}) CHECK(modular_error(4, 1.0f, 2, b, 1, &range) && !range);
+    CHECK(modular_error(31, 1.0f, 2, 0, 1, &range) && !range && modular_error(-1, 1.0f, 2, 0, 1, &range) && !range);
+    for (float c : {0.0f, -1.0f, INFINITY, NAN}) CHECK(modular_error(4, c, 2, 0, 1, &range) && !range);
+    CHECK(modular_error(4, 1.0f, 2, 0, 0, &range) && !range && modular_error(4, 1.0f, 2, 0, -5, &range) && !range);
+    CHECK(!modular_error(7, 1.0f, 2, 0, 256, &range, &Bn) && Bn == 128 && !range);          // the packed rule stops at 255
+    CHECK(!modular_error(4, 1.0f, 2, 30, 1058, &range, &Bn) && Bn == 31 && !modular_error(4, 1.0f, 2, 64, 4096, &range, &Bn) && Bn == 48);
+    CHECK(!modular_error(2, 1.0f, 4, 2, 26, &range, &Bn) && Bn == 5 && !modular_error(7, 1.0f, 2, 2, 255, &range, &Bn) && Bn == 129);
+    CHECK(!modular_error(0, 1.0f, 4, 4, 2147483647ll, &range, &Bn) && Bn == 3 && !range);   // n B_n past 2^32
+    CHECK(modular_error(0, 1.0f, 4, 4, 2147483648ll, &range) && range);
+    CHECK(!modular_error(6, 1.9f, 4, 10, 1, &range, &Bn) && Bn == 127);                      // 254 <= 255
+    CHECK(modular_error(6, 1.9f, 4, 12, 1, &range) && range && modular_error(7, 1.0f, 4, 0, 1, &range) && range);
+    CHECK(!modular_error(14, 1.0f, 2, 1024, 1, &range, &Bn) && Bn == 16896);                 // 33792 <= 65535
+    CHECK(modular_error(15, 1.0f, 2, 0, 1, &range) && range && modular_error(30, 2.0f, 2, 0, 1, &range) && range);
+    // ... its guard in 1..H and its L within 32 bits; out may not overlap sum
+    CHECK(!modular_decode_error(2, 1, 5, &range) && !modular_decode_error(2, 32768, 5, &range) && !modular_decode_error(4, 128, 0, &range));
+    CHECK(modular_decode_error(2, 0, 5, &range) && !range && modular_decode_error(2, 32769, 5, &range) && !range);
+    CHECK(modular_decode_error(4, 129, 5, &range) && !range && modular_decode_error(4, -1, 5, &range) && !range);
+    CHECK(!modular_decode_error(2, 1, 0xFFFFFFFFull, &range) && modular_decode_error(2, 1, 0x100000000ull, &range) && range);
+    CHECK(modular_alias_error(buf, buf, 8, 2) && modular_alias_error(buf + 16, buf, 8, 2) && modular_alias_error(buf, buf + 12, 8, 2));
+    CHECK(!modular_alias_error(buf, buf + 16, 8, 2) && !modular_alias_error(buf + 16, buf, 4, 4) && modular_alias_error(buf + 16, buf, 5, 4));
+    const ArgList md = decode_unpack_mod_args(5, 2, true), mn = decode_unpack_mod_args(5, 2, false);
+    CHECK(md.n == 3 && md.a[0].width == 8 && md.a[0].in_place && md.a[1].width == 20 && md.a[1].is_out && md.a[1].in_place &&
+          md.a[2].present && md.a[2].is_out && !md.a[2].in_place && md.a[2].width == 8 && md.a[2].slot == ec_flags &&
+          !mn.a[2].present && !names_slot_twice(md));
     CHECK(!decode_error(0, 1) && !decode_error(30, 1) && decode_error(31, 1) && decode_error(-1, 1) && decode_error(16, 0));
     // the rotation's rule: h in 4..12, L > 0, L_rot = round_up(L, 2^h), L_rot / 32 sign words within 2^36 PRG slots
     uint64_t L_rot = 0;
